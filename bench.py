@@ -5,9 +5,13 @@ A "step" = one Gauss-Newton iteration (one Thallo_ProblemStep: PCGInit + lIterat
 iterations + PCGLinearUpdate) on one synthetic 2048x2048 image_warping instance already resident
 in HBM (reference workload: examples/image_warping/src/main.cpp:131-149, 8 GN x 100 PCG).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2048] [--liters 100]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2048] [--liters 100] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0).  `value` = whole-job PCG iterations per second.
+Prints ONE JSON line (rank 0).  `value` = whole-job PCG iterations per second, `ms_per_step` = milliseconds per timed step.
+A plain run sets up, warms up, times the K steps and prints the line; whatever takes runs of its own (`roofline.applyjtj_standalone`,
+`small_working_sets`, `cpu_baseline`) is measured with `--full` only (`--no-small` / `--no-cpu-baseline` leave parts of it out).
+`--dump-outputs DIR` (N = 1): after the timed steps, what the timed path computed in its last step -- the unknowns Offset and Angle
+and the cost -- as DIR/<name>.npy (float32 / float64, at most 64 MB in all: past that a fixed, seeded sample of each array's elements).
 `roofline` = the dominant kernel (PCGIteration: one launch = a whole PCG iteration; since round 5 p_k goes into a ring of planes, 57.1 B/pixel, and the delta update is a
 launch of its own next to the loop) -- its OWN duration (begin-to-end timestamps of two HIP events handed to the launch itself, hipExtLaunchKernelGGL) sampled at every
 53rd launch of it INSIDE the timed region (`roofline.method_version` 2; version 1, rounds 1-4: events recorded around the launch, dispatch gap included, on 74.8 B/pixel --
@@ -59,10 +63,36 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=2048)
     ap.add_argument("--liters", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-small", action="store_true")              # skip the extra 512^2 / 2048x256 timings (resident PCG loop vs launch per iteration)
+    ap.add_argument("--full", action="store_true")                  # also the measurements that take runs of their own: standalone applyJTJ, small working sets, CPU baseline
+    ap.add_argument("--no-cpu-baseline", action="store_true")       # (with --full) skip the CPU baseline
+    ap.add_argument("--no-small", action="store_true")              # (with --full) skip the extra 512^2 / 2048x256 timings (resident PCG loop vs launch per iteration)
     ap.add_argument("--sample-period", type=int, default=-1)      # HIP events around every N-th launch of each kernel inside the timed region (default 53; 0: none, roofline from the loop's event pair)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)  # write the last timed step's outputs as DIR/<name>.npy
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array of `arrays` (name -> float32 / float64 numpy array) as path/<name>.npy.  If they hold more than `limit` bytes in all,
+    each array is replaced by the same fixed, seeded sample of its flattened elements (sorted indices, seed 0) that brings the total under it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    room = limit - 256 * len(arrays)                            # (256 bytes per file for the .npy header)
+    frac = 1.0 if total <= room else max(room, 0) / total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if frac < 1.0:
+            k = max(1, int(a.size * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def standalone_applyjtj(torch, W, H, p_np, reps=50):
@@ -213,6 +243,8 @@ def main():
     s.set_kernel_sampling(0)
     ks = s.kernel_stats()
     final_cost = s.current_cost()
+    # what a caller of the timed path receives after its last step: the unknowns (updated in place) and the cost
+    outputs = {"offset": dev[0].cpu().numpy(), "angle": dev[1].cpu().numpy(), "cost": np.array([final_cost], np.float64)} if args.dump_outputs else None
     ring = "PCGDeltaUpdate" in ks
     persistent = "PCGLoopPersistent" in ks
     assert s.step(params) == 0                 # budget used up: finalises the plan and its performance summary
@@ -240,8 +272,6 @@ def main():
     ach = dom_bytes * npx / (step1_ms * 1e-3) / 1e9
     # the loop's bytes per iteration: the marching launch + 12 per pending term + delta read and written once per PCGDeltaUpdate launch
     sched_bytes = dom_bytes + 12.0 + 24.0 * (ks.get("PCGDeltaUpdate", {}).get("launches", 0) / K) / L_it
-    sa_ms = standalone_applyjtj(torch, W, H, p)
-    sa_gbs = ALG_BYTES_APPLYJTJ * npx / (sa_ms * 1e-3) / 1e9
     traffic, traffic_source = None, None
     for rel in (os.path.join("profiles", "traffic_latest.json"),):
         tf = os.path.join(ROOT, rel)
@@ -287,16 +317,19 @@ def main():
                                        "avg_launch_ms": ks["PCGDeltaUpdate"]["mean_ms"]} if ring and one_kernel and ks.get("PCGDeltaUpdate", {}).get("samples") else None),
                      # the same launch priced with SURVEY.md 8d's bytes of the reference's three-kernel formulation -- a speed-up figure, not a
                      # roofline fraction (it exceeds the HBM peak because the schedule removes 45 % of those bytes)
-                     "reference_formulation": {"bytes_per_pixel": ref_bytes, "equivalent_GBps": ref_bytes * npx / (step1_ms * 1e-3) / 1e9},
-                     "applyjtj_standalone": {"algorithmic_bytes_per_pixel": ALG_BYTES_APPLYJTJ, "avg_launch_ms": sa_ms,
-                                             "achieved": sa_gbs, "frac": sa_gbs / HBM_PEAK_GBS}},
+                     "reference_formulation": {"bytes_per_pixel": ref_bytes, "equivalent_GBps": ref_bytes * npx / (step1_ms * 1e-3) / 1e9}},
     }
     if not one_kernel:      # z-free two-kernel schedule: read r 12, Ap 12, flags 1; write r 12
         step2_ms = ks["PCGStep2"]["mean_ms"]
         out["roofline"]["pcg_step2"] = {"algorithmic_bytes_per_pixel": 37, "avg_launch_ms": step2_ms, "achieved": 37 * npx / (step2_ms * 1e-3) / 1e9}
+    if args.full:           # (runs of its own, after the timed region)
+        sa_ms = standalone_applyjtj(torch, W, H, p)
+        sa_gbs = ALG_BYTES_APPLYJTJ * npx / (sa_ms * 1e-3) / 1e9
+        out["roofline"]["applyjtj_standalone"] = {"algorithmic_bytes_per_pixel": ALG_BYTES_APPLYJTJ, "avg_launch_ms": sa_ms,
+                                                  "achieved": sa_gbs, "frac": sa_gbs / HBM_PEAK_GBS}
     # BASELINE config 1's size and one rank's slab of the 8-GPU run: working sets that fit the chip's registers run the whole PCG loop of a GN step in ONE
     # launch (thallo_hip_iw_pcg_resident); the launch-per-iteration schedule of the same plan beside it (THALLO_RESIDENT=0).  Not the headline metric: extra keys.
-    if not args.no_small:
+    if args.full and not args.no_small:
         def small(w, h, resident):
             os.environ["THALLO_RESIDENT"] = "1" if resident else "0"
             try:
@@ -354,7 +387,7 @@ def main():
                 os.environ.pop("THALLO_RESIDENT", None)
         out["small_working_sets"]["shape_from_shading_640x480"] = {"gn": {"resident_loop": small_sfs(True, False), "launch_per_iteration": small_sfs(False, False)},
                                                                     "lm": {"resident_loop": small_sfs(True, True), "launch_per_iteration": small_sfs(False, True)}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as orc
         q = syn.image_warping(W, H)
         sample_l = L_it
@@ -366,6 +399,8 @@ def main():
                                "note": "baseline only (an OpenMP restatement, not a tuned CPU solver); the GPU / CPU ratio says nothing about kernel quality",
                                "sample": f"1 GN step x {sample_l} PCG iterations of the same {W}x{H} instance, OpenMP port of the "
                                          "reference algorithm (oracle/cpu_port_image_warping.c)"}
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(out))
 
 

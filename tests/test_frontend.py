@@ -140,20 +140,30 @@ REF_PAIRS = [("examples/image_warping/image_warping.t", "image_warping"), ("exam
              ("tests/minimal_graph/laplacian.t", "laplacian_graph"), ("tests/minimal/laplacian.t", "laplacian_image_shipped_guard")]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree exists in the build container only")
-@pytest.mark.parametrize("rel,mine", REF_PAIRS)
-def test_bundled_energies_are_the_references_energies(rel, mine):
-    """The bundled .t files are re-written specifications (different text).  Run through the front-end, each of them and the reference's own file (read
-    in place, never copied) produce the SAME translation unit -- the same expression DAG per residual component, the same unknown accesses, the same
-    guards -- up to the residuals' names.  So everything the GPU tests establish about a bundled energy (oracle trajectories, gold PNGs, generated
-    vs hand-written plugins) is established about the energy the reference's file states, not about a restatement of it."""
+def _unit_digests(path):
+    """SHA-256 of what the front-end makes of an energy file up to the residuals' names: its translation unit, and its declarations without the
+    residuals' names and schedule marks."""
+    import hashlib
     import re
-    norm = lambda t: re.sub(r"// ---- residual \w+", "// ---- residual R", t)
-    a, b = norm(_text(os.path.join("/root/reference", rel), 1)), norm(_text(thallo_amd.energy_file(mine), 1))
-    assert a == b
-    da, db = _text(os.path.join("/root/reference", rel), 0), _text(thallo_amd.energy_file(mine), 0)
-    strip = lambda d: [re.sub("( J| JtJ| Jp)+$", "", re.sub("^residual [^ ]+", "residual", ln)) for ln in d.splitlines()]
-    assert strip(da) == strip(db)
+    unit = re.sub(r"// ---- residual \w+", "// ---- residual R", _text(path, 1))
+    decl = "\n".join(re.sub("( J| JtJ| Jp)+$", "", re.sub("^residual [^ ]+", "residual", ln)) for ln in _text(path, 0).splitlines())
+    return {"unit_sha256": hashlib.sha256(unit.encode()).hexdigest(), "declarations_sha256": hashlib.sha256(decl.encode()).hexdigest()}
+
+
+@pytest.mark.parametrize("rel,mine", REF_PAIRS)
+def test_bundled_energies_are_the_references_energies(golden_dir, rel, mine):
+    """The bundled .t files are re-written specifications (different text).  Run through the front-end, each of them and the reference's own file
+    produce the SAME translation unit -- the same expression DAG per residual component, the same unknown accesses, the same guards -- up to the
+    residuals' names.  The reference's side is recorded as digests in tests/golden/reference_energy_units.json (tests/golden/make_reference_unit_digests.py,
+    run against a checkout of the reference whenever the front-end's output changes).  So everything the GPU tests establish about a bundled energy
+    (oracle trajectories, gold PNGs, generated vs hand-written plugins) is established about the energy the reference's file states, not about a
+    restatement of it."""
+    import json
+    recorded = json.load(open(os.path.join(golden_dir, "reference_energy_units.json")))[rel]
+    assert recorded["bundled"] == mine
+    got = _unit_digests(thallo_amd.energy_file(mine))
+    assert got["unit_sha256"] == recorded["unit_sha256"]
+    assert got["declarations_sha256"] == recorded["declarations_sha256"]
 
 
 REF = "/root/reference"

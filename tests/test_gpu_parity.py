@@ -239,11 +239,11 @@ def test_image_warping_resident_loop_reports_a_wait_that_ran_out(torch):
 
 
 def test_bench_py_single_gpu_line(torch):
-    """bench.py as the driver runs it (N = 1), shortened: one JSON line with the contract's keys, the roofline object computed from this run's own events and the CPU baseline leg
-    (round 6: the line broke once when timingLevel 0 stopped recording the coarse events bench.py reads -- nothing in the suite ran it on one GPU)."""
+    """bench.py --full as the driver runs it (N = 1), shortened: one JSON line with the contract's keys, the roofline object computed from this run's own events and the CPU
+    baseline leg (round 6: the line broke once when timingLevel 0 stopped recording the coarse events bench.py reads -- nothing in the suite ran it on one GPU)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-small"], capture_output=True, text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-small"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["metric"] == "pcg_iters_per_sec" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 1000 and d["higher_is_better"] is True
@@ -252,6 +252,34 @@ def test_bench_py_single_gpu_line(torch):
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and 0.3 < rf["frac"] < 1.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-6, rf
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"], cb
+    assert rf["applyjtj_standalone"]["avg_launch_ms"] > 0, rf
+
+
+def test_bench_py_plain_run_dumps_the_last_steps_outputs(torch, tmp_path):
+    """A plain bench.py run times exactly --steps steps (`ms_per_step` = one of them), measures nothing that takes a run of its own, and with --dump-outputs
+    writes what the timed path computed in its last step: the unknowns and the cost.  Two runs with the same arguments write the same outputs."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W = H = 256
+    start = syn.image_warping(W, H)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--size", str(W), "--liters", "20", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["metric"] == "pcg_iters_per_sec" and line["unit"] == "PCG iterations/s" and line["dtype"] == "f32"
+        assert line["ms_per_step"] > 0 and abs(line["ms_per_step"] - 20 / line["value"] * 1e3) <= 1e-9 * line["ms_per_step"], line
+        assert "cpu_baseline" not in line and "small_working_sets" not in line and "applyjtj_standalone" not in line["roofline"], sorted(line)
+        out = {n: np.load(d / f"{n}.npy") for n in ("offset", "angle", "cost")}
+        assert sorted(os.listdir(d)) == ["angle.npy", "cost.npy", "offset.npy"]
+        assert out["offset"].shape == (H, W, 2) and out["offset"].dtype == np.float32 and out["angle"].shape == (H, W) and out["angle"].dtype == np.float32
+        assert out["cost"].dtype == np.float64 and out["cost"][0] == line["final_cost"]
+        assert np.isfinite(out["offset"]).all() and not np.array_equal(out["offset"], start[0])
+        dumps.append(out)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 @pytest.mark.parametrize("W,H,lit", [(512, 512, 100), (2048, 256, 40), (2048, 512, 40), (1024, 1024, 25), (1200, 800, 16), (256, 256, 30), (640, 480, 25), (130, 7, 12), (124, 64, 9), (250, 2, 5), (126, 130, 7)])

@@ -1,4 +1,4 @@
-"""Turn the rocprofv3 outputs that tools/profile.sh left in gpurun_out/ into the small committed summaries under
+"""Turn the rocprofv3 outputs that tools/profile.sh left in $PROFILE_OUT (default profile_out/) into the small committed summaries under
 profiles/<round>/ and profiles/traffic_latest.json (read by bench.py for roofline.traffic)."""
 import collections, csv, glob, json, os, shutil, sys
 
@@ -6,8 +6,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r05"
 out = os.path.join(ROOT, "profiles", rnd)
 os.makedirs(out, exist_ok=True)
-g = os.path.join(ROOT, "gpurun_out")
-newest = lambda pat: max(glob.glob(pat), key=os.path.getmtime)      # gpurun_out/ accumulates earlier runs
+g = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out"))
+newest = lambda pat: max(glob.glob(pat), key=os.path.getmtime)      # the output directory accumulates earlier runs
 ks = newest(os.path.join(g, "prof_kt", "*", "*_kernel_stats.csv"))
 shutil.copy(ks, os.path.join(out, "bench_kernel_stats.csv"))
 for f in ("bench_under_rocprof.json", "bench_plain.json"):
