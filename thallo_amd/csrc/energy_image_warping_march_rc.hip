@@ -141,6 +141,9 @@ __device__ __forceinline__ void take(RawRc<DMODE>& d, const RawRc<DMODE>& s)
     if (DMODE == 2) { take4u(d.ppo, s.ppo); take2u(d.ppa, s.ppa); }
 }
 
+template <int V> struct IC { static constexpr int value = V; };      // a compile-time argument of the row step
+enum { PH_ENTER = 0, PH_S1 = 1, PH_FULL = 2 };                       // what a row step does (k_iter_march_rc)
+
 struct PRow { v2f xy[2]; float pa[2]; };                         // p of a lane's pixel pair in one row: (x, y) of each pixel as a register pair (iw_march.hpp jtjp_pair_xy)
 struct GRow { v2f cs[2], gx[2]; float a[2]; unsigned f; };       // (cos, sin) of Angle and (sin, -cos), the active bits as 0 / 1, the two flags bytes
 struct RRow { v2f xy[2]; float ra[2]; };                         // r_k
@@ -207,22 +210,28 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
 
     typedef RawRc<DMODE> RawT;
     RawT slot[DEPTH];
-    auto issue = [&](RawT& s, int t) {
-        const unsigned tc = (unsigned)(t < 0 ? 0 : t > g.H - 1 ? g.H - 1 : t), row = tc * (unsigned)W2;
+    const unsigned W2u = (unsigned)W2;
+    const int t_first = ya - 2, t_last = yb + 1;              // rows of p_{k-1} / cs / flags to take
+    // The loads of the step that takes row t-DEPTH: row tn = t of p_{k-1} / cs / flags, row tn-1 of r_{k-1} (delta, p_{k-2}).  CL: the rows may need clamping
+    // (into the image, to t_last, delta / p_{k-2} into the segment); the steady loop's rows never do, so its row offsets are plain multiples of the row pitch.
+    auto issue = [&](RawT& s, int tn, auto CL_) __attribute__((always_inline)) {
+        constexpr bool CL = decltype(CL_)::value;
+        if (CL && tn > t_last) tn = t_last;
+        const unsigned tc = CL ? (unsigned)(tn < 0 ? 0 : tn > g.H - 1 ? g.H - 1 : tn) : (unsigned)tn, row = tc * W2u;
         s.po = bld4<nt_pin>(RS_P, vo16, row * 16u); s.pa = bld2<nt_pin>(RS_P, vo8, angle0 + row * 8u);
         s.cs = bld4<nt_const>(RS_CS, vo16, row * 16u);
         const unsigned par = row & 1u;
         s.f = bld1<nt_const>(RS_F, par ? vf1 : vf0, (row - par) * 2u);
-        const unsigned tr = (unsigned)(t - 1 < 0 ? 0 : t - 1 > g.H - 1 ? g.H - 1 : t - 1), rrow = tr * (unsigned)W2;
+        const unsigned tr = CL ? (unsigned)(tn - 1 < 0 ? 0 : tn - 1 > g.H - 1 ? g.H - 1 : tn - 1) : (unsigned)(tn - 1), rrow = tr * W2u;
         s.ro = bld4<nt_ra>(RS_R, vo16, rrow * 16u); s.ra = bld2<nt_ra>(RS_R, vo8, angle0 + rrow * 8u);
         if (DMODE != 1) {       // delta (and p_{k-2}) of the segment's own rows only (the halo rows re-read a row of the segment, unused)
-            const unsigned td = (unsigned)(t - 1 < ya ? ya : t - 1 > yb - 1 ? yb - 1 : t - 1), drow = td * (unsigned)W2;
+            const unsigned td = CL ? (unsigned)(tn - 1 < ya ? ya : tn - 1 > yb - 1 ? yb - 1 : tn - 1) : (unsigned)(tn - 1), drow = td * W2u;
             s.dlo = bld4<nt_delta>(RS_D, vo16, drow * 16u); s.dla = bld2<nt_delta>(RS_D, vo8, angle0 + drow * 8u);
             if (DMODE == 2) { s.ppo = bld4<false>(RS_Q, vo16, drow * 16u); s.ppa = bld2<false>(RS_Q, vo8, angle0 + drow * 8u); }
         }
     };
 
-    // rings of four rows, indexed by the row modulo 4 (compile-time inside a trip of four rows)
+    // rings of four rows, indexed by the row's position inside a trip of four (compile-time)
     PRow pp[4], pk[4]; GRow gg[4]; RRow rr[2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -238,135 +247,159 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
 
     float acc = 0.0f; double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     const unsigned mxin = xin ? 0xffffu : 0u;
+
+    // The row step that takes row t, at position J of its trip, specialised by phase PH (compile-time):
+    //   PH_ENTER:  row t enters the p_{k-1} / geometry rings (rows ya-2, ya-1);
+    //   PH_S1:     ... and A p_{k-1}(t-1) -> r_k(t-1), p_k(t-1), stored for the segment's own rows (rows ya, ya+1);
+    //   PH_FULL:   ... and A p_k(t-2) with the iteration's sums of row t-2 (rows ya+2 .. yb+1: exactly the segment's rows t-2).
+    // A segment takes rows ya-2 .. yb+1 of p_{k-1}, R + 4 steps, and no step works on a row nothing consumes.  (The earlier loop started DEPTH rows early with
+    // empty slots and rounded up to whole trips: at 35 rows, 44 full steps against 35 full + 2 + 2 partial ones here.  The steps it dropped added exact zeros
+    // to the sums -- a 0 multiplicand, M^-1 = 0 -- so r, p, delta and the sums keep their bits.)
+    // CL: the step's rows may need clamping (head and tail); the steady loop runs only steps whose rows are all inside the image and the segment.
+    // The row step itself is BRANCH-FREE: lanes outside the image go through the same arithmetic on zeros / finite garbage that nothing consumes -- pixels
+    // outside the image are INACTIVE (flags 0: every term that would read them is multiplied by 0) -- and only the stores (exec mask) and the sums (a 0 / 1
+    // multiplicand, M^-1 = 0) are predicated.  A uniform branch around the arithmetic is a merge point with a phi per ring register.
+    auto step = [&](int t, auto J_, auto PH_, auto CL_) __attribute__((always_inline)) {
+        constexpr int j = decltype(J_)::value, PH = decltype(PH_)::value;
+        constexpr bool CL = decltype(CL_)::value;
+        // ring roles at this step: row t -> index j, t-1 -> j+3, t-2 -> j+2, t-3 -> j+1 (mod 4)
+        PRow& p0 = pp[j % 4]; const PRow& p1 = pp[(j + 3) % 4]; const PRow& p2 = pp[(j + 2) % 4];
+        GRow& g0 = gg[j % 4]; const GRow& g1 = gg[(j + 3) % 4]; const GRow& g2 = gg[(j + 2) % 4]; const GRow& g3 = gg[(j + 1) % 4];
+        PRow& k1 = pk[(j + 3) % 4]; const PRow& k2 = pk[(j + 2) % 4]; const PRow& k3 = pk[(j + 1) % 4];
+        RRow& r1 = rr[(j + 1) % 2]; const RRow& r2 = rr[j % 2];
+        RawT cur;
+        take(cur, slot[j % DEPTH]);                  // (the only place that waits for memory)
+        fence_order();                               // the refill stays behind the moves ...
+        issue(slot[j % DEPTH], t + DEPTH, CL_);
+        fence_order();                               // ... and in front of the arithmetic
+        // ---- row t enters the p_{k-1} / geometry rings (outside the image: inactive)
+        {
+            const bool rowok = !CL || (t >= 0 && t < g.H);
+            const unsigned par = ((unsigned)t * W2u) & 1u;
+            const unsigned fl = (cur.f >> (par ? 16u - sh0 : sh0)) & (rowok ? mxin : 0u);
+            p0.xy[0] = uf2(cur.po.x, cur.po.y); p0.xy[1] = uf2(cur.po.z, cur.po.w); p0.pa[0] = uf(cur.pa.x); p0.pa[1] = uf(cur.pa.y);
+            g0.cs[0] = uf2(cur.cs.x, cur.cs.y); g0.cs[1] = uf2(cur.cs.z, cur.cs.w); g0.f = fl;
+            g0.gx[0] = v2f{ g0.cs[0].y, -g0.cs[0].x }; g0.gx[1] = v2f{ g0.cs[1].y, -g0.cs[1].x };
+            g0.a[0] = (float)(fl & 1u); g0.a[1] = (float)((fl >> 8) & 1u);
+        }
+        // ---- row u = t-1: A p_{k-1}(u) -> r_k(u), p_k(u)
+        if constexpr (PH >= PH_S1) {
+            const int u = t - 1;
+            const float4 m0 = lut[g1.f & 31u], m1 = lut[(g1.f >> 8) & 31u];      // (M^-1 offsets, M^-1 angle, w_fit^2 or 0)
+            const float wfit[2] = { m0.z, m1.z };
+            v2f axy[2]; float av[2];
+            jtjp_pair_xy(p2, p1, p0, g2, g1, g0, g2.a, g1.a, g0.a, wfit, wr2, axy, av);
+            // a ghost row of the slab: the row above the strip's first segment / below its last one (wave-uniform; only in the head and the tail)
+            const bool ghost_row = SLAB && CL && ((u == ya - 1 && ya == g.row0 && u >= 0) || (u == yb && yb == g.row1 && u < g.H));
+            if (ghost_row) {            // A p_{k-1} of a ghost row: what the exchange delivered (a blocking load, twice per boundary wave and launch)
+                const unsigned row = (unsigned)u * W2u;
+                const u32x4 ao = bld4<false>(RS_AI, vo16, row * 16u); const u32x2 aa = bld2<false>(RS_AI, vo8, angle0 + row * 8u);
+                axy[0] = uf2(ao.x, ao.y); axy[1] = uf2(ao.z, ao.w); av[0] = uf(aa.x); av[1] = uf(aa.y);
+            }
+            v2f rxy[2] = { uf2(cur.ro.x, cur.ro.y), uf2(cur.ro.z, cur.ro.w) }; float rq[2] = { uf(cur.ra.x), uf(cur.ra.y) };
+            rxy[0] = fma2(-alpha, axy[0], rxy[0]); rxy[1] = fma2(-alpha, axy[1], rxy[1]);
+            rq[0] = __builtin_fmaf(-alpha, av[0], rq[0]); rq[1] = __builtin_fmaf(-alpha, av[1], rq[1]);
+            const float mo[2] = { m0.x, m1.x }, ma[2] = { m0.y, m1.y };
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                k1.xy[q] = mo[q] * rxy[q] + beta * p1.xy[q]; k1.pa[q] = ma[q] * rq[q] + beta * p1.pa[q];
+                r1.xy[q] = rxy[q]; r1.ra[q] = rq[q];
+            }
+            const bool mine = !CL || (u >= ya && u < yb);
+            if (xout && (mine || ghost_row)) {      // this wave's own rows, or a ghost row of the slab (kept current here)
+                const unsigned row = (unsigned)u * W2u;
+                bst4<nt_out>(RS_RO, vo16, row * 16u, rxy[0].x, rxy[0].y, rxy[1].x, rxy[1].y); bst2<nt_out>(RS_RO, vo8, angle0 + row * 8u, rq[0], rq[1]);
+                bst4<nt_pout>(RS_Q, vo16, row * 16u, k1.xy[0].x, k1.xy[0].y, k1.xy[1].x, k1.xy[1].y); bst2<nt_pout>(RS_Q, vo8, angle0 + row * 8u, k1.pa[0], k1.pa[1]);
+                if (DMODE != 1 && mine) {
+                    float d[4] = { uf(cur.dlo.x), uf(cur.dlo.y), uf(cur.dlo.z), uf(cur.dlo.w) }, da[2] = { uf(cur.dla.x), uf(cur.dla.y) };
+                    if (DMODE == 2) {
+                        d[0] = __builtin_fmaf(alpha2, uf(cur.ppo.x), d[0]); d[1] = __builtin_fmaf(alpha2, uf(cur.ppo.y), d[1]);
+                        d[2] = __builtin_fmaf(alpha2, uf(cur.ppo.z), d[2]); d[3] = __builtin_fmaf(alpha2, uf(cur.ppo.w), d[3]);
+                        da[0] = __builtin_fmaf(alpha2, uf(cur.ppa.x), da[0]); da[1] = __builtin_fmaf(alpha2, uf(cur.ppa.y), da[1]);
+                    }
+                    d[0] = __builtin_fmaf(alpha, p1.xy[0].x, d[0]); d[1] = __builtin_fmaf(alpha, p1.xy[0].y, d[1]);
+                    d[2] = __builtin_fmaf(alpha, p1.xy[1].x, d[2]); d[3] = __builtin_fmaf(alpha, p1.xy[1].y, d[3]);
+                    da[0] = __builtin_fmaf(alpha, p1.pa[0], da[0]); da[1] = __builtin_fmaf(alpha, p1.pa[1], da[1]);
+                    bst4<nt_delta>(RS_D, vo16, row * 16u, d[0], d[1], d[2], d[3]); bst2<nt_delta>(RS_D, vo8, angle0 + row * 8u, da[0], da[1]);
+                }
+            }
+        }
+        // (phases in sequence: letting the scheduler interleave the two stencils and the two pixels' double sums for ILP costs ~60 registers -- the
+        //  difference between one and two waves per SIMD; at two waves per SIMD the other wave fills the issue slots)
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- row v = t-2: A p_k(v) and the iteration's sums (output lanes only: elsewhere the table's entry 0 -- M^-1 = 0 -- and a 0 multiplicand).  Full steps
+        // are exactly t = ya+2 .. yb+1, so v is always one of the segment's rows.
+        if constexpr (PH >= PH_FULL) {
+            const int v = t - 2;
+            const bool on = xout;
+            const float4 m0 = lut[on ? g2.f & 31u : 0u], m1 = lut[on ? (g2.f >> 8) & 31u : 0u];
+            const float wfit[2] = { m0.z, m1.z }, mo[2] = { m0.x, m1.x }, ma[2] = { m0.y, m1.y };
+            v2f axy[2]; float av[2];
+            jtjp_pair_xy(k3, k2, k1, g3, g2, g1, g3.a, g2.a, g1.a, wfit, wr2, axy, av);
+            if (SLAB && xout && (v == g.row0 || v == g.row1 - 1)) {      // the rows of A p_k the neighbouring ranks' ghost rows need
+                if (SLAB == 1) {
+                    const unsigned row = (unsigned)v * W2u;
+                    bst4<false>(RS_AO, vo16, row * 16u, axy[0].x, axy[0].y, axy[1].x, axy[1].y); bst2<false>(RS_AO, vo8, angle0 + row * 8u, av[0], av[1]);
+                } else {            // peer-to-peer, write-through; drained by every wave before the arrival ticket (iter_tail)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        if (v == (k == 0 ? g.row0 : g.row1 - 1) && dd.peer_r[k]) {
+                            float* d2 = dd.peer_r[k] + dd.peer_off_o[k] + 2 * x0;
+                            st_sys(d2, axy[0].x); st_sys(d2 + 1, axy[0].y); st_sys(d2 + 2, axy[1].x); st_sys(d2 + 3, axy[1].y);
+                            float* d1 = dd.peer_r[k] + dd.peer_off_a[k] + x0;
+                            st_sys(d1, av[0]); st_sys(d1 + 1, av[1]);
+                        }
+                    }
+                }
+            }
+            const float msum = on ? 1.0f : 0.0f;
+            __builtin_amdgcn_sched_barrier(0);
+            iter_sums_pixel_masked(msum, k2.xy[0].x, k2.xy[0].y, k2.pa[0], axy[0].x, axy[0].y, av[0], r2.xy[0].x, r2.xy[0].y, r2.ra[0], mo[0], ma[0], acc, s0, s1, s2);
+            __builtin_amdgcn_sched_barrier(0);
+            iter_sums_pixel_masked(msum, k2.xy[1].x, k2.xy[1].y, k2.pa[1], axy[1].x, axy[1].y, av[1], r2.xy[1].x, r2.xy[1].y, r2.ra[1], mo[1], ma[1], acc, s0, s1, s2);
+        }
+        // a row's arithmetic stays inside its step: without the pin the double sums of all four rows of a trip sink behind the fourth row's take (their only
+        // consumers are the next sums), with the 14 values each of them reads kept alive until then -- 99 live registers at a trip's first take, 256 at its end
+        asm volatile("" : "+v"(acc), "+v"(s0), "+v"(s1), "+v"(s2));
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
     // deferred cross-rank finish: the launch's last workgroup has no rows (the host added eight workgroups); its wave 0 is the exchange of iteration k-1
     if (SLAB == 2 && prev.gs != nullptr && prev.count > 0 && blockIdx.x == gridDim.x - 1 && wave == 0 && !work) rc_exchange_prev(aNp, prev, dd);
 
     if (work) {
-        const int t_first = ya - 2, t_last = yb + 1;          // rows of p_{k-1} / cs / flags to take
-        // No prologue (a second path into the loop header makes its wait the conservative merge of both): the loop starts DEPTH rows early with empty slots.
-        // The rings are indexed by j, the position inside the trip, so any starting row works.
-        // The row step itself is BRANCH-FREE: rows outside [t_first, t_last] (lead-in: empty slots; rounding-up: clamped re-reads) and lanes outside the image go
-        // through the same arithmetic on zeros / finite garbage that nothing consumes -- pixels outside the image are INACTIVE (flags 0: every term that would read
-        // them is multiplied by 0), and a row's p_k is only used by the sums of rows that are themselves in range -- and only the stores (exec mask) and the sums
-        // (a 0 / 1 multiplicand, M^-1 = 0) are predicated.  A uniform branch around the arithmetic is a merge point with a phi per ring register.
+        // head: the loads of the first DEPTH rows, nothing else; rows ya-2, ya-1 enter the rings
 #pragma unroll
-        for (int j = 0; j < DEPTH; ++j) slot[j] = RawT{};
-        const int t_begin = t_first - DEPTH;
-        for (int t0 = t_begin; t0 <= t_last; t0 += 4) {
-            // The iteration's scalars, at the start of the SECOND trip: the first trip issued the loads of the first rows and entered (at most) rows ya-2, ya-1,
-            // which need neither alpha nor beta; the partial loads queue up behind those row loads and the additions run while the rows arrive.
-            // (DEPTH 1 reaches row ya in its first trip: in front of the loop.)  Wave-uniform: kept in SGPRs.
-            if (DEPTH == 1 ? t0 == t_begin : t0 == t_begin + 4) {
-                if (SLAB == 2 && prev.gs != nullptr && prev.count > 0) rc_iteration_scalars_x(aNp, prev, dd, alpha, beta);
-                else rc_iteration_scalars(aNp, aDp, bNp, prev, alpha, beta, scal_writer);
-                alpha = to_sgpr(alpha); beta = to_sgpr(beta);
-                if (DMODE == 2) alpha2 = to_sgpr(safe_div<false>(rc_sum(aNpp), rc_sum(aDpp)));
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int t = t0 + j;
-                // ring roles at this step: row t -> index j, t-1 -> j+3, t-2 -> j+2, t-3 -> j+1 (mod 4)
-                PRow& p0 = pp[j % 4]; const PRow& p1 = pp[(j + 3) % 4]; const PRow& p2 = pp[(j + 2) % 4];
-                GRow& g0 = gg[j % 4]; const GRow& g1 = gg[(j + 3) % 4]; const GRow& g2 = gg[(j + 2) % 4]; const GRow& g3 = gg[(j + 1) % 4];
-                PRow& k1 = pk[(j + 3) % 4]; const PRow& k2 = pk[(j + 2) % 4]; const PRow& k3 = pk[(j + 1) % 4];
-                RRow& r1 = rr[(j + 1) % 2]; const RRow& r2 = rr[j % 2];
-                RawT cur;
-                take(cur, slot[j % DEPTH]);                  // (the only place that waits for memory)
-                fence_order();                               // the refill stays behind the moves ...
-                issue(slot[j % DEPTH], t + DEPTH > t_last ? t_last : t + DEPTH);
-                fence_order();                               // ... and in front of the arithmetic
-                // ---- row t enters the p_{k-1} / geometry rings (outside the image: inactive)
-                {
-                    const bool rowok = t >= 0 && t < g.H;
-                    const unsigned par = ((unsigned)t * (unsigned)W2) & 1u;
-                    const unsigned fl = (cur.f >> (par ? 16u - sh0 : sh0)) & (rowok ? mxin : 0u);
-                    p0.xy[0] = uf2(cur.po.x, cur.po.y); p0.xy[1] = uf2(cur.po.z, cur.po.w); p0.pa[0] = uf(cur.pa.x); p0.pa[1] = uf(cur.pa.y);
-                    g0.cs[0] = uf2(cur.cs.x, cur.cs.y); g0.cs[1] = uf2(cur.cs.z, cur.cs.w); g0.f = fl;
-                    g0.gx[0] = v2f{ g0.cs[0].y, -g0.cs[0].x }; g0.gx[1] = v2f{ g0.cs[1].y, -g0.cs[1].x };
-                    g0.a[0] = (float)(fl & 1u); g0.a[1] = (float)((fl >> 8) & 1u);
-                }
-                // ---- row u = t-1: A p_{k-1}(u) -> r_k(u), p_k(u)
-                const int u = t - 1;
-                {
-                    const float4 m0 = lut[g1.f & 31u], m1 = lut[(g1.f >> 8) & 31u];      // (M^-1 offsets, M^-1 angle, w_fit^2 or 0)
-                    const float wfit[2] = { m0.z, m1.z };
-                    v2f axy[2]; float av[2];
-                    jtjp_pair_xy(p2, p1, p0, g2, g1, g0, g2.a, g1.a, g0.a, wfit, wr2, axy, av);
-                    // a ghost row of the slab: the row above the strip's first segment / below its last one (wave-uniform).  Only THAT wave keeps it current: the
-                    // rounding-up steps of other segments pass by the same row index with clamped re-reads in their slots
-                    const bool ghost_row = SLAB && ((u == ya - 1 && ya == g.row0 && u >= 0) || (u == yb && yb == g.row1 && u < g.H));
-                    if (ghost_row) {            // A p_{k-1} of a ghost row: what the exchange delivered (a blocking load, twice per boundary wave and launch)
-                        const unsigned row = (unsigned)u * (unsigned)W2;
-                        const u32x4 ao = bld4<false>(RS_AI, vo16, row * 16u); const u32x2 aa = bld2<false>(RS_AI, vo8, angle0 + row * 8u);
-                        axy[0] = uf2(ao.x, ao.y); axy[1] = uf2(ao.z, ao.w); av[0] = uf(aa.x); av[1] = uf(aa.y);
-                    }
-                    v2f rxy[2] = { uf2(cur.ro.x, cur.ro.y), uf2(cur.ro.z, cur.ro.w) }; float rq[2] = { uf(cur.ra.x), uf(cur.ra.y) };
-                    rxy[0] = fma2(-alpha, axy[0], rxy[0]); rxy[1] = fma2(-alpha, axy[1], rxy[1]);
-                    rq[0] = __builtin_fmaf(-alpha, av[0], rq[0]); rq[1] = __builtin_fmaf(-alpha, av[1], rq[1]);
-                    const float mo[2] = { m0.x, m1.x }, ma[2] = { m0.y, m1.y };
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        k1.xy[q] = mo[q] * rxy[q] + beta * p1.xy[q]; k1.pa[q] = ma[q] * rq[q] + beta * p1.pa[q];
-                        r1.xy[q] = rxy[q]; r1.ra[q] = rq[q];
-                    }
-                    const bool mine = u >= ya && u < yb;
-                    if (xout && (mine || ghost_row)) {      // this wave's own rows, or a ghost row of the slab (kept current here)
-                        const unsigned row = (unsigned)u * (unsigned)W2;
-                        bst4<nt_out>(RS_RO, vo16, row * 16u, rxy[0].x, rxy[0].y, rxy[1].x, rxy[1].y); bst2<nt_out>(RS_RO, vo8, angle0 + row * 8u, rq[0], rq[1]);
-                        bst4<nt_pout>(RS_Q, vo16, row * 16u, k1.xy[0].x, k1.xy[0].y, k1.xy[1].x, k1.xy[1].y); bst2<nt_pout>(RS_Q, vo8, angle0 + row * 8u, k1.pa[0], k1.pa[1]);
-                        if (DMODE != 1 && mine) {
-                            float d[4] = { uf(cur.dlo.x), uf(cur.dlo.y), uf(cur.dlo.z), uf(cur.dlo.w) }, da[2] = { uf(cur.dla.x), uf(cur.dla.y) };
-                            if (DMODE == 2) {
-                                d[0] = __builtin_fmaf(alpha2, uf(cur.ppo.x), d[0]); d[1] = __builtin_fmaf(alpha2, uf(cur.ppo.y), d[1]);
-                                d[2] = __builtin_fmaf(alpha2, uf(cur.ppo.z), d[2]); d[3] = __builtin_fmaf(alpha2, uf(cur.ppo.w), d[3]);
-                                da[0] = __builtin_fmaf(alpha2, uf(cur.ppa.x), da[0]); da[1] = __builtin_fmaf(alpha2, uf(cur.ppa.y), da[1]);
-                            }
-                            d[0] = __builtin_fmaf(alpha, p1.xy[0].x, d[0]); d[1] = __builtin_fmaf(alpha, p1.xy[0].y, d[1]);
-                            d[2] = __builtin_fmaf(alpha, p1.xy[1].x, d[2]); d[3] = __builtin_fmaf(alpha, p1.xy[1].y, d[3]);
-                            da[0] = __builtin_fmaf(alpha, p1.pa[0], da[0]); da[1] = __builtin_fmaf(alpha, p1.pa[1], da[1]);
-                            bst4<nt_delta>(RS_D, vo16, row * 16u, d[0], d[1], d[2], d[3]); bst2<nt_delta>(RS_D, vo8, angle0 + row * 8u, da[0], da[1]);
-                        }
-                    }
-                }
-                // (phases in sequence: letting the scheduler interleave the two stencils and the two pixels' double sums for ILP costs ~60 registers -- the
-                //  difference between one and two waves per SIMD; at two waves per SIMD the other wave fills the issue slots)
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- row v = t-2: A p_k(v) and the iteration's sums (the wave's own rows and output lanes only: elsewhere the table's entry 0 -- M^-1 = 0 -- and a 0 multiplicand)
-                {
-                    const int v = t - 2;
-                    const bool on = xout && v >= ya && v < yb;
-                    const float4 m0 = lut[on ? g2.f & 31u : 0u], m1 = lut[on ? (g2.f >> 8) & 31u : 0u];
-                    const float wfit[2] = { m0.z, m1.z }, mo[2] = { m0.x, m1.x }, ma[2] = { m0.y, m1.y };
-                    v2f axy[2]; float av[2];
-                    jtjp_pair_xy(k3, k2, k1, g3, g2, g1, g3.a, g2.a, g1.a, wfit, wr2, axy, av);
-                    if (SLAB && xout && v >= ya && v < yb && (v == g.row0 || v == g.row1 - 1)) {      // the rows of A p_k the neighbouring ranks' ghost rows need
-                        if (SLAB == 1) {
-                            const unsigned row = (unsigned)v * (unsigned)W2;
-                            bst4<false>(RS_AO, vo16, row * 16u, axy[0].x, axy[0].y, axy[1].x, axy[1].y); bst2<false>(RS_AO, vo8, angle0 + row * 8u, av[0], av[1]);
-                        } else {            // peer-to-peer, write-through; drained by every wave before the arrival ticket (iter_tail)
-#pragma unroll
-                            for (int k = 0; k < 2; ++k) {
-                                if (v == (k == 0 ? g.row0 : g.row1 - 1) && dd.peer_r[k]) {
-                                    float* d2 = dd.peer_r[k] + dd.peer_off_o[k] + 2 * x0;
-                                    st_sys(d2, axy[0].x); st_sys(d2 + 1, axy[0].y); st_sys(d2 + 2, axy[1].x); st_sys(d2 + 3, axy[1].y);
-                                    float* d1 = dd.peer_r[k] + dd.peer_off_a[k] + x0;
-                                    st_sys(d1, av[0]); st_sys(d1 + 1, av[1]);
-                                }
-                            }
-                        }
-                    }
-                    const float msum = on ? 1.0f : 0.0f;
-                    __builtin_amdgcn_sched_barrier(0);
-                    iter_sums_pixel_masked(msum, k2.xy[0].x, k2.xy[0].y, k2.pa[0], axy[0].x, axy[0].y, av[0], r2.xy[0].x, r2.xy[0].y, r2.ra[0], mo[0], ma[0], acc, s0, s1, s2);
-                    __builtin_amdgcn_sched_barrier(0);
-                    iter_sums_pixel_masked(msum, k2.xy[1].x, k2.xy[1].y, k2.pa[1], axy[1].x, axy[1].y, av[1], r2.xy[1].x, r2.xy[1].y, r2.ra[1], mo[1], ma[1], acc, s0, s1, s2);
-                }
-                // a row's arithmetic stays inside its step: without the pin the double sums of all four rows of a trip sink behind the fourth row's take (their only
-                // consumers are the next sums), with the 14 values each of them reads kept alive until then -- 99 live registers at a trip's first take, 256 at its end
-                asm volatile("" : "+v"(acc), "+v"(s0), "+v"(s1), "+v"(s2));
-                __builtin_amdgcn_sched_barrier(0);
-            }
+        for (int i = 0; i < DEPTH; ++i) issue(slot[i], t_first + i, IC<1>{});
+        step(t_first, IC<0>{}, IC<PH_ENTER>{}, IC<1>{});
+        step(t_first + 1, IC<1>{}, IC<PH_ENTER>{}, IC<1>{});
+        // The iteration's scalars, behind the loads of the first rows: rows ya-2, ya-1 need neither alpha nor beta; the partial loads queue up behind those
+        // row loads and the additions run while the rows arrive.  Wave-uniform: kept in SGPRs.
+        if (SLAB == 2 && prev.gs != nullptr && prev.count > 0) rc_iteration_scalars_x(aNp, prev, dd, alpha, beta);
+        else rc_iteration_scalars(aNp, aDp, bNp, prev, alpha, beta, scal_writer);
+        alpha = to_sgpr(alpha); beta = to_sgpr(beta);
+        if (DMODE == 2) alpha2 = to_sgpr(safe_div<false>(rc_sum(aNpp), rc_sum(aDpp)));
+        step(ya, IC<2>{}, IC<PH_S1>{}, IC<1>{});
+        step(ya + 1, IC<3>{}, IC<PH_S1>{}, IC<1>{});
+        // steady loop: whole trips of full steps whose rows need no clamp -- rows t+DEPTH <= t_last inside the image, delta / p_{k-2} rows inside the segment
+        // (and with them t inside the image, t-1 one of the segment's rows, no ghost row).  It is entered only at a trip boundary, with the same DEPTH rows
+        // in flight as at its back edge.
+        int t_lim = t_last < g.H - 1 ? t_last : g.H - 1;
+        if (DMODE != 1 && yb < t_lim) t_lim = yb;
+        const int t_safe = t_lim - DEPTH;                     // the last step whose rows need no clamp
+        int t = ya + 2;
+        for (; t + 3 <= t_safe; t += 4) {
+            step(t, IC<0>{}, IC<PH_FULL>{}, IC<0>{});
+            step(t + 1, IC<1>{}, IC<PH_FULL>{}, IC<0>{});
+            step(t + 2, IC<2>{}, IC<PH_FULL>{}, IC<0>{});
+            step(t + 3, IC<3>{}, IC<PH_FULL>{}, IC<0>{});
         }
+        // tail: the rest, t .. t_last (at most DEPTH + 5 steps: t > t_safe - 3 and t_last - t_safe <= DEPTH + 2), with clamps
+        auto tail = [&](auto I_) __attribute__((always_inline)) {
+            constexpr int i = decltype(I_)::value;
+            if constexpr (i < DEPTH + 5) { if (t + i <= t_last) step(t + i, IC<i % 4>{}, IC<PH_FULL>{}, IC<1>{}); }
+        };
+        tail(IC<0>{}); tail(IC<1>{}); tail(IC<2>{}); tail(IC<3>{}); tail(IC<4>{}); tail(IC<5>{}); tail(IC<6>{}); tail(IC<7>{}); tail(IC<8>{});
     }
     iter_tail<MARCH_NT, SLAB == 2>(acc, s0, s1, s2, red, redd, aD_out, s12_out, bNp, &dd, fin_tickets, aD_word, bN_word, xslot);
 }
@@ -379,8 +412,9 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
 [[maybe_unused]] constexpr int MARCH_RC_DEPTH = 4;      // (sweep build: the depth of the cache-policy variants)
 constexpr int MARCH_RC_OCC = 2;
 // Rows of prefetch: four where a wave has many rows (since the arithmetic went onto register pairs the row step is short enough for memory latency to show: 2048^2,
-// 35 rows per wave, 63.3 -> 59.5 us per PCG iteration), two where it has few -- the loop starts DEPTH rows early with empty slots, and at 5 rows per wave (2048 x 256)
-// four lead-in steps cost 14 %.  tools/rc_depth_by_size.py: 26 rows a tie, 22 / 18 / 9 / 5 rows 1-14 % for two.
+// 35 rows per wave, 63.3 -> 59.5 us per PCG iteration), two where it has few -- measured when the loop started DEPTH rows early with empty slots (at 5 rows
+// per wave, 2048 x 256, four lead-in steps cost 14 %; tools/rc_depth_by_size.py: 26 rows a tie, 22 / 18 / 9 / 5 rows 1-14 % for two).  The march has no lead-in
+// steps since (the head only issues the first DEPTH rows' loads), so the threshold is worth re-measuring.
 [[maybe_unused]] constexpr int MARCH_RC_DEEP_ROWS = 24;
 #ifdef THALLO_MARCH_SWEEP
 namespace thallo {
