@@ -151,8 +151,13 @@ unsigned long long ThalloX_ProblemFileUnitHash(const char* filename);
  * to cap - 1) or -1 (ThalloX_LastError).  A Plan on a file no hand-written plugin recognises -- or on any file under THALLO_FRONTEND=generate -- compiles
  * that unit with hipRTC and runs it. */
 int ThalloX_FrontendText(const char* filename, int what, char* out, int cap);
-/* ... given the problem's dimensions (the array Thallo_ProblemPlan takes): needed by files that use Sum, which is expanded for those sizes */
+/* ... given the problem's dimensions (the array Thallo_ProblemPlan takes): needed by files that use Sum, which is expanded for those sizes.
+ * what = 2: the ROW-SLAB unit a distributed plan of the file compiles (owned-row kernels, global pixel coordinates; -1 if the file has no row-slab form) */
 int ThalloX_FrontendTextDims(const char* filename, int what, const unsigned* dims, char* out, int cap);
+/* Row slabs of a generated energy, host only (no device): the ghost rows g >= 1 a slab needs towards each neighbour -- the largest row span of one residual's
+ * data accesses, computed arrays composed with their own footprint -- or -1 with ThalloX_LastError naming the construct that has no row-slab form
+ * (SampledImage, Sparse maps, graph or 3-D domains, more than one Unknown, materialize lines, direct solve).  global_dims: the problem's dimensions. */
+int ThalloX_FrontendSlabGhostRows(const char* filename, const unsigned* global_dims);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU, one process per GPU (the reference is single-device, API/src/util.t:769-772).
@@ -170,7 +175,10 @@ int ThalloX_FrontendTextDims(const char* filename, int what, const unsigned* dim
  * shape_from_shading (TWO ghost rows per neighbour; Gauss-Newton and ThalloX_EnableLM; BOTH transports: per PCG iteration one exchange -- the
  * all-gather carries the GN form's sums and rows, and the LM form's alphaD, then betaN + q + the ghost rows of z, in two; on the device-side
  * transport the LM iteration is one launch + ONE mailbox / peer-to-peer exchange that also finishes alphaD, betaN, q and the zeta test,
- * thallo_hip_dist_xrows_lm).
+ * thallo_hip_dist_xrows_lm); and GENERATED image energies (files run through the front-end, dsl.hpp) with one Unknown over {W, H}, every input that has
+ * the H dimension over exactly {W, H}, fixed-offset accesses and residuals with the unknown-wise form: g ghost rows per neighbour as
+ * ThalloX_FrontendSlabGhostRows says (the stencil's row span, >= 1), global_row0 / global_rows required when world > 1, Gauss-Newton and ThalloX_EnableLM,
+ * both transports; the plan compiles the front-end's row-slab unit (ThalloX_FrontendTextDims what = 2) at this call.
  * Graph energies (arap_mesh_deformation) are split into contiguous VERTEX RANGES instead: every rank makes its Plan for the WHOLE problem, passes the
  * whole (replicated) buffers, and sets row0 / row1 to the vertex range it owns (equal ranges: N % world == 0); per PCG iteration one all-gather
  * of [alphaD, N, S1, S2 | the owned slice of A p]; the unknowns stay replicated bit for bit.  Gauss-Newton, all-gather transport.
@@ -189,7 +197,7 @@ typedef int (*ThalloX_AllGatherFn)(void* user, const void* send, void* recv, lon
 typedef int (*ThalloX_AllReduceFn)(void* user, void* buf, long count, void* stream);
 typedef struct ThalloX_Distributed {
     int rank, world;                 /* world <= 8 (THALLO_DIST_MAX_WORLD) */
-    unsigned int row0, row1;         /* owned rows [row0, row1) of the local image; g ghost rows above iff row0 == g, below iff row1 == H_local - g (g = 1 or 2, see below) */
+    unsigned int row0, row1;         /* owned rows [row0, row1) of the local image; g ghost rows above iff row0 == g, below iff row1 == H_local - g (g >= 1: the energy's, see below) */
     ThalloX_AllGatherFn allgather;
     void* user;
     int device_exchange;             /* 1: try the mailbox / peer-to-peer exchange (falls back to the all-gather if its self-check fails) */

@@ -162,6 +162,19 @@ def last_error():
     return lib().ThalloX_LastError().decode()
 
 
+def slab_ghost_rows(path, dims):
+    """Ghost rows a row slab of the generated energy in `path` needs towards each neighbour (include/Thallo.h ThalloX_FrontendSlabGhostRows; host only).
+    dims: the problem's dimensions.  Raises ValueError, naming the construct, when the file has no row-slab form."""
+    L = lib()
+    L.ThalloX_FrontendSlabGhostRows.argtypes = [C.c_char_p, C.c_void_p]
+    L.ThalloX_FrontendSlabGhostRows.restype = C.c_int
+    d = (C.c_uint * len(dims))(*[int(x) for x in dims])
+    g = L.ThalloX_FrontendSlabGhostRows(os.fsencode(path), d)
+    if g < 0:
+        raise ValueError(last_error())
+    return g
+
+
 def rccl_unique_id():
     """128 bytes from ncclGetUniqueId (rank 0); raises when the library cannot bind RCCL"""
     buf = (C.c_ubyte * 128)()

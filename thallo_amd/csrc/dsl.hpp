@@ -136,7 +136,21 @@ struct Generated {
     std::vector<long> jp_offset;                   // per residual: offset of its rows in the Jp vector (Jt[Jp] schedule), in units of elements x components
     int n_prm = 0;
     bool has_wide = false;                         // some residual took the wide lowering (more than 48 unknown accesses): the plugin compiles the unit without loop unrolling
+    // IN: >= 0 = emit the ROW-SLAB unit instead (a second unit; see slab_form): this dimension is the row.  Ctx::dim then carries four more ints behind the problem's
+    // dimensions -- row0, row1 (the owned rows of the local image), yoff (its first row's global index) and Hg (the global height) --; the gather group kernels walk the
+    // owned rows only; :asvalue() of the row, InBounds and the instance guards are global, data reads stay guarded by the local extent.
+    int slab_rowdim = -1;
+    // ... the wide residuals of a slab unit (no unknown-wise form): residual-wise cost over the owned rows, evalJTF / applyJTJ over the instances that touch an owned row,
+    // scatter-adds into owned unknowns only
+    struct SlabWide { int ri; std::string cost, jtf, jtj; };
+    std::vector<SlabWide> slab_wide;
 };
+
+// Row slabs (solver_dist.cpp's flat form) for a generated energy: one Unknown over a 2-D domain {W, H}, every input with the H dimension over exactly {W, H}, every
+// residual over {W, H} with fixed-offset unknown accesses, no SampledImage / Sparse / 3-D domains / materialize lines / direct solve.  `ghost` = the largest row span
+// (max - min row offset) of the data accesses of any one residual (computed arrays composed with their own footprint; Exclude conditions at the unknowns they guard), >= 1.
+struct SlabForm { int rowdim = -1; int ghost = 1; };
+bool slab_form(const Problem& p, SlabForm& out, std::string& why);
 // f64 (Thallo_InitializationParameters::doublePrecision): constants as double literals; the plugin compiles the unit with `float` standing for double
 bool generate_source(const Problem& p, Generated& out, std::string& err, bool f64 = false);
 

@@ -102,6 +102,12 @@ class GeneratedPlugin : public EnergyPlugin, public EnergyPlugin64 {
     {
         if (ca_valid_ || G.computed.empty()) return 0;
         TimedLaunch t(c, "precompute");
+        if (slab_on_) {          // the slab unit's precompute kernels: every local row, :asvalue() / InBounds in global rows
+            void* sc = slab_ctx();
+            for (size_t k = 0; k < sca_fn_.size(); ++k) { void* args[] = { sc }; const int rc = launch_fn(sca_fn_[k], grid_for(ca_nel[k], 4096), args, c.stream); if (rc < 0) return rc; }
+            ca_valid_ = true;
+            return 0;
+        }
         for (size_t k = 0; k < G.computed.size(); ++k) {
             void* args[] = { ctx.data() };
             const int rc = launch_fn(ca_fn[k], grid_for(ca_nel[k], 4096), args, c.stream); if (rc < 0) return rc;
@@ -336,9 +342,15 @@ public:
             jval[ri] = new DeviceBuffer(); jcol[ri] = new DeviceBuffer();
             if (jval[ri]->alloc(sizeof(float) * ent + 256) || jcol[ri]->alloc(sizeof(int) * ent + 256)) { set_error("%s: out of device memory for the materialized J of %s", label.c_str(), P.residuals[ri].name.c_str()); return; }
         }
+        {   // row slabs (dsl.hpp slab_form): decided here, compiled at set_row_slab
+            dsl::SlabForm sf; std::string why;
+            if (f64_) slab_why_ = "doublePrecision = 1";
+            else if (!dsl::slab_form(P, sf, why)) slab_why_ = why;
+            else { slab_ok_ = true; slab_g_ = sf.ghost; slab_rowdim_ = sf.rowdim; }
+        }
         ok_ = true;
     }
-    ~GeneratedPlugin() override { if (mod) (void)hipModuleUnload(mod); for (auto b : ca_buf) delete b; for (auto b : jval) delete b; for (auto b : jcol) delete b; for (auto b : jdest) delete b; for (auto r : inc_runs_) delete r; }
+    ~GeneratedPlugin() override { if (smod_) (void)hipModuleUnload(smod_); if (mod) (void)hipModuleUnload(mod); for (auto b : ca_buf) delete b; for (auto b : jval) delete b; for (auto b : jcol) delete b; for (auto b : jdest) delete b; for (auto r : inc_runs_) delete r; }
     const char* schedule_name() const override
     {
         if (direct_) return "dense direct solve";
@@ -553,6 +565,7 @@ public:
 
     int cost(LaunchCtx& c, float* out) override
     {
+        if (slab_on_) return slab_cost(c, out);
         if (precompute(c) < 0) return -1;
         TimedLaunch t(c, "computeCost");
         const int cap = THALLO_HIP_MAX_PARTIALS / (int)P.residuals.size();
@@ -570,6 +583,7 @@ public:
     }
     int pcg_init(LaunchCtx& c, SolverVectors& v, int cur, float* aN) override
     {
+        if (slab_on_) return slab_init(c, v, cur, aN);
         if (precompute(c) < 0) return -1;
         TimedLaunch t(c, "PCGInit1");
         hipStream_t s = c.stream;
@@ -654,7 +668,15 @@ public:
         return thallo_hip_dot(p, Ap, n_unk, out, s);                  // PCGStep1_Finish: alphaD = p . Ap_X
     }
     int apply_jtj(LaunchCtx& c, const float* p, float* Ap, float* out) override
-    { TimedLaunch t(c, "PCGStep1"); return apply(c, p, Ap, out, thallo_hip_vector_elems(n_unk)); }
+    {
+        TimedLaunch t(c, "PCGStep1");
+        if (slab_on_) {          // (LM on a slab, the model cost: the partials of p . Ap over the owned rows)
+            if (slab_apply(c, p, Ap, thallo_hip_vector_elems(n_unk)) < 0) return -1;
+            const long o = rowlen_() * row0_, n = rowlen_() * (row1_ - row0_);
+            return thallo_hip_dot(p + o, Ap + o, n, out, c.stream);
+        }
+        return apply(c, p, Ap, out, thallo_hip_vector_elems(n_unk));
+    }
     // (measured and dropped, round 5: the single-reduction form for a whole-domain gather kernel -- N, S1, S2 in double behind the store of Ap -- made generated
     //  image_warping's two launches 67 + 103 us against 41 + 77 + 43 for the three of the reference's schedule: the flat launches run at HBM rate either way and the
     //  double-precision sums cost the gather kernel more than the third launch does)
@@ -663,6 +685,128 @@ public:
         { TimedLaunch t(c, "PCGStep3"); int rc = thallo_hip_pcg_pupdate(v.z, v.p[cur], v.p[cur ^ 1], v.delta, v.n, first ? 1 : 0, aN, aD, bN, c.stream); if (rc < 0) return rc; }
         TimedLaunch t(c, "PCGStep1");
         return apply(c, v.p[cur ^ 1], v.Ap, out, v.n_alloc);
+    }
+private:
+    // ---- one row slab of a multi-GPU run (solver_dist.cpp, flat form; dsl.hpp slab_form).  A second translation unit (Generated::slab_rowdim), compiled at set_row_slab:
+    // the gather group kernels over the owned rows [row0, row1) of the local image, global :asvalue() / InBounds / instance guards (c.dim[nd + 2] = yoff, + 3 = Hg), the
+    // computed arrays on every local row; wide residuals residual-wise over the instances that touch an owned row.  The three sums of the single-reduction form come from
+    // thallo_hip_block_sums over the owned range (one fixed slot per workgroup, no atomics).
+    bool slab_ok_ = false, slab_on_ = false, slab_failed_ = false;
+    std::string slab_why_, slab_err_;
+    int slab_g_ = 1, slab_rowdim_ = -1, row0_ = 0, row1_ = 0, yoff_ = 0, Hg_ = 0;
+    dsl::Generated GS;
+    hipModule_t smod_ = nullptr;
+    std::vector<hipFunction_t> sca_fn_, sgrp_jtj_, sgrp_jtf_, sgrp_cost_, swide_cost_, swide_jtf_, swide_jtj_;
+    std::vector<unsigned char> sctx_;
+    size_t soff_prm_ = 0, soff_uoff_ = 0, soff_cap_ = 0;
+    long W_() const { return dimv[(size_t)P.inputs[(size_t)unknown_input[0]].dims[0]]; }
+    long H_() const { return dimv[(size_t)slab_rowdim_]; }
+    long rowlen_() const { return W_() * P.inputs[(size_t)unknown_input[0]].channels; }
+    // the slab unit's Ctx: the plan's, with four more ints behind the dimensions
+    void* slab_ctx()
+    {
+        const size_t nin = P.inputs.size(), nd = P.dims.size();
+        memcpy(sctx_.data(), ctx.data(), 8 * nin);
+        memcpy(&sctx_[off_dim], &ctx[off_dim], 4 * nd);
+        const int ex[4] = { row0_, row1_, yoff_, Hg_ };
+        memcpy(&sctx_[off_dim + 4 * nd], ex, sizeof ex);
+        memcpy(&sctx_[soff_prm_], &ctx[off_prm], 4 * nin);
+        memcpy(&sctx_[soff_uoff_], &ctx[off_uoff], 8 * nin);
+        memcpy(&sctx_[soff_cap_], &ctx[off_cap], ctx.size() - off_cap);
+        return sctx_.data();
+    }
+    int build_slab_unit()
+    {
+        GS = dsl::Generated(); GS.slab_rowdim = slab_rowdim_; GS.want_gather.assign(P.residuals.size(), 1);
+        std::string err;
+        if (!dsl::generate_source(P, GS, err)) { set_error("%s: row-slab unit: %s", label.c_str(), err.c_str()); return -1; }
+        if (GS.n_planes != G.n_planes || GS.computed.size() != G.computed.size()) { set_error("%s: row-slab unit: computed arrays differ from the plan's", label.c_str()); return -1; }
+        if (rtc_build("#include <hip/hip_runtime.h>\n" + GS.source, GS.has_wide, (P.file + " (row slab)").c_str(), &smod_)) return -1;
+        auto get = [&](const std::string& n, std::vector<hipFunction_t>& v) {
+            hipFunction_t f = nullptr;
+            if (hipModuleGetFunction(&f, smod_, n.c_str()) != hipSuccess) { set_error("%s: generated slab kernel %s missing", label.c_str(), n.c_str()); return false; }
+            v.push_back(f); return true;
+        };
+        for (auto& gc : GS.computed) if (!get(gc.kernel, sca_fn_)) return -1;
+        for (auto& g : GS.groups) if (!get(g.jtj, sgrp_jtj_) || !get(g.jtf, sgrp_jtf_) || !get(g.cost, sgrp_cost_)) return -1;
+        for (auto& w : GS.slab_wide) if (!get(w.cost, swide_cost_) || !get(w.jtf, swide_jtf_) || !get(w.jtj, swide_jtj_)) return -1;
+        const size_t nin = P.inputs.size(), nd = P.dims.size() + 4;
+        soff_prm_ = off_dim + 4 * nd; soff_uoff_ = (soff_prm_ + 4 * nin + 7) / 8 * 8; soff_cap_ = soff_uoff_ + 8 * nin;
+        sctx_.assign(soff_cap_ + (ctx.size() - off_cap), 0);
+        return 0;
+    }
+public:
+    bool supports_row_slabs() const override { return slab_ok_; }
+    bool slab_returns_sums() const override { return slab_ok_; }
+    bool apply_returns_sums() const override { return slab_on_; }
+    bool slab_setup_ok() const override { return !slab_failed_; }
+    const char* slab_setup_error() const override { return slab_failed_ ? slab_err_.c_str() : slab_why_.c_str(); }
+    int slab_ghost_rows() const override { return slab_g_; }
+    int slab_width() const override { return slab_ok_ ? (int)W_() : 0; }
+    const char* slab_refusal() const { return slab_why_.c_str(); }
+    int set_row_slab(int row0, int row1) override
+    {
+        if (!slab_ok_) { set_error("%s: no row-slab form: %s", label.c_str(), slab_why_.c_str()); return -1; }
+        if (row0 < 0 || row1 > (int)H_() || row0 >= row1) { set_error("%s: row slab [%d,%d) of %ld rows", label.c_str(), row0, row1, H_()); return -1; }
+        row0_ = row0; row1_ = row1;
+        if (!yoff_ && !Hg_) Hg_ = (int)H_();
+        ca_valid_ = false;
+        //  a compile or allocation failure is NOT an early return: it is this rank's "no" in the set-up's first agreement (slab_setup_ok), where every rank returns the error
+        if (!slab_on_ && !slab_failed_ && build_slab_unit()) { slab_failed_ = true; slab_err_ = last_error(); return 0; }
+        slab_on_ = !slab_failed_;
+        return 0;
+    }
+    int set_slab_global(int global_row0, int global_rows) override
+    {
+        if (global_row0 < 0 || global_rows < global_row0 + (int)H_()) { set_error("%s: local rows [%d,%ld) outside the %d global rows", label.c_str(), global_row0, global_row0 + H_(), global_rows); return -1; }
+        yoff_ = global_row0; Hg_ = global_rows; ca_valid_ = false; return 0;
+    }
+    int slab_cost(LaunchCtx& c, float* out)
+    {
+        if (precompute(c) < 0) return -1;
+        TimedLaunch t(c, "computeCost");
+        void* sc = slab_ctx();
+        const long nown = W_() * (row1_ - row0_);
+        const int nk = (int)(sgrp_cost_.size() + swide_cost_.size());
+        const int cap = THALLO_HIP_MAX_PARTIALS / (nk > 0 ? nk : 1);
+        int total = 0;
+        for (hipFunction_t f : sgrp_cost_) { const int g = grid_for(nown, cap); float* o = out + total; void* args[] = { sc, &o }; if (launch_fn(f, g, args, c.stream) < 0) return -1; total += g; }
+        for (hipFunction_t f : swide_cost_) { const int g = grid_for(nown, cap); float* o = out + total; void* args[] = { sc, &o }; if (launch_fn(f, g, args, c.stream) < 0) return -1; total += g; }
+        return total;
+    }
+    int slab_init(LaunchCtx& c, SolverVectors& v, int cur, float* aN)
+    {
+        if (precompute(c) < 0) return -1;
+        TimedLaunch t(c, "PCGInit1");
+        hipStream_t s = c.stream;
+        const size_t bytes = (size_t)v.n_alloc * sizeof(float);
+        if (hipMemsetAsync(v.r, 0, bytes, s) != hipSuccess || hipMemsetAsync(v.pre, 0, bytes, s) != hipSuccess || hipMemsetAsync(v.p[cur], 0, bytes, s) != hipSuccess ||
+            hipMemsetAsync(v.delta, 0, bytes, s) != hipSuccess) return -1;
+        void* sc = slab_ctx();
+        const long nown = W_() * (row1_ - row0_), nins = W_() * H_();
+        for (hipFunction_t f : sgrp_jtf_) { float *r = v.r, *pre = v.pre; int mode = 0; void* args[] = { sc, &r, &pre, &mode }; if (launch_fn(f, grid_for(nown, 4096), args, s) < 0) return -1; }
+        for (hipFunction_t f : swide_jtf_) { float *r = v.r, *pre = v.pre; void* args[] = { sc, &r, &pre }; if (launch_fn(f, grid_for(nins, 4096), args, s) < 0) return -1; }
+        if (v.diag && hipMemcpyAsync(v.diag, v.pre, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;      // LM: the raw diagonal
+        const long o = rowlen_() * row0_, n = rowlen_() * (row1_ - row0_);
+        return thallo_hip_pcg_init_finish(v.r + o, v.pre + o, v.pre + o, v.z + o, n, P.use_preconditioner ? 1 : 0, aN, s);     // alphaN partials over the owned rows
+    }
+    int slab_apply(LaunchCtx& c, const float* p, float* Ap, long n_alloc)
+    {   // Ap = J^T J p on the owned rows (0 elsewhere)
+        hipStream_t s = c.stream;
+        if (hipMemsetAsync(Ap, 0, (size_t)n_alloc * sizeof(float), s) != hipSuccess) return -1;
+        void* sc = slab_ctx();
+        const long nown = W_() * (row1_ - row0_), nins = W_() * H_();
+        for (hipFunction_t f : sgrp_jtj_) { int mode = 0; float* none = nullptr; void* args[] = { sc, &p, &Ap, &mode, &none }; if (launch_fn(f, grid_for(nown, 4096), args, s) < 0) return -1; }
+        for (hipFunction_t f : swide_jtj_) { void* args[] = { sc, &p, &Ap }; if (launch_fn(f, grid_for(nins, 4096), args, s) < 0) return -1; }
+        return 0;
+    }
+    int apply_jtj_sums(LaunchCtx& c, SolverVectors& v, const float* p, float* Ap, float* out, const thallo_fin_t& fin) override
+    {
+        if (!slab_on_ || fin.tickets) return -1;              // (the flat slab form finishes the scalars after its exchange)
+        TimedLaunch t(c, "PCGStep1");
+        if (slab_apply(c, p, Ap, v.n_alloc) < 0) return -1;
+        const long o = rowlen_() * row0_, n = rowlen_() * (row1_ - row0_);
+        return thallo_hip_block_sums(p + o, Ap + o, v.r + o, P.use_preconditioner ? v.pre + o : nullptr, n, out, v.s12, c.stream);
     }
 };
 
@@ -728,11 +872,29 @@ extern "C" int ThalloX_FrontendTextDims(const char* filename, int what, const un
     thallo::dsl::Problem p; std::string err, text;
     if (!thallo::dsl::run_problem_file(filename, p, err, dims)) { thallo::set_error("%s", err.c_str()); return -1; }
     if (what == 0) text = thallo::dsl::describe(p);
-    else {
+    else if (what == 2) {      // the row-slab unit (a second unit: what = 1 is untouched by it)
+        thallo::dsl::SlabForm sf;
+        if (!thallo::dsl::slab_form(p, sf, err)) { thallo::set_error("%s: no row-slab form: %s", filename, err.c_str()); return -1; }
+        thallo::dsl::Generated g; g.slab_rowdim = sf.rowdim; g.want_gather.assign(p.residuals.size(), 1);
+        if (!thallo::dsl::generate_source(p, g, err)) { thallo::set_error("%s: %s", filename, err.c_str()); return -1; }
+        text = "#include <hip/hip_runtime.h>\n" + g.source;
+    } else {
         thallo::dsl::Generated g;
         if (!thallo::dsl::generate_source(p, g, err)) { thallo::set_error("%s: %s", filename, err.c_str()); return -1; }
         text = "#include <hip/hip_runtime.h>\n" + g.source;
     }
     snprintf(out, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
+}
+
+// Row slabs of a generated energy (dsl.hpp slab_form), host only: the ghost rows g >= 1 a slab needs towards each neighbour, or -1 (ThalloX_LastError says why the file
+// has no row-slab form).  global_dims: the problem's dimensions (files that use Sum are expanded for those sizes; NULL: none given).
+extern "C" int ThalloX_FrontendSlabGhostRows(const char* filename, const unsigned* global_dims)
+{
+    if (!filename) { thallo::set_error("ThalloX_FrontendSlabGhostRows: no file"); return -1; }
+    thallo::dsl::Problem p; std::string err;
+    if (!thallo::dsl::run_problem_file(filename, p, err, global_dims)) { thallo::set_error("%s", err.c_str()); return -1; }
+    thallo::dsl::SlabForm sf;
+    if (!thallo::dsl::slab_form(p, sf, err)) { thallo::set_error("%s: no row-slab form: %s", filename, err.c_str()); return -1; }
+    return sf.ghost;
 }

@@ -229,6 +229,11 @@ public:
     virtual bool supports_row_slabs() const { return false; }
     virtual int  set_row_slab(int /*row0*/, int /*row1*/) { return -1; }
     virtual int  slab_ghost_rows() const { return 1; }         // stencil radius = ghost rows towards each neighbour
+    virtual bool slab_returns_sums() const { return apply_returns_sums(); }      // the flat slab form's applyJTJ returns the three sums (generated energies: once the slab is set)
+    // set_row_slab may leave a rank-local failure behind (the generated slab unit did not compile, out of memory) instead of returning early: it is this rank's "no" in the
+    // first agreement of the set-up, where every rank returns the error
+    virtual bool slab_setup_ok() const { return true; }
+    virtual const char* slab_setup_error() const { return ""; }
     virtual int  set_slab_global(int /*global_row0*/, int /*global_rows*/) { return 0; }      // energies whose expressions use global pixel coordinates
     virtual int  slab_width() const { return 0; }
     virtual bool slab_grid_ok() const { return false; }       // after prepare(): the precondition of the one-kernel slab schedule holds on this rank

@@ -279,7 +279,11 @@ int Plan::set_distributed_impl(const ThalloX_Distributed& cfg)
         return 0;
     }
     const bool flat = plugin->dist_flat_form();         // single-image energies in the single-reduction form (shape_from_shading); else image_warping's one-kernel form
-    if (!plugin->supports_row_slabs() || (flat && (!plugin->apply_returns_sums() || plugin->unknown_images().size() != 1))) { set_error("distributed: %s has no row-slab form", plugin->name()); return -1; }
+    if (!plugin->supports_row_slabs() || (flat && (!plugin->slab_returns_sums() || plugin->unknown_images().size() != 1))) {
+        const char* why = plugin->slab_setup_error();
+        set_error("distributed: %s has no row-slab form%s%s", plugin->name(), why[0] ? ": " : "", why);
+        return -1;
+    }
     if (lm_ && !flat) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); return -1; }
     if (cfg.world < 1 || cfg.world > THALLO_DIST_MAX_WORLD || cfg.rank < 0 || cfg.rank >= cfg.world) { set_error("distributed: rank %d of %d (at most %d ranks)", cfg.rank, cfg.world, THALLO_DIST_MAX_WORLD); return -1; }
     if (cfg.world > 1 && !cfg.allgather && !(rccl_ && rccl_->world == cfg.world && rccl_->rank == cfg.rank)) { set_error("distributed: world > 1 needs an all-gather callback (or ThalloX_PlanUseRccl)"); return -1; }
@@ -315,9 +319,15 @@ int Plan::set_distributed_impl(const ThalloX_Distributed& cfg)
         bool mem = ensure_sums_buffer() == 0;
         if (mem && plugin->one_kernel_slab() && !plugin->use_preconditioner() && ensure_iter_buffers()) mem = false;       // (r', Ap' of the one-launch-per-iteration slab loop)
         if (mem && (D.ctl.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(D.ctl.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess)) mem = false;
+        const bool unit_ok = plugin->slab_setup_ok();                    // (generated energies: the slab unit compiled on this rank)
+        const std::string unit_err = unit_ok ? "" : plugin->slab_setup_error();
         bool all = false;
-        if (dist_agree(mem, all)) return -1;                             // the first use of the caller's all-gather: fails here, not mid-solve
-        if (!all) { set_error(mem ? "distributed: another rank ran out of device memory" : "distributed: out of device memory"); return -1; }
+        if (dist_agree(mem && unit_ok, all)) return -1;                  // the first use of the caller's all-gather: fails here, not mid-solve
+        if (!all) {
+            if (!unit_ok) set_error("distributed: rank %d: %s", cfg.rank, unit_err.c_str());
+            else set_error(mem ? "distributed: another rank could not set up its row slab (out of device memory, or its generated slab kernels failed to build)" : "distributed: out of device memory");
+            return -1;
+        }
         // ---- device-side exchange (thallo_hip_dist_xrows): scalar ring + row inbox in one IPC allocation per rank; decided by every rank alike
         D.want_p2p = cfg.device_exchange != 0;
         {   const char* e = env_switch("THALLO_DIST_P2P"); if (e && e[0] == '0') D.want_p2p = false; }
