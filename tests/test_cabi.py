@@ -103,6 +103,12 @@ def test_marching_geometry_search_is_bounded(L):
         L.thallo_hip_march_debug_set(6, 256)
         assert L.thallo_hip_iw_march_rows(2048, 2048) == 35          # 17 strips x ceil(59 segments / 4 waves) = 255 workgroups <= 256
         assert L.thallo_hip_iw_march_rows(2048, 256) == 5            # 17 x ceil(52 / 4) = 221
+        # ... and the prefetch depth those rows get (tests/march_classes.py reads MARCH_RC_DEEP_ROWS from the source): should the threshold move, this fails and the
+        # class coverage of the forced-R sweep (tests/test_march_classes.py) is re-evaluated on purpose instead of shapes changing depth silently
+        import march_classes as mc
+        assert mc.DEEP_ROWS == 24 and mc.depth(35) == 4 and mc.depth(5) == 2
+        assert mc.pick_rows(2048, 2048, 0, forced_cap=256) == 35 and mc.pick_rows(2048, 256, 0, forced_cap=256) == 5
+        assert {(mc.depth(35), n) for n in (35, 18)} == mc.depth_n_pairs([(2048, 2048)], cus=256)      # 58 segments of 35 rows and one of 18
         assert L.thallo_hip_iw_march_rows(124 * 256, 64) > 0         # exactly 256 strips: one segment row
         assert L.thallo_hip_iw_march_rows(124 * 256 + 2, 64) == 0    # 257 strips: no R fits -> 0, not an endless loop
         assert L.thallo_hip_iw_march_rows(65536, 4096) == 0
