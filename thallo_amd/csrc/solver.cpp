@@ -452,6 +452,35 @@ void Plan::linear_update_tail(int L, bool batched)
     plugin->unknowns_written();
 }
 
+// The head and the tail that every PCG-loop form of a GN step shares (the direct solve records other coarse events and keeps its own lines).
+// gn_begin: "Nonlinear Setup" around PCGInit1 (alphaN_0's partials into slot B = 2), "Linear Solve" started; false: the launch failed, the step ends.
+bool Plan::gn_begin(int& ev_lin)
+{
+    hipStream_t s = ctx.stream;
+    const int ev_setup = timer_.start("Nonlinear Setup", s);
+    cur_ = 0;
+    const int nb = plugin->pcg_init(ctx, v_, cur_, slot(2));
+    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
+    set_nb(2, nb); finish(2);
+    timer_.stop(ev_setup, s);
+    ev_lin = timer_.start("Linear Solve", s);
+    return true;
+}
+// gn_finish: the loop is enqueued, "Nonlinear Finish" starts (the caller's update of the unknowns follows); gn_end: the step is counted, its events end
+int Plan::gn_finish(int L, int ev_lin)
+{
+    last_l_iters = L;
+    timer_.stop(ev_lin, ctx.stream);
+    return timer_.start("Nonlinear Finish", ctx.stream);
+}
+int Plan::gn_end(int ev_fin, int ev_iter)
+{
+    sp.nIter++;
+    timer_.stop(ev_fin, ctx.stream);
+    timer_.stop(ev_iter, ctx.stream);
+    return 1;
+}
+
 int Plan::step_gn(int ev_iter)
 {   // GN branch, fused schedule (DESIGN.md "PCG schedule")
     if (plugin->direct_solve()) {                     // the linear system solved exactly, no PCG loop (gauss_newton.t:1612-1613)
@@ -472,16 +501,9 @@ int Plan::step_gn(int ev_iter)
     if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok()) return step_gn_resident(ev_iter);
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
-    const int L = sp.lIterations;
-    hipStream_t s = ctx.stream;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
-    const int B = 2;                       // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
+    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    int ev_lin, nb;
+    if (!gn_begin(ev_lin)) return 0;
     const bool batched = plugin->batches_delta() && batch_delta_;      // every other delta update deferred (thallo_hip.h THALLO_IW_STEP1_MODE)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
@@ -495,14 +517,9 @@ int Plan::step_gn(int ev_iter)
         if (nb < 0) { set_error("PCGStep2 launch failed (%d)", nb); return 0; }
         set_nb(jB, nb); finish(jB);
     }
-    last_l_iters = L;
-    timer_.stop(ev_lin, s);
-    const int ev_fin = timer_.start("Nonlinear Finish", s);
+    const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, batched);
-    sp.nIter++;
-    timer_.stop(ev_fin, s);
-    timer_.stop(ev_iter, s);
-    return 1;
+    return gn_end(ev_fin, ev_iter);
 }
 
 // ------------------------------------------------------------------ Levenberg-Marquardt branch
@@ -529,16 +546,10 @@ int Plan::ensure_lm_vectors()
 int Plan::step_gn_one_kernel(int ev_iter)
 {   // GN branch, ONE kernel + one scalar launch per PCG iteration (DESIGN.md "PCG schedule", thallo_hip_iw_pcg_iter)
     if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
-    const int L = sp.lIterations;
+    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
-    const int B = 2;                       // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
+    int ev_lin, nb;
+    if (!gn_begin(ev_lin)) return 0;
     // Deferred finish (where the plugin offers it): the launch of iteration k adds up iteration k-1's partials
     // itself -- alphaD_{k-1} and betaN_{k-1} = N - 2 alpha S1 + alpha^2 S2 -- while its first rows load, instead of iteration k-1's last workgroup
     // reading them back at the very end of its launch; one one-wave launch per GN step finishes the last iteration.
@@ -652,9 +663,7 @@ int Plan::step_gn_one_kernel(int ev_iter)
             fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
         }
     }
-    last_l_iters = L;
-    timer_.stop(ev_lin, s);
-    const int ev_fin = timer_.start("Nonlinear Finish", s);
+    const int ev_fin = gn_finish(L, ev_lin);
     if (ring && L > 0) {
         // PCGLinearUpdate with every pending term: all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first
         if (flush_ring(L - 1 - THALLO_HIP_MAX_UPDATE_TERMS) || wait_for(L)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
@@ -671,10 +680,7 @@ int Plan::step_gn_one_kernel(int ev_iter)
         }
         plugin->unknowns_written();
     } else linear_update_tail(L, batched);
-    sp.nIter++;
-    timer_.stop(ev_fin, s);
-    timer_.stop(ev_iter, s);
-    return 1;
+    return gn_end(ev_fin, ev_iter);
 }
 
 // The plan's second stream (lowest priority, non-blocking: the loop's stream may be the NULL stream): background updates of delta next to the PCG loop
@@ -735,44 +741,27 @@ int Plan::step_gn_resident(int ev_iter)
     // trace and the cost path do not know which schedule ran.  Replaces the loop of gauss_newton.t:1615-1687.
     if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
     const int L = sp.lIterations, B = 2;
-    hipStream_t s = ctx.stream;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
-    nb = plugin->pcg_resident(ctx, v_, L, sum(B), scal(B + 1));
+    int ev_lin;
+    if (!gn_begin(ev_lin)) return 0;
+    const int nb = plugin->pcg_resident(ctx, v_, L, sum(B), scal(B + 1));
     if (nb < 0) { set_error("PCGLoopResident launch failed (%d)", nb); return 0; }
     for (int k = 0; k < L; ++k) { const int jD = B + 2 * k + 1, jB = jD + 1; set_nb(jD, 1); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
     cur_ = L & 1;
     resident_used_ = true;
-    last_l_iters = L;
-    timer_.stop(ev_lin, s);
-    const int ev_fin = timer_.start("Nonlinear Finish", s);
+    const int ev_fin = gn_finish(L, ev_lin);
     if (plugin->resident_updates_unknowns()) plugin->unknowns_written();      // (PCGLinearUpdate rode in the resident launch)
     else linear_update_tail(L, false);
-    sp.nIter++;
-    timer_.stop(ev_fin, s);
-    timer_.stop(ev_iter, s);
-    return 1;
+    return gn_end(ev_fin, ev_iter);
 }
 
 int Plan::step_gn_expanded(int ev_iter)
 {   // GN branch, single-reduction form for gather energies: per PCG iteration pcg_update (flat) + applyJTJ with sums + scalars_finish
     // (thallo_hip.h "single-reduction PCG form") instead of PCGStep3 + applyJTJ + PCGStep2 and their finish launches
     if (ensure_sums_buffer()) { set_error("out of device memory for the single-reduction schedule"); return 0; }
-    const int L = sp.lIterations;
+    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
-    const int B = 2;                       // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
+    int ev_lin, nb;
+    if (!gn_begin(ev_lin)) return 0;
     // THALLO_FIN_IN_KERNEL unset: the finish of iteration k-1 -- alphaD, betaN from the applyJTJ launch's partials -- is folded into the flat update of iteration k
     // (thallo_hip_pcg_update_fin: every workgroup adds the partials up for itself, the same bits), so the applyJTJ launch has no tail; one one-wave launch finishes the last iteration
     const bool defer = fin_in_kernel_ && fin_deferred_;
@@ -800,15 +789,9 @@ int Plan::step_gn_expanded(int ev_iter)
         }
         fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
     }
-    const bool batched = false;
-    last_l_iters = L;
-    timer_.stop(ev_lin, s);
-    const int ev_fin = timer_.start("Nonlinear Finish", s);
-    linear_update_tail(L, batched);
-    sp.nIter++;
-    timer_.stop(ev_fin, s);
-    timer_.stop(ev_iter, s);
-    return 1;
+    const int ev_fin = gn_finish(L, ev_lin);
+    linear_update_tail(L, false);
+    return gn_end(ev_fin, ev_iter);
 }
 
 int Plan::ensure_sums_buffer()
@@ -838,320 +821,394 @@ float Plan::read_sum(int j)
     return f;
 }
 
+// ---- One LM step (gauss_newton.t:1545-1785 with every UsesLambda() branch taken): lm_setup, ONE of four PCG loops (lm_schedule), lm_finish.
+//
+// The zeta test (:1666-1686) runs ON THE DEVICE: all lIterations iterations are enqueued, a one-wave kernel behind each PCGStep2
+// (or PCGStep2's own last workgroup) applies the test and sets the gate word, after which the remaining launches of the loop return at
+// once; delta, r, z stay as of the break.  One read-back per GN step (iterations done, delta.J^T J delta, delta.b, new cost) instead of
+// the reference's blocking 4-byte copy per PCG iteration (fetchQ :1146-1150); iteration counts and costs are pinned against the oracle's
+// host-side test (tests/test_gpu_parity.py::test_lm_device_side_zeta_matches_the_oracle).
+//
+// One row slab of a multi-GPU run (flat form, solver_dist.cpp): the energy-independent kernels run on the owned rows' sub-vectors [o, o + n),
+// p is kept current on the ghost rows too ([oe, oe + ne)), and every reduction is made global where it is produced: per PCG iteration one
+// exchange for alphaD and one for [betaN, q | ghost rows of z]; all ranks see the same scalars, so gate and trust region cannot diverge.
+Plan::LmStep::LmStep(Plan& plan, int ev_iter_)
+    : P(plan), s(plan.ctx.stream), L(plan.sp.lIterations), T0(2 * L + 4), T1(2 * L + 5),
+      period(plan.sp.residual_reset_period > 0 ? plan.sp.residual_reset_period : (1 << 30)), slab(plan.dist_ != nullptr),
+      pc(plan.plugin->use_preconditioner()), fold_ctc(plan.plugin->apply_adds_ctc()),
+      // (round 6: plugins whose PCGInit1 launch also finalises the diagonal -- shape_from_shading on packed planes, one GPU; THALLO_LM_FOLD_STEP=0: the two launches, A/B)
+      fold_init(!slab && plan.lm_fold_step_ && plan.plugin->init_folds_lm_diagonal()),
+      lmst((float*)plan.scratch_.ptr + 16), gate(reinterpret_cast<const unsigned*>(lmst) + 1), ev_iter(ev_iter_)
+{
+    const DistState* D = P.dist_;
+    o = slab ? D->rowlen * D->row0 : 0; n = slab ? D->rowlen * (D->row1 - D->row0) : P.v_.n;
+    oe = slab ? D->rowlen * (D->row0 - D->top) : 0; ne = slab ? D->rowlen * (D->row1 + D->bot - (D->row0 - D->top)) : P.v_.n;
+}
+
+// A launch of this rank that fails: on one GPU the step ends (return 0).  One slab of several must not leave the collective sequence: it goes on
+// issuing every exchange of the step with poisoned payloads, skips its own launches, and the error becomes everybody's at the cost evaluation
+// at the end of the step (solver_dist.cpp, DistState::failed).
+void Plan::LmStep::check(int rc, const char* what)
+{
+    if (rc >= 0 || skip()) return;
+    if (slab) P.dist_fail("%s failed (%d)", what, rc); else { set_error("%s failed (%d)", what, rc); failed = true; }
+}
+
 int Plan::step_lm(int ev_iter)
-{   // gauss_newton.t:1545-1785 with every UsesLambda() branch taken; unfused (reference-shaped) PCG schedule because
-    // q = 0.5 delta.(r+b) needs the current delta inside PCGStep2 and PCGStep1_Finish adds CtC*p.
-    // Slots: 0 cost, 1 q, B.. as in GN (alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2); last two: scratch dots.
-    //
-    // The zeta test (:1666-1686) runs ON THE DEVICE: all lIterations iterations are enqueued, a one-wave kernel behind each PCGStep2
-    // (or PCGStep2's own last workgroup) applies the test and sets the gate word, after which the remaining launches of the loop return at
-    // once; delta, r, z stay as of the break.  One read-back per GN step (iterations done, delta.J^T J delta, delta.b, new cost) instead of
-    // the reference's blocking 4-byte copy per PCG iteration (fetchQ :1146-1150); iteration counts and costs are pinned against the oracle's
-    // host-side test (tests/test_gpu_parity.py::test_lm_device_side_zeta_matches_the_oracle).
-    hipStream_t s = ctx.stream;
-    const int L = sp.lIterations, B = 2, QS = 1, T0 = 2 * L + 4, T1 = 2 * L + 5;
-    // One row slab of a multi-GPU run (flat form, solver_dist.cpp): the energy-independent kernels run on the owned rows' sub-vectors [o, o + n),
-    // p is kept current on the ghost rows too ([oe, oe + ne)), and every reduction is made global where it is produced: per PCG iteration one
-    // exchange for alphaD and one for [betaN, q | ghost rows of z]; all ranks see the same scalars, so gate and trust region cannot diverge.
-    const bool slab = dist_ != nullptr;
-    // A launch of this rank that fails: on one GPU the step ends (return 0).  One slab of several must not leave the collective sequence: it goes on
-    // issuing every exchange of the step with poisoned payloads, skips its own launches, and the error becomes everybody's at the cost evaluation
-    // at the end of the step (solver_dist.cpp, DistState::failed).
-    bool failed = false;
-    auto skip = [&]() { return failed || (slab && dist_->failed); };
-    auto check = [&](int rc, const char* what) {
-        if (rc >= 0 || skip()) return;
-        if (slab) dist_fail("%s failed (%d)", what, rc); else { set_error("%s failed (%d)", what, rc); failed = true; }
-    };
-    if (ensure_lm_vectors()) check(-1, "allocating the LM vectors");
-    if (failed) return 0;
-    const long o = slab ? dist_->rowlen * dist_->row0 : 0, n = slab ? dist_->rowlen * (dist_->row1 - dist_->row0) : v_.n;
-    const long oe = slab ? dist_->rowlen * (dist_->row0 - dist_->top) : 0, ne = slab ? dist_->rowlen * (dist_->row1 + dist_->bot - (dist_->row0 - dist_->top)) : v_.n;
-    auto global = [&](int j) { return slab ? dist_sum_slot(j) : 0; };                         // nonzero: the collective itself failed
-    auto global_rows = [&](int j, float* vec) { return slab ? dist_sum_and_rows(j, vec) : 0; };
-    const bool pc = plugin->use_preconditioner();
-    const bool fold_ctc = plugin->apply_adds_ctc();
+{
+    LmStep st(*this, ev_iter);
+    if (!lm_setup(st)) return 0;
+    {   GateOff gate_off(ctx, st.gate);
+        switch (lm_schedule(st)) {
+        case LmSchedule::Resident:      lm_loop_resident(st); break;
+        case LmSchedule::OneKernel:     lm_loop_one_kernel(st); break;
+        case LmSchedule::OneKernelSlab: lm_loop_one_kernel_slab(st); break;
+        case LmSchedule::Reference:     lm_loop_reference(st); break;
+        }
+    }
+    if (st.failed || st.coll_failed) return 0;
+    return lm_finish(st);
+}
+
+// Vectors, the trust region's start, PCGInit1 + PCGFinalizeDiagonal, alphaN_0 over the ranks, the LM state reset.  false: the step ends.
+bool Plan::lm_setup(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const int B = st.B; const long o = st.o;
+    if (ensure_lm_vectors()) st.check(-1, "allocating the LM vectors");
+    if (st.failed) return false;
+    if (!st.slab && ensure_sums_buffer()) return false;               // (the zeta test by PCGStep2's last workgroup takes its tickets)
+    const int ev_setup = timer_.start("Nonlinear Setup", s);
+    lm_trust_region_at_start();
+    cur_ = 0;
+    int nb = 0;
+    if (st.fold_init) {
+        if (!st.skip()) {
+            nb = plugin->pcg_init_lm(ctx, v_, cur_, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal, sp.nIter == 0 ? 1 : 0, slot(B));
+            st.check(nb, "PCGInit1 (+ PCGFinalizeDiagonal) launch");
+        }
+    } else {
+        if (!st.skip()) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); st.check(nb, "PCGInit1 launch"); }        // r, raw diag (v_.diag); delta = 0
+        if (!st.skip()) {
+            TimedLaunch t(ctx, "PCGFinalizeDiagonal");                // :1596-1604 (alphaN restarts from 0)
+            nb = thallo_hip_lm_finalize_diagonal(v_.diag + o, v_.SSq + o, v_.CtC + o, v_.pre + o, v_.r + o, v_.b + o, v_.z + o, st.n, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal,
+                                                 sp.nIter == 0 ? 1 : 0, st.pc ? 1 : 0, slot(B), s);
+            st.check(nb, "PCGFinalizeDiagonal launch");
+        }
+    }
+    if (st.failed) return false;
+    if (!st.skip()) set_nb(B, nb);
+    if (st.global_rows(B, v_.z)) return false;                        // alphaN_0 over all ranks; ghost rows of z
+    if (!st.skip()) st.check(thallo_hip_lm_state_reset(st.lmst, s), "LM state reset");       // (delta = 0 -> q = 0, :965)
+    if (st.failed) return false;
+    timer_.stop(ev_setup, s);
+    st.ev_lin = timer_.start("Linear Solve", s);
+    return true;
+}
+
+// Which PCG loop this step runs (DESIGN.md §3 "LM schedules").  All but the reference-shaped loop need lIterations within one residual-reset period (the reset then falls
+// on the last iteration and changes nothing that is read afterwards) or, on one GPU, a plugin whose iteration can start from a reset residual (lm_iter_after_reset;
+// bundle adjustment's three-launch form).  ensure_iter_buffers() allocates: it runs only where everything in front of it holds.
+Plan::LmSchedule Plan::lm_schedule(const LmStep& st)
+{
+    const int L = st.L, period = st.period;
+    // round 6: the loop, the zeta test, the owed update of delta, the model cost and the update of the unknowns in ONE resident launch (plugins whose state fits the chip's
+    // registers: shape_from_shading at the size of the reference's data set).  THALLO_RESIDENT=0: one launch per iteration (A/B).
+    if (!st.slab && st.fold_init && lm_fold_step_ && lm_fold_p_ && st.fold_ctc && one_kernel_ && plugin->resident_lm_ok() && L >= 1 && L <= period) return LmSchedule::Resident;
+    // One launch per LM iteration (plugins that offer it: shape_from_shading's marching kernel): the vector update, PCGStep3, (J^T J + CtC) p, all sums and the zeta test in
+    // pcg_iter_lm.  THALLO_LM_FOLD_P=0: the reference-shaped loop (A/B).
+    if (!st.slab && lm_fold_p_ && st.fold_ctc && plugin->lm_one_kernel() && L >= 1 && (L <= period || plugin->lm_iter_after_reset()) && v_.p[1] != nullptr && ensure_iter_buffers() == 0)
+        return LmSchedule::OneKernel;
+    // ... and on a row slab (device-side transport; plugins whose pcg_iter_lm keeps the ghost rows current)
+    if (st.slab && dist_->flat && dist_->xrows_now && lm_fold_p_ && st.fold_ctc && plugin->lm_one_kernel_slab() && L >= 1 && L <= period &&
+        v_.p[1] != nullptr && v_.r2 != nullptr && v_.Ap2 != nullptr && v_.s12b != nullptr) return LmSchedule::OneKernelSlab;
+    return LmSchedule::Reference;
+}
+
+// One launch per LM iteration on a row slab: the launch stores partials only, ONE exchange per LM iteration carries the 13 sums and the boundary rows of the new A p,
+// finishes alphaD_k, betaN_k, q_{k+1} and applies the zeta test (thallo_hip_dist_xrows_lm).  Ghost rows of r and M^-1 are fetched once per step.
+void Plan::lm_loop_one_kernel_slab(LmStep& st)
+{
+    const int L = st.L, B = st.B;
+    if (st.global_rows(-1, v_.r) || st.global_rows(-1, v_.pre)) { st.coll_failed = true; return; }
+    cur_ = 0;
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        const thallo_fin_t fin = { sum(jN), nullptr, nullptr, nullptr };
+        if (!st.skip()) {
+            nb = plugin->pcg_iter_lm(ctx, v_, cur_, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), slot(jD), fin, st.lmst, k, sp.q_tolerance);
+            st.check(nb, "PCGIteration (LM) launch");
+        }
+        if (!st.skip()) set_nb(jD, nb);
+        float* Ao = v_.Abuf(cur_ ^ 1);
+        cur_ ^= 1;
+        if (dist_xrows_lm(Ao, jN, jD, jB, nb, st.lmst, k)) { st.coll_failed = true; return; }
+        st.k_done = k + 1;
+    }
+    if (!st.skip()) {
+        TimedLaunch t(ctx, "PCGUpdate");
+        st.check(thallo_hip_lm_owed_delta(v_.delta + st.o, v_.p[1] + st.o, v_.p[0] + st.o, st.n, scal(B), scal(B + 1), 2, st.lmst, L, st.s), "PCGUpdate (owed delta) launch");
+    }
+}
+
+// The whole loop, the owed update of delta, the model cost and the update of the unknowns in one resident launch
+void Plan::lm_loop_resident(LmStep& st)
+{
+    const int L = st.L, B = st.B;
+    cur_ = 0;
+    finish(B);
+    const int nb = plugin->pcg_resident_lm(ctx, v_, L, sum(B), scal(B + 1), st.lmst, sp.q_tolerance, slot(st.T0), slot(st.T1));
+    st.check(nb, "PCGLoopResident (LM) launch");
+    if (st.failed) return;
+    for (int k = 0; k < L; ++k) { const int jD = B + 2 * k + 1, jB = jD + 1; set_nb(jD, 1); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+    set_nb(st.T0, nb); set_nb(st.T1, nb);
+    st.model_cost_done = true; st.k_done = L; resident_used_ = true;
+}
+
+// One launch per LM iteration on one GPU (or the plugin's few: bundle adjustment's three); every residual_reset_period-th iteration is followed by the reference's reset
+// (:1653-1657) as launches of its own.  Behind the loop the one update of delta it still owes, alone or inside the one-launch model cost.
+void Plan::lm_loop_one_kernel(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const int L = st.L, B = st.B, period = st.period;
+    float* lmst = st.lmst;
+    cur_ = 0;
+    // alphaN_0 as a word (the owed-delta launch reads the scalars of iteration "done - 1" by address)
+    st.check(thallo_hip_finish_sum(partial_sum(B), scal(B), s), "alphaN_0 sum");
+    if (!st.failed) fin_[B] = 1;
+    bool after_reset = false; int reset_nb = 0;
+    // THALLO_FIN_IN_KERNEL unset and the plugin's iteration is several launches (lm_iter_defers_finish: bundle adjustment): the applyJTJ launches of iteration k leave partials
+    // only and the flat update of iteration k + 1 finishes them -- words, q, the zeta test -- in every workgroup (thallo_hip_pcg_update_lm_fin); iterations that a residual
+    // reset follows (the reset needs alpha_k first) and the last one finish in their own launch.  Q0 / Q1 alternate between words 0 and 6 of the state by parity.
+    const bool defer = fin_deferred_ && plugin->lm_iter_defers_finish();
+    auto own_finish = [&](int k) { return !defer || k == L - 1 || (((k + 1) % period) == 0 && k + 1 < L); };
+    int nb = 0, nb_prev = 0;
+    for (int k = 0; k < L && !st.failed; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        const thallo_fin_t fin = { sum(jN), own_finish(k) ? v_.fin_tickets : nullptr, scal(jD), scal(jB) };
+        const bool finish_prev = defer && k > 0 && !own_finish(k - 1);
+        const thallo_sum_t aD_prev_partials = { slot(k ? jD - 2 : jD), nb_prev };
+        ctx.lm_defer_aD_word = finish_prev ? scal(jD - 2) : nullptr; ctx.lm_defer_bN_word = finish_prev ? scal(jN) : nullptr;
+        ctx.lm_q_in = defer ? ((k & 1) ? 6 : 0) : 0; ctx.lm_q_out = defer ? ((k & 1) ? 0 : 6) : 0;
+        // behind a reset the iteration's first launch gets betaN_{k-1} as the reset's PARTIALS and replaces the word (the expansion's value) by their sum; everything
+        // later -- this iteration's finish, the next one's alpha, the owed update of delta, alpha_beta_trace -- reads the word, which is valid either way (a loop that the
+        // zeta test ended AT the reset iteration never ran the reset: its word is the expansion's)
+        const thallo_sum_t bn_partials = { slot(jN), reset_nb };
+        ctx.lm_reset_bn_word = after_reset ? scal(jN) : nullptr;
+        nb = plugin->pcg_iter_lm(ctx, v_, cur_, k == 0, sum(k ? jN - 2 : jN), finish_prev ? aD_prev_partials : sum(k ? jD - 2 : jD), after_reset ? bn_partials : sum(jN), slot(jD), fin,
+                                 lmst, k, sp.q_tolerance);
+        ctx.lm_reset_bn_word = nullptr; after_reset = false;
+        ctx.lm_defer_aD_word = ctx.lm_defer_bN_word = nullptr; ctx.lm_q_in = ctx.lm_q_out = 0;
+        nb_prev = nb;
+        st.check(nb, "PCGIteration (LM) launch");
+        if (st.failed) break;
+        set_nb(jD, nb); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
+        cur_ ^= 1;
+        st.k_done = k + 1;
+        if (((k + 1) % period) == 0 && k + 1 < L) {
+            // residual reset (:1653-1657; on the last iteration it changes nothing that is read afterwards): delta_{k+1} = delta_k + alpha_k p_k now,
+            // r = b - (J^T J + CtC) delta and the partials of betaN_k = r . M^-1 r (the next iteration's first launch adds them up, replaces the expansion's word by
+            // the sum and forms p_{k+1} only); q_{k+1} and the zeta test stay the launch's own -- the same quantity, and the gate word it may have set ends these
+            // launches too.
+            { TimedLaunch t(ctx, "PCGStep2"); st.check(thallo_hip_lm_step2_first_half(v_.delta, v_.p[cur_], st.n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
+            if (st.failed) break;
+            nb = plugin->lm_reset_residual(ctx, v_, slot(jB));
+            st.check(nb, "residual reset launch");
+            if (st.failed) break;
+            reset_nb = nb;
+            after_reset = true;
+        }
+    }
+    if (st.failed) return;
+    // round 6: the owed update of delta, the model cost's applyJTJ and its dot product in ONE launch (plugins that offer it); delta moves to the other buffer
+    st.model_cost_done = lm_fold_step_ && plugin->lm_model_cost_one_launch();
+    if (st.model_cost_done) {
+        nb = plugin->lm_model_cost(ctx, v_, scal(B), scal(B + 1), 2, lmst, L, slot(st.T0), slot(st.T1), true);      // (... and savePreviousUnknowns + PCGLinearUpdate)
+        st.check(nb, "PCGModelCost launch");
+        if (!st.failed) { set_nb(st.T0, nb); set_nb(st.T1, nb); std::swap(v_.delta, v_.Adelta); }
+    } else {            // p_k lives in p[1] for even k, p[0] for odd k
+        TimedLaunch t(ctx, "PCGUpdate");
+        st.check(thallo_hip_lm_owed_delta(v_.delta, v_.p[1], v_.p[0], st.n, scal(B), scal(B + 1), 2, lmst, L, s), "PCGUpdate (owed delta) launch");
+    }
+}
+
+// The reference-shaped (unfused) loop -- q = 0.5 delta.(r+b) needs the current delta inside PCGStep2 and PCGStep1_Finish adds CtC*p -- on one GPU or a row slab:
+// PCGStep3 / PCGStep1 / PCGStep1_Finish / PCGStep2 / zeta, the residual reset every residual_reset_period iterations.
+void Plan::lm_loop_reference(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const int L = st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const long o = st.o, n = st.n;
+    const bool slab = st.slab, fold_ctc = st.fold_ctc;
+    float* lmst = st.lmst;
     // PCGStep3 folded into the apply too (one GPU; plugins that offer it; THALLO_LM_FOLD_P=0: A/B, read_ab_switches)
     const bool fold_p = lm_fold_p_ && fold_ctc && !slab && plugin->apply_folds_pupdate() && v_.p[1] != nullptr;
     // the zeta test by PCGStep2's last workgroup (one GPU): one launch less per iteration.  A slab needs the GLOBAL q first.
-    if (!slab && ensure_sums_buffer()) return 0;
     const bool zeta_in_step2 = !slab;
-    float* lmst = (float*)scratch_.ptr + 16;                          // 8 words: Q0, gate, iterations done, | dJJd, db, new cost
-    const unsigned* gate = reinterpret_cast<const unsigned*>(lmst) + 1;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
-    if (sp.nIter == 0) { radius_ = sp.trust_region_radius; decrease_factor_ = sp.radius_decrease_factor; }   // :1185-1186 (copied at init)
-    cur_ = 0;
-    int nb = 0;
-    // (round 6: plugins whose PCGInit1 launch also finalises the diagonal -- shape_from_shading on packed planes, one GPU; THALLO_LM_FOLD_STEP=0: the two launches, A/B)
-    const bool fold_init = !slab && lm_fold_step_ && plugin->init_folds_lm_diagonal();
-    if (fold_init && !skip()) {
-        nb = plugin->pcg_init_lm(ctx, v_, cur_, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal, sp.nIter == 0 ? 1 : 0, slot(B));
-        check(nb, "PCGInit1 (+ PCGFinalizeDiagonal) launch");
-    }
-    if (!fold_init && !skip()) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); check(nb, "PCGInit1 launch"); }        // r, raw diag (v_.diag); delta = 0
-    if (!fold_init && !skip()) {
-        TimedLaunch t(ctx, "PCGFinalizeDiagonal");                    // :1596-1604 (alphaN restarts from 0)
-        nb = thallo_hip_lm_finalize_diagonal(v_.diag + o, v_.SSq + o, v_.CtC + o, v_.pre + o, v_.r + o, v_.b + o, v_.z + o, n, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal,
-                                             sp.nIter == 0 ? 1 : 0, pc ? 1 : 0, slot(B), s);
-        check(nb, "PCGFinalizeDiagonal launch");
-    }
-    if (failed) return 0;
-    if (!skip()) set_nb(B, nb);
-    if (global_rows(B, v_.z)) return 0;                               // alphaN_0 over all ranks; ghost rows of z
-    if (!skip()) check(thallo_hip_lm_state_reset(lmst, s), "LM state reset");       // (delta = 0 -> q = 0, :965)
-    if (failed) return 0;
-    timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
     float* p = v_.p[0];
-    int k_done = 0;
-    thallo_hip_lm_set_gate(gate); ctx.gate = gate;
-    bool coll_failed = false;                                         // a collective itself failed: nothing left to stay in step with
-    bool model_cost_done = false;                                     // the two sums of the model cost are already in slots T0 / T1 (one launch behind the one-launch loop)
-    // One launch per LM iteration (one GPU; plugins that offer it: shape_from_shading's marching kernel; lIterations within one residual-reset period, where the reset
-    // -- it falls on the last iteration -- changes nothing that is read afterwards): the vector update, PCGStep3, (J^T J + CtC) p, all sums and the zeta test in
-    // pcg_iter_lm; behind the loop the one update of delta it still owes.  THALLO_LM_FOLD_P=0: the reference-shaped loop (A/B).
-    const int period = sp.residual_reset_period > 0 ? sp.residual_reset_period : (1 << 30);
-    // Plugins whose iteration can start from a reset residual (lm_iter_after_reset; bundle adjustment's three-launch form) run any L: every residual_reset_period-th iteration
-    // is followed by the reference's reset (:1653-1657) as launches of its own, below.
-    // round 6: the loop, the zeta test, the owed update of delta, the model cost and the update of the unknowns in ONE resident launch (plugins whose state fits the chip's
-    // registers: shape_from_shading at the size of the reference's data set); lIterations within one residual-reset period.  THALLO_RESIDENT=0: the launches below (A/B).
-    const bool resident_lm = !slab && fold_init && lm_fold_step_ && lm_fold_p_ && fold_ctc && one_kernel_ && plugin->resident_lm_ok() && L >= 1 && L <= period;
-    const bool one_kernel_lm = !resident_lm && !slab && lm_fold_p_ && fold_ctc && plugin->lm_one_kernel() && L >= 1 && (L <= period || plugin->lm_iter_after_reset()) && v_.p[1] != nullptr &&
-                               ensure_iter_buffers() == 0;
-    // ... and on a row slab of a multi-GPU run (device-side transport; plugins whose pcg_iter_lm keeps the ghost rows current): the launch stores partials only, ONE
-    // exchange per LM iteration carries the 13 sums and the boundary rows of the new A p, finishes alphaD_k, betaN_k, q_{k+1} and applies the zeta test
-    // (thallo_hip_dist_xrows_lm).  Ghost rows of r and M^-1 are fetched once per step.
-    const bool one_kernel_lm_slab = slab && dist_->flat && dist_->xrows_now && lm_fold_p_ && fold_ctc && plugin->lm_one_kernel_slab() && L >= 1 && L <= period &&
-                                    v_.p[1] != nullptr && v_.r2 != nullptr && v_.Ap2 != nullptr && v_.s12b != nullptr;
-    if (one_kernel_lm_slab) {
-        if (global_rows(-1, v_.r) || global_rows(-1, v_.pre)) return 0;
-        cur_ = 0;
-        for (int k = 0; k < L; ++k) {
-            const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-            const thallo_fin_t fin = { sum(jN), nullptr, nullptr, nullptr };
-            if (!skip()) {
-                nb = plugin->pcg_iter_lm(ctx, v_, cur_, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), slot(jD), fin, lmst, k, sp.q_tolerance);
-                check(nb, "PCGIteration (LM) launch");
-            }
-            if (!skip()) set_nb(jD, nb);
-            float* Ao = v_.Abuf(cur_ ^ 1);
-            cur_ ^= 1;
-            if (dist_xrows_lm(Ao, jN, jD, jB, nb, lmst, k)) { coll_failed = true; break; }
-            k_done = k + 1;
-        }
-        if (!coll_failed && !skip()) {
-            TimedLaunch t(ctx, "PCGUpdate");
-            check(thallo_hip_lm_owed_delta(v_.delta + o, v_.p[1] + o, v_.p[0] + o, n, scal(B), scal(B + 1), 2, lmst, L, s), "PCGUpdate (owed delta) launch");
-        }
-    }
-    if (resident_lm) {
-        cur_ = 0;
-        finish(B);
-        nb = plugin->pcg_resident_lm(ctx, v_, L, sum(B), scal(B + 1), lmst, sp.q_tolerance, slot(T0), slot(T1));
-        check(nb, "PCGLoopResident (LM) launch");
-        if (!failed) {
-            for (int k = 0; k < L; ++k) { const int jD = B + 2 * k + 1, jB = jD + 1; set_nb(jD, 1); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            set_nb(T0, nb); set_nb(T1, nb);
-            model_cost_done = true; k_done = L; resident_used_ = true;
-        }
-    }
-    if (one_kernel_lm) {
-        cur_ = 0;
-        {   // alphaN_0 as a word (the owed-delta launch reads the scalars of iteration "done - 1" by address)
-            check(thallo_hip_finish_sum(partial_sum(B), scal(B), s), "alphaN_0 sum");
-            if (!failed) fin_[B] = 1;
-        }
-        bool after_reset = false; int reset_nb = 0;
-        // THALLO_FIN_IN_KERNEL unset and the plugin's iteration is several launches (lm_iter_defers_finish: bundle adjustment): the applyJTJ launches of iteration k leave partials
-        // only and the flat update of iteration k + 1 finishes them -- words, q, the zeta test -- in every workgroup (thallo_hip_pcg_update_lm_fin); iterations that a residual
-        // reset follows (the reset needs alpha_k first) and the last one finish in their own launch.  Q0 / Q1 alternate between words 0 and 6 of the state by parity.
-        const bool defer = fin_deferred_ && plugin->lm_iter_defers_finish();
-        auto own_finish = [&](int k) { return !defer || k == L - 1 || (((k + 1) % period) == 0 && k + 1 < L); };
-        int nb_prev = 0;
-        for (int k = 0; k < L && !failed; ++k) {
-            const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-            const thallo_fin_t fin = { sum(jN), own_finish(k) ? v_.fin_tickets : nullptr, scal(jD), scal(jB) };
-            const bool finish_prev = defer && k > 0 && !own_finish(k - 1);
-            const thallo_sum_t aD_prev_partials = { slot(k ? jD - 2 : jD), nb_prev };
-            ctx.lm_defer_aD_word = finish_prev ? scal(jD - 2) : nullptr; ctx.lm_defer_bN_word = finish_prev ? scal(jN) : nullptr;
-            ctx.lm_q_in = defer ? ((k & 1) ? 6 : 0) : 0; ctx.lm_q_out = defer ? ((k & 1) ? 0 : 6) : 0;
-            // behind a reset the iteration's first launch gets betaN_{k-1} as the reset's PARTIALS and replaces the word (the expansion's value) by their sum; everything
-            // later -- this iteration's finish, the next one's alpha, the owed update of delta, alpha_beta_trace -- reads the word, which is valid either way (a loop that the
-            // zeta test ended AT the reset iteration never ran the reset: its word is the expansion's)
-            const thallo_sum_t bn_partials = { slot(jN), reset_nb };
-            ctx.lm_reset_bn_word = after_reset ? scal(jN) : nullptr;
-            nb = plugin->pcg_iter_lm(ctx, v_, cur_, k == 0, sum(k ? jN - 2 : jN), finish_prev ? aD_prev_partials : sum(k ? jD - 2 : jD), after_reset ? bn_partials : sum(jN), slot(jD), fin,
-                                     lmst, k, sp.q_tolerance);
-            ctx.lm_reset_bn_word = nullptr; after_reset = false;
-            ctx.lm_defer_aD_word = ctx.lm_defer_bN_word = nullptr; ctx.lm_q_in = ctx.lm_q_out = 0;
-            nb_prev = nb;
-            check(nb, "PCGIteration (LM) launch");
-            if (failed) break;
-            set_nb(jD, nb); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
-            cur_ ^= 1;
-            k_done = k + 1;
-            if (((k + 1) % period) == 0 && k + 1 < L) {
-                // residual reset (:1653-1657; on the last iteration it changes nothing that is read afterwards): delta_{k+1} = delta_k + alpha_k p_k now,
-                // r = b - (J^T J + CtC) delta and the partials of betaN_k = r . M^-1 r (the next iteration's first launch adds them up, replaces the expansion's word by
-                // the sum and forms p_{k+1} only); q_{k+1} and the zeta test stay the launch's own -- the same quantity, and the gate word it may have set ends these
-                // launches too.
-                { TimedLaunch t(ctx, "PCGStep2"); check(thallo_hip_lm_step2_first_half(v_.delta, v_.p[cur_], n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
-                if (failed) break;
-                nb = plugin->lm_reset_residual(ctx, v_, slot(jB));
-                check(nb, "residual reset launch");
-                if (failed) break;
-                reset_nb = nb;
-                after_reset = true;
-            }
-        }
-        // round 6: the owed update of delta, the model cost's applyJTJ and its dot product in ONE launch (plugins that offer it); delta moves to the other buffer
-        model_cost_done = !failed && lm_fold_step_ && plugin->lm_model_cost_one_launch();
-        if (model_cost_done) {
-            nb = plugin->lm_model_cost(ctx, v_, scal(B), scal(B + 1), 2, lmst, L, slot(T0), slot(T1), true);      // (... and savePreviousUnknowns + PCGLinearUpdate)
-            check(nb, "PCGModelCost launch");
-            if (!failed) { set_nb(T0, nb); set_nb(T1, nb); std::swap(v_.delta, v_.Adelta); }
-        } else
-        if (!failed) {      // p_k lives in p[1] for even k, p[0] for odd k
-            TimedLaunch t(ctx, "PCGUpdate");
-            check(thallo_hip_lm_owed_delta(v_.delta, v_.p[1], v_.p[0], n, scal(B), scal(B + 1), 2, lmst, L, s), "PCGUpdate (owed delta) launch");
-        }
-    }
-    for (int k = 0; !resident_lm && !one_kernel_lm && !one_kernel_lm_slab && k < L && !failed && !coll_failed; ++k) {
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        if (!skip()) {
+        if (!st.skip()) {
             if (fold_p) {                                             // PCGStep3 + PCGStep1 + PCGStep1_Finish in one launch; p ping-pongs between the two buffers
                 float* pn = p == v_.p[0] ? v_.p[1] : v_.p[0];
                 ctx.lm_ctc = v_.CtC;
                 nb = plugin->apply_jtj_pupdate(ctx, v_.z, p, pn, v_.Ap, slot(jD), k == 0, sum(k ? jN - 2 : jN), sum(jN));
                 ctx.lm_ctc = nullptr;
-                check(nb, "PCGStep1 (+ PCGStep3) launch");
+                st.check(nb, "PCGStep1 (+ PCGStep3) launch");
                 p = pn;
             } else {
                 {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
-                    check(thallo_hip_pcg_pupdate(v_.z + oe, p + oe, p + oe, nullptr, ne, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch");
+                    st.check(thallo_hip_pcg_pupdate(v_.z + st.oe, p + st.oe, p + st.oe, nullptr, st.ne, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch");
                 }
                 if (fold_ctc) {                                       // PCGStep1 + PCGStep1_Finish in one launch: (J^T J + CtC) p ; alphaD
                     ctx.lm_ctc = v_.CtC;
                     nb = plugin->apply_jtj(ctx, p, v_.Ap, slot(jD));
                     ctx.lm_ctc = nullptr;
-                    check(nb, "PCGStep1 launch");
+                    st.check(nb, "PCGStep1 launch");
                 } else {
                     nb = plugin->apply_jtj(ctx, p, v_.Ap, slot(T0));  // PCGStep1 (J^T J p)
-                    check(nb, "PCGStep1 launch");
-                    if (!skip()) {
+                    st.check(nb, "PCGStep1 launch");
+                    if (!st.skip()) {
                         TimedLaunch t(ctx, "PCGStep1_Finish");        // + CtC p ; alphaD
                         nb = thallo_hip_lm_step1_finish(v_.Ap + o, v_.CtC + o, p + o, n, slot(jD), s);
-                        check(nb, "PCGStep1_Finish launch");
+                        st.check(nb, "PCGStep1_Finish launch");
                     }
                 }
             }
-            if (!skip()) set_nb(jD, nb);
+            if (!st.skip()) set_nb(jD, nb);
         }
-        if (failed) break;
-        if (global(jD)) { coll_failed = true; break; }
+        if (st.failed) return;
+        if (st.global(jD)) { st.coll_failed = true; return; }
         int nbq = 0; bool zeta_done = false;
         const bool reset = ((k + 1) % sp.residual_reset_period) == 0;     // :1653-1657
         if (reset) {
-            if (!skip()) { TimedLaunch t(ctx, "PCGStep2"); check(thallo_hip_lm_step2_first_half(v_.delta + o, p + o, n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
-            if (global_rows(-1, v_.delta)) { coll_failed = true; break; }          // (slab: applyJTJ reads delta on the ghost rows)
-            if (!skip()) {
+            if (!st.skip()) { TimedLaunch t(ctx, "PCGStep2"); st.check(thallo_hip_lm_step2_first_half(v_.delta + o, p + o, n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
+            if (st.global_rows(-1, v_.delta)) { st.coll_failed = true; return; }          // (slab: applyJTJ reads delta on the ghost rows)
+            if (!st.skip()) {
                 TimedLaunch t(ctx, "PCGStep2");
                 ctx.lm_ctc = fold_ctc ? v_.CtC : nullptr;
                 nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0));         // computeAdelta (+ CtC delta)
                 ctx.lm_ctc = nullptr;
-                check(nb, "computeAdelta launch");
-                if (!skip() && !fold_ctc) check(thallo_hip_lm_step1_finish(v_.Adelta + o, v_.CtC + o, v_.delta + o, n, slot(T1), s), "computeAdelta (CtC) launch");
-                if (!skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(jB), slot(QS), s); check(nb, "PCGStep2 (second half) launch"); }
+                st.check(nb, "computeAdelta launch");
+                if (!st.skip() && !fold_ctc) st.check(thallo_hip_lm_step1_finish(v_.Adelta + o, v_.CtC + o, v_.delta + o, n, slot(T1), s), "computeAdelta (CtC) launch");
+                if (!st.skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(jB), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
                 nbq = nb;
             }
-        } else if (!skip()) {
+        } else if (!st.skip()) {
             TimedLaunch t(ctx, "PCGStep2");
             if (zeta_in_step2) nb = thallo_hip_pcg_step2_full_zeta(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS),
                                                                     v_.fin_tickets, k, sp.q_tolerance, lmst, s);
             else nb = thallo_hip_pcg_step2_full(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS), 1, s);
-            check(nb, "PCGStep2 launch");
+            st.check(nb, "PCGStep2 launch");
             nbq = nb; zeta_done = zeta_in_step2;
         }
-        if (failed) break;
-        if (!skip()) { set_nb(jB, nb); set_nb(QS, nbq); }
-        if (slab) { bool zd = false; if (dist_two_sums_and_rows(QS, jB, v_.z, lmst, k, &zd)) { coll_failed = true; break; } zeta_done = zeta_done || zd; }   // q and betaN over all ranks; ghost rows of z (device-side transport: + the zeta test)
-        k_done = k + 1;
-        if (!zeta_done && !skip()) {
+        if (st.failed) return;
+        if (!st.skip()) { set_nb(jB, nb); set_nb(QS, nbq); }
+        if (slab) { bool zd = false; if (dist_two_sums_and_rows(QS, jB, v_.z, lmst, k, &zd)) { st.coll_failed = true; return; } zeta_done = zeta_done || zd; }   // q and betaN over all ranks; ghost rows of z (device-side transport: + the zeta test)
+        st.k_done = k + 1;
+        if (!zeta_done && !st.skip()) {
             TimedLaunch t(ctx, "PCGZeta");
-            check(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, lmst, s), "PCGZeta launch");
+            st.check(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, lmst, s), "PCGZeta launch");
         }
     }
-    thallo_hip_lm_set_gate(nullptr); ctx.gate = nullptr;
-    if (failed || coll_failed) return 0;
-    timer_.stop(ev_lin, s);
+}
+
+// The ranks of a slab run agree on whether every rank got through the step; false: somebody did not (or the collective failed), every rank stops
+bool Plan::lm_agree_all()
+{
+    bool all = false;
+    if (dist_agree(!dist_->failed, all)) return false;
+    if (all) return true;
+    const std::string mine = dist_->failed ? last_error() : "";
+    if (dist_->failed) set_error("distributed: this rank failed (%s); every rank stops", mine.c_str()); else set_error("distributed: another rank reported a failure; every rank stops");
+    ready_ = false; dist_->stopped = true;
+    return false;
+}
+
+hipError_t Plan::copy_unknowns(bool restore)
+{   // savePreviousUnknowns (gauss_newton.t:915-920), or revertUpdate: the same copies the other way
+    const auto& imgs = plugin->unknown_images();
+    hipError_t last = hipSuccess;                                     // (every image's copy is attempted, as before; the last failure is the one reported)
+    long off = 0;
+    for (size_t k = 0; k < imgs.size(); ++k) {
+        float* X = plugin->unknown_ptr((int)k); float* saved = v_.prevX + off;
+        const hipError_t e = hipMemcpyAsync(restore ? X : saved, restore ? saved : X, imgs[k].n_floats * sizeof(float), hipMemcpyDeviceToDevice, ctx.stream);
+        if (e != hipSuccess) last = e;
+        off += imgs[k].n_floats;
+    }
+    return last;
+}
+
+int Plan::lm_iterations_done(const float* rep, int enqueued)
+{   // words 1, 2 of the LM state: the gate (nonzero: the zeta test ended the loop) and the iteration it ended at
+    unsigned frozen; int frozen_at;
+    memcpy(&frozen, &rep[1], sizeof(frozen)); memcpy(&frozen_at, &rep[2], sizeof(frozen_at));
+    return frozen ? frozen_at : enqueued;
+}
+
+// Model cost, savePreviousUnknowns, PCGLinearUpdate, the new cost, the ranks' agreement, the step's ONE blocking read-back, accept or revert
+int Plan::lm_finish(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const int T0 = st.T0, T1 = st.T1;
+    const bool slab = st.slab;
+    float* lmst = st.lmst;
+    timer_.stop(st.ev_lin, s);
     const int ev_fin = timer_.start("Nonlinear Finish", s);
     // model_cost_change = cost - 0.5|F + J delta|^2 = delta.b - 0.5 delta.(J^T J delta)   (b = -J^T F; thallo.t:3845-3865
     // expanded algebraically, which also avoids the reference's cancellation between two large sums)
-    if (global_rows(-1, v_.delta)) return 0;
-    if (!model_cost_done) {
-        if (!skip()) { nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); check(nb, "model cost: applyJTJ launch"); }
-        if (!skip()) set_nb(T0, nb);
-        if (!skip()) { nb = thallo_hip_dot(v_.delta + o, v_.b + o, n, slot(T1), s); check(nb, "model cost: dot launch"); }
-        if (!skip()) set_nb(T1, nb);
+    if (st.global_rows(-1, v_.delta)) return 0;
+    int nb = 0;
+    if (!st.model_cost_done) {
+        if (!st.skip()) { nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); st.check(nb, "model cost: applyJTJ launch"); }
+        if (!st.skip()) set_nb(T0, nb);
+        if (!st.skip()) { nb = thallo_hip_dot(v_.delta + st.o, v_.b + st.o, st.n, slot(T1), s); st.check(nb, "model cost: dot launch"); }
+        if (!st.skip()) set_nb(T1, nb);
     }
-    if (failed) return 0;
+    if (st.failed) return 0;
     // the two sums over all ranks, into the step's report.  Device-side transport: ONE exchange carries both and writes them where the report is read from (it was two
     // exchanges and two one-wave launches that copied their words there; three launches fewer, though the step's time did not move: 37.5 us per PCG iteration either way on a
     // 2048 x 256 shape_from_shading slab -- that stretch of the step is bound by the host's launch rate, not by the launches' 4 us each)
     const bool two_in_one = slab && dist_->xrows_now;
     if (two_in_one) {
         const thallo_sum_t dummy = { (const float*)dist_->send.ptr, 1 };
-        if (dist_xrows(nullptr, false, 0, skip() ? dummy : partial_sum(T0), skip() ? (const float*)dist_->send.ptr : slot(T1), nullptr, skip() ? 1 : nb_[T1], lmst + 3, lmst + 4, nullptr, 0)) return 0;
-    } else if (global(T0) || global(T1)) return 0;
-    const auto& imgs = plugin->unknown_images();
-    if (!skip()) {
+        if (dist_xrows(nullptr, false, 0, st.skip() ? dummy : partial_sum(T0), st.skip() ? (const float*)dist_->send.ptr : slot(T1), nullptr, st.skip() ? 1 : nb_[T1], lmst + 3, lmst + 4, nullptr, 0)) return 0;
+    } else if (st.global(T0) || st.global(T1)) return 0;
+    if (!st.skip()) {
         if (!two_in_one) {
             thallo_hip_finish_sum(sum(T0), lmst + 3, s);
             thallo_hip_finish_sum(sum(T1), lmst + 4, s);
         }
-        long off = 0;                                                 // savePreviousUnknowns :915-920
-        for (size_t k = 0; !model_cost_done && k < imgs.size(); ++k) {
-            HIP_OK(hipMemcpyAsync(v_.prevX + off, plugin->unknown_ptr((int)k), imgs[k].n_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-            off += imgs[k].n_floats;
+        if (!st.model_cost_done) {                                    // (the one-launch model cost has done both)
+            HIP_OK(copy_unknowns(false));
+            linear_update_tail(0, false);                             // PCGLinearUpdate: X += delta (the owned rows of a slab)
         }
-        if (!model_cost_done) linear_update_tail(0, false);           // PCGLinearUpdate: X += delta (the owned rows of a slab); the one-launch model cost has done both
     }
     if (slab && dist_exchange_unknown_rows()) return 0;
-    bool failed_before_cost_exchange = false;
-    {   // cost after the step, into the same report: ONE blocking read per GN step
-        int nbc = 0;
-        if (!skip()) { nbc = plugin->cost(ctx, slot(0)); check(nbc, "cost kernel launch"); }
-        if (failed) return 0;
-        if (!skip()) set_nb(0, nbc);
-        failed_before_cost_exchange = slab && dist_->failed;          // (then this rank's payload in the exchange below is poisoned: every rank's new cost is NaN)
-        if (global(0)) return 0;
-        if (!skip()) thallo_hip_finish_sum(sum(0), lmst + 5, s);
-    }
+    // cost after the step, into the same report: ONE blocking read per GN step
+    int nbc = 0;
+    if (!st.skip()) { nbc = plugin->cost(ctx, slot(0)); st.check(nbc, "cost kernel launch"); }
+    if (st.failed) return 0;
+    if (!st.skip()) set_nb(0, nbc);
+    const bool failed_before_cost_exchange = slab && dist_->failed;   // (then this rank's payload in the exchange below is poisoned: every rank's new cost is NaN)
+    if (st.global(0)) return 0;
+    if (!st.skip()) thallo_hip_finish_sum(sum(0), lmst + 5, s);
     // The step's outcome decides the trust region on every rank: agree on whether every rank got through it before anyone acts on its report.  On the host transport that
     // is one more collective per step.  On the device-side transport a failed rank's exchanges are POISONED (dist_xrows: NaN payloads), so the new cost -- a rank-ordered
     // sum, the same bits on every rank -- is non-finite on EVERY rank if any rank failed before the cost exchange: only then do the ranks agree through the host (every rank
     // takes the same branch); a rank that fails behind that exchange poisons the next step's.  (One blocking collective less per LM step: ~35 us of a 455-us step on a
     // 2048 x 256 shape_from_shading slab.)
-    auto agree_all = [&]() -> bool {
-        bool all = false;
-        if (dist_agree(!dist_->failed, all)) return false;
-        if (!all) {
-            const std::string mine = dist_->failed ? last_error() : "";
-            if (dist_->failed) set_error("distributed: this rank failed (%s); every rank stops", mine.c_str()); else set_error("distributed: another rank reported a failure; every rank stops");
-            ready_ = false; dist_->stopped = true;
-            return false;
-        }
-        return true;
-    };
     const bool late_agree = slab && dist_->xrows_now;
-    if (slab && !late_agree && !agree_all()) return 0;
+    if (slab && !late_agree && !lm_agree_all()) return 0;
     float rep[8] = { 0 };
     {   float* hw = host_words();
         HIP_OK(hipMemcpyAsync(hw ? hw : rep, lmst, sizeof(rep), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
         if (hw) memcpy(rep, hw, sizeof(rep));
     }
-    if (late_agree && (failed_before_cost_exchange || !std::isfinite(rep[5])) && !agree_all()) return 0;      // (a failed rank skipped its own cost launches: its rep[5] says nothing)
+    if (late_agree && (failed_before_cost_exchange || !std::isfinite(rep[5])) && !lm_agree_all()) return 0;      // (a failed rank skipped its own cost launches: its rep[5] says nothing)
     if (resident_used_) {     // (the LM step's resident launch: its waits are bounded; one that ran out voids THIS step -- nothing of its report can be trusted)
         resident_used_ = false;
         unsigned pm[5] = { 0, 0, 0, 0, 0 };
@@ -1162,8 +1219,7 @@ int Plan::step_lm(int ev_iter)
             return 0;
         }
     }
-    { int frozen_at; memcpy(&frozen_at, &rep[2], sizeof(int)); unsigned fz; memcpy(&fz, &rep[1], sizeof(fz)); if (fz) k_done = frozen_at; }
-    return lm_accept_or_revert(rep[3], rep[4], rep[5], k_done, ev_fin, ev_iter);
+    return lm_accept_or_revert(rep[3], rep[4], rep[5], lm_iterations_done(rep, st.k_done), ev_fin, st.ev_iter);
 }
 
 // The end of an LM step (gauss_newton.t:1707-1753): step quality from the model cost change delta.b - 0.5 delta.(J^T J delta) and the new cost; accept (grow the trust region,
@@ -1171,7 +1227,6 @@ int Plan::step_lm(int ev_iter)
 int Plan::lm_accept_or_revert(float dJJd, float db, float newCost, int k_done, int ev_fin, int ev_iter)
 {
     hipStream_t s = ctx.stream;
-    const auto& imgs = plugin->unknown_images();
     last_l_iters = k_done;
     const float model_cost_change = db - 0.5f * dJJd;
     const float cost_change = prev_cost_ - newCost;
@@ -1188,11 +1243,7 @@ int Plan::lm_accept_or_revert(float dJJd, float db, float newCost, int k_done, i
             prev_cost_ = newCost;
         }
     } else {                                                                      // :1733-1749
-        long off = 0;
-        for (size_t k = 0; k < imgs.size(); ++k) {                               // revertUpdate
-            HIP_OK(hipMemcpyAsync(plugin->unknown_ptr((int)k), v_.prevX + off, imgs[k].n_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-            off += imgs[k].n_floats;
-        }
+        HIP_OK(copy_unknowns(true));                                             // revertUpdate
         plugin->unknowns_written();
         radius_ = radius_ / decrease_factor_;
         decrease_factor_ = 2.0f * decrease_factor_;

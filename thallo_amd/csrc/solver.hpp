@@ -182,13 +182,61 @@ private:
     int  step_gn_expanded(int ev_iter);
     int  step_gn_one_kernel(int ev_iter);
     int  step_gn_resident(int ev_iter);
+    bool gn_begin(int& ev_lin);                         // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2, "Linear Solve" started
+    int  gn_finish(int L, int ev_lin);                  // ... its tail: "Nonlinear Finish" started (the caller's update of the unknowns follows) ...
+    int  gn_end(int ev_fin, int ev_iter);               // ... and the step counted, its events ended
     bool resident_used_ = false;    // a resident launch ran since the last cost evaluation (its error word is read there)
     float compute_cost();
     float* host_words();
     int   step_gn(int ev_iter);
+    // ---- Levenberg-Marquardt: step_lm = lm_setup, one of four PCG loops (lm_schedule), lm_finish
+    enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident };
+    // Between the LM state reset and the end of the PCG loop the plugin's launches are gated on the state's gate word (the zeta test on the device); whichever way
+    // the loop is left, the gate is off again before the next launch that has to run
+    struct GateOff {
+        LaunchCtx& c;
+        GateOff(LaunchCtx& ctx, const unsigned* gate) : c(ctx) { thallo_hip_lm_set_gate(gate); c.gate = gate; }
+        void off() { thallo_hip_lm_set_gate(nullptr); c.gate = nullptr; }
+        ~GateOff() { off(); }
+    };
+    // What every part of one LM step needs, computed once (lm_setup), and what the loop hands to lm_finish.
+    // Slots: 0 cost, QS q, B.. as in GN (alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2); T0, T1: scratch dots (the model cost's two sums).
+    struct LmStep {
+        Plan& P;
+        hipStream_t s;
+        int L, T0, T1, period;
+        static constexpr int B = 2, QS = 1;
+        bool slab;                                      // one row slab of a multi-GPU run (flat form)
+        long o, n, oe, ne;                              // the owned rows' sub-vector [o, o + n); with the ghost rows [oe, oe + ne)
+        bool pc, fold_ctc, fold_init;
+        float* lmst;                                    // 8 words: Q0, gate, iterations done, | dJJd, db, new cost
+        const unsigned* gate;
+        int ev_iter, ev_lin = -1;
+        int k_done = 0;
+        bool model_cost_done = false;                   // the two sums of the model cost are already in slots T0 / T1, the unknowns saved and updated
+        bool failed = false;                            // one GPU: a launch failed, the step ends
+        bool coll_failed = false;                       // a collective itself failed: nothing left to stay in step with
+        LmStep(Plan& plan, int ev_iter);
+        bool skip() const { return failed || (slab && P.dist_->failed); }
+        void check(int rc, const char* what);
+        int  global(int j) { return slab ? P.dist_sum_slot(j) : 0; }                              // nonzero: the collective itself failed
+        int  global_rows(int j, float* vec) { return slab ? P.dist_sum_and_rows(j, vec) : 0; }
+    };
     int   step_lm(int ev_iter);
+    bool  lm_setup(LmStep& st);
+    LmSchedule lm_schedule(const LmStep& st);
+    void  lm_loop_reference(LmStep& st);
+    void  lm_loop_one_kernel(LmStep& st);
+    void  lm_loop_one_kernel_slab(LmStep& st);
+    void  lm_loop_resident(LmStep& st);
+    int   lm_finish(LmStep& st);
+    bool  lm_agree_all();
     int   lm_accept_or_revert(float dJJd, float db, float newCost, int k_done, int ev_fin, int ev_iter);      // the end of an LM step: accept / revert, trust region (shared by step_lm and the shard form)
     int   step_lm_shard(int ev_iter);                   // solver_dist.cpp: LM on residual shards (bundle adjustment's camera shards)
+    // ... and what the two drivers share
+    void  lm_trust_region_at_start() { if (sp.nIter == 0) { radius_ = sp.trust_region_radius; decrease_factor_ = sp.radius_decrease_factor; } }   // gauss_newton.t:1185-1186 (copied at init)
+    hipError_t copy_unknowns(bool restore);             // savePreviousUnknowns (unknowns -> prevX) / revertUpdate (prevX -> unknowns)
+    static int lm_iterations_done(const float* rep, int enqueued);      // the step's report: the iteration the zeta test froze the loop at, if it did
     int   ensure_lm_vectors();
     float read_sum(int j);
     float radius_ = 1e4f, decrease_factor_ = 2.0f;

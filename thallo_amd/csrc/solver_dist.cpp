@@ -1084,7 +1084,7 @@ int Plan::step_lm_shard(int ev_iter)
     float* lmst = (float*)scratch_.ptr + 16;                                      // 8 words: Q0, gate, iterations done, | dJJd, db, -
     const unsigned* gate = reinterpret_cast<const unsigned*>(lmst) + 1;
     const int ev_setup = timer_.start("Nonlinear Setup", s);
-    if (sp.nIter == 0) { radius_ = sp.trust_region_radius; decrease_factor_ = sp.radius_decrease_factor; }
+    lm_trust_region_at_start();
     // words[i] = (sum over the ranks, in rank order, of the camera block's partials in slot js[i]) + the point block's partials pts[i]: ONE all-gather of `count` floats
     auto gsum = [&](int count, const int* js, float* const* pts, const int* nbp, float* const* outs) -> int {
         for (int i = 0; i < count; ++i) DLOCAL(thallo_hip_finish_sum(partial_sum(js[i]), send + i, s), "camera block sum");
@@ -1113,8 +1113,7 @@ int Plan::step_lm_shard(int ev_iter)
     timer_.stop(ev_setup, s);
     const int ev_lin = timer_.start("Linear Solve", s);
     float* p = v_.p[0];
-    thallo_hip_lm_set_gate(gate); ctx.gate = gate;
-    struct GateOff { LaunchCtx& c; ~GateOff() { thallo_hip_lm_set_gate(nullptr); c.gate = nullptr; } } gate_off{ ctx };
+    GateOff gate_off(ctx, gate);
     const int period = sp.residual_reset_period > 0 ? sp.residual_reset_period : (1 << 30);
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
@@ -1168,7 +1167,7 @@ int Plan::step_lm_shard(int ev_iter)
             DLOCAL(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, lmst, s), "PCGZeta launch");
         }
     }
-    thallo_hip_lm_set_gate(nullptr); ctx.gate = nullptr;
+    gate_off.off();
     timer_.stop(ev_lin, s);
     const int ev_fin = timer_.start("Nonlinear Finish", s);
     // model cost change = delta.b - 0.5 delta.(J^T J delta): both sums are LINEAR in the ranks' contributions -- the applyJTJ launch's own partials of delta.(its part of
@@ -1182,21 +1181,14 @@ int Plan::step_lm_shard(int ev_iter)
         if (gsum(2, js, ps, ns, os)) return 0;
     }
     if (!D.failed) {
-        const auto& imgs = plugin->unknown_images();
-        long o2 = 0;                                                  // savePreviousUnknowns :915-920
-        for (size_t k = 0; k < imgs.size(); ++k) {
-            DCOPY(hipMemcpyAsync(v_.prevX + o2, plugin->unknown_ptr((int)k), imgs[k].n_floats * sizeof(float), hipMemcpyDeviceToDevice, s), "savePreviousUnknowns");
-            o2 += imgs[k].n_floats;
-        }
+        DCOPY(copy_unknowns(false), "savePreviousUnknowns");
         linear_update_tail(0, false);                                 // X += delta: this rank's cameras, all points (replicated)
     }
     const float newCost = dist_cost();                                // rank-ordered sum of the ranks' costs; a failed rank makes EVERY rank stop here
     if (!ready_ || !std::isfinite(newCost)) { timer_.stop(ev_fin, s); timer_.stop(ev_iter, s); if (!finalized_) { finalized_ = true; } return 0; }
     float rep[8] = { 0 };
     if (hipMemcpyAsync(rep, lmst, sizeof(rep), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { set_error("distributed: LM report read-back failed"); return 0; }
-    int k_done = L;
-    { int frozen_at; memcpy(&frozen_at, &rep[2], sizeof(int)); unsigned fz; memcpy(&fz, &rep[1], sizeof(fz)); if (fz) k_done = frozen_at; }
-    return lm_accept_or_revert(rep[3], rep[4], newCost, k_done, ev_fin, ev_iter);
+    return lm_accept_or_revert(rep[3], rep[4], newCost, lm_iterations_done(rep, L), ev_fin, ev_iter);
 }
 
 int Plan::dist_self_check()
