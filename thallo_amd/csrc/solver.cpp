@@ -353,7 +353,7 @@ void Plan::init(void** params)
     if (!dist_) { if (!local_ok) return; }
     else {
         dist_->failed = false; dist_->stopped = false;      // a new solve
-        const bool need_grid = !dist_->flat && !dist_->range;
+        const bool need_grid = dist_->form == DistForm::Slab;
         bool all = false;
         if (dist_agree(local_ok && (!need_grid || plugin->slab_grid_ok()), all)) return;
         if (!all) {
@@ -364,7 +364,7 @@ void Plan::init(void** params)
     }
     ready_ = true;
     if (dist_ && dist_->want_p2p && !dist_->checked && dist_self_check()) { ready_ = false; return; }
-    if (dist_ && dist_->checked && dist_->p2p_on && !dist_->flat && !dist_->range && !dist_->shard) {      // (also right behind a self-check that has just passed: ADVICE r5)
+    if (dist_ && dist_->checked && dist_->p2p_on && dist_->form == DistForm::Slab) {      // (also right behind a self-check that has just passed: ADVICE r5)
         // Every Init agrees anew on what depends on the plugin's state NOW: whether every rank's slab runs the resident kernel (a rank may have switched it
         // off since -- a bounded wait that ran out, THALLO_RESIDENT at re-Init) and whether the marching kernel's cross-rank finish is deferred.  Here, never at the
         // first step: a step may be inside a captured graph.
@@ -417,8 +417,8 @@ int Plan::step(void** params)
         else { if (!finalized_) finalize(); return 0; }
     }
     const int ev_iter = timer_.start("Nonlinear Iteration", ctx.stream);
-    if (dist_ && lm_ && !dist_->shard && (!dist_->flat || dist_->range)) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); if (!finalized_) finalize(); return 0; }
-    const int rc = lm_ && dist_ && dist_->shard ? step_lm_shard(ev_iter) : lm_ ? step_lm(ev_iter) : dist_ ? step_gn_slab(ev_iter) : step_gn(ev_iter);
+    if (dist_ && lm_ && !dist_->runs_lm()) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); if (!finalized_) finalize(); return 0; }
+    const int rc = lm_ && dist_ && dist_->form == DistForm::Shard ? step_lm_shard(ev_iter) : lm_ ? step_lm(ev_iter) : dist_ ? step_gn_slab(ev_iter) : step_gn(ev_iter);
     if (rc == 1 && sp.max_solver_time_in_seconds > 0.0f && ev_total_ >= 0) {   // :1767-1779
         hipStream_t s = ctx.stream;
         hipEvent_t q = nullptr; hipEventCreate(&q); hipEventRecord(q, s); hipEventSynchronize(q);
@@ -440,7 +440,7 @@ void Plan::linear_update_tail(int L, bool batched)
     for (size_t k = 0; k < imgs.size(); ++k) {
         TimedLaunch t(ctx, "PCGLinearUpdate");
         long lo = 0, len = imgs[k].n_floats;
-        if (dist_ && !dist_->range) { const long rowlen = imgs[k].n_floats / dist_->Hl; lo = rowlen * dist_->row0; len = rowlen * (dist_->row1 - dist_->row0); }
+        if (dist_ && !dist_->full_vectors()) { const long rowlen = imgs[k].n_floats / dist_->Hl; lo = rowlen * dist_->row0; len = rowlen * (dist_->row1 - dist_->row0); }
         float* X = plugin->unknown_ptr((int)k) + lo;
         const float* dl = v_.delta + off + lo;
         if (L > 1 && batched && ((L - 1) & 1))
@@ -701,7 +701,7 @@ bool Plan::aux_stream()
 // 16384 x 8192: 20 planes of 1.6 GB).  THALLO_DELTA_PLANES=N asks for exactly N (no memory test); planes are released with the plan.
 bool Plan::ring_possible() const
 {   // one GPU, or (round 6) one rank's row slab of the one-kernel schedule: launch k writes p_k into whichever plane it is handed (the ghost rows are kept current there too)
-    return plugin->takes_any_p_plane() && (!dist_ || (!dist_->flat && !dist_->range && !dist_->shard && !dist_->part));
+    return plugin->takes_any_p_plane() && (!dist_ || dist_->form == DistForm::Slab);
 }
 void Plan::ring_prepare(int L)
 {
@@ -920,7 +920,7 @@ Plan::LmSchedule Plan::lm_schedule(const LmStep& st)
     if (!st.slab && lm_fold_p_ && st.fold_ctc && plugin->lm_one_kernel() && L >= 1 && (L <= period || plugin->lm_iter_after_reset()) && v_.p[1] != nullptr && ensure_iter_buffers() == 0)
         return LmSchedule::OneKernel;
     // ... and on a row slab (device-side transport; plugins whose pcg_iter_lm keeps the ghost rows current)
-    if (st.slab && dist_->flat && dist_->xrows_now && lm_fold_p_ && st.fold_ctc && plugin->lm_one_kernel_slab() && L >= 1 && L <= period &&
+    if (st.slab && dist_->form == DistForm::Flat && dist_->xrows_now && lm_fold_p_ && st.fold_ctc && plugin->lm_one_kernel_slab() && L >= 1 && L <= period &&
         v_.p[1] != nullptr && v_.r2 != nullptr && v_.Ap2 != nullptr && v_.s12b != nullptr) return LmSchedule::OneKernelSlab;
     return LmSchedule::Reference;
 }

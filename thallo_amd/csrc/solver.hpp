@@ -39,55 +39,84 @@ public:
     ~CoarseTimer() { cleanup(); }
 };
 
-// Row-slab multi-GPU state of a Plan (one process per GPU; SURVEY.md 8e -- the reference is single-device, util.t:769-772, so this is
-// new design).  The Plan was made for the LOCAL image {W, owned rows + ghost rows}; rows [row0,row1) are owned.  Per PCG iteration ONE
-// kernel + ONE exchange: either the caller's all-gather (RCCL) of [alphaD, N, S1, S2 | boundary rows of Ap], or -- after a self-check on
-// this very topology -- device mailboxes + peer-to-peer ghost-row stores done by the kernel itself (dist_device.hpp).  solver_dist.cpp.
+// Multi-GPU state of a Plan (one process per GPU; SURVEY.md 8e -- the reference is single-device, util.t:769-772, so this is new design).  solver_dist.cpp.
+// The form a plan runs in across ranks: chosen once, by Plan::dist_pick_form, from what the plugin can do.
+enum class DistForm {
+    Slab,       // image_warping's row slabs: the Plan was made for the LOCAL image {W, owned rows + ghost rows}; rows [row0,row1) are owned.  Per PCG iteration ONE kernel +
+                // ONE exchange: either the caller's all-gather (RCCL) of [alphaD, N, S1, S2 | boundary rows of Ap], or -- after a self-check on this very topology -- device
+                // mailboxes + peer-to-peer ghost-row stores done by the kernel itself (dist_device.hpp)
+    Flat,       // row slabs of single-image energies with apply_jtj_sums (shape_from_shading, generated stencils): vectors stay where the Plan allocated them
+    Range,      // graph domains (ARAP): every rank holds the whole problem and FULL-length vectors and owns the contiguous unit range [row0, row1) (units = vertices), equal on all ranks
+    Partition,  // ... or (ThalloX_PlanSetGhostExchange) the rank holds its owned units [0, row1) + ghost units; only the boundary units' values travel
+    Shard       // bundle adjustment's camera shards: the unknowns [sh_off, sh_off + sh_len) (the points) are replicated; their J^T F / diag / A p are partial sums over the
+                // rank's residuals and are all-reduced; sums over them are taken after that, by every rank for itself
+};
 struct DistState {
     ThalloX_Distributed cfg;
-    int W = 0, Hl = 0, row0 = 0, row1 = 0, top = 0, bot = 0, ghost = 1;
-    long N = 0, na = 0;
-    void* block = nullptr; bool block_ipc = false;      // [r | z | r' | Ap | Ap'] (one allocation peers can map)
-    unsigned char handle_block[64], handle_mail[64];
-    int mem_kind[2] = { -1, -1 };
+    DistForm form = DistForm::Slab;
+    // What the call sites ask of the form (the four booleans these replace: flat = Flat; range = Range, Partition, Shard; part = Partition; shard = Shard):
+    //                      Slab  Flat  Range  Partition  Shard
+    //   full_vectors()      -     -     x       x         x     was `range`: linear updates and the like cover the whole local vector, not the owned rows
+    //   flat_exchange()     -     x     -       x         x     was `flat || shard || part`: the device-side exchange is a launch of its own (xrows / xunits / allreduce)
+    //   runs_lm()           -     x     -       -         x     was `shard || (flat && !range)`: Levenberg-Marquardt runs across ranks
+    // `form == DistForm::Slab` was `!flat && !range` (with or without `&& !shard`, `&& !part`: both imply range)
+    bool full_vectors() const { return form == DistForm::Range || form == DistForm::Partition || form == DistForm::Shard; }
+    bool flat_exchange() const { return form == DistForm::Flat || form == DistForm::Partition || form == DistForm::Shard; }
+    bool runs_lm() const { return form == DistForm::Flat || form == DistForm::Shard; }
+    // ---- every form
     DeviceBuffer send, gath;                             // message buffers (floats), sized for the larger of the two message kinds
     long msg = 0, msg_iter = 0, msg_x = 0;
+    int Hl = 0, row0 = 0, row1 = 0;                      // row forms: the local image's rows, [row0,row1) owned; unit forms: units, [row0,row1) owned
+    // ---- Slab and Flat: the rows
+    int W = 0, top = 0, bot = 0, ghost = 1;
+    long N = 0, na = 0;
+    // ---- Slab
+    void* block = nullptr; bool block_ipc = false;      // [r | z | r' | Ap | Ap'] (one allocation peers can map)
+    unsigned char handle_block[64];
     thallo_segs_t seg_first_last, seg_top, seg_bot, seg_iter_fl, seg_iter_top, seg_iter_bot;
-    // flat form (single-image energies with apply_jtj_sums: shape_from_shading): vectors stay where the Plan allocated them, all-gather transport only
-    bool flat = false;
+    bool resident_all = false;                           // EVERY rank's slab fits the resident PCG kernel (agreed once per Init: a rank whose last segment cannot be a full one says no)
+    int mail_L = 0;
+    long ghost_off = 0;                                  // byte offset of the resident kernel's ghost area inside every rank's mailbox block (0: none)
+    int defer_state = -1;                                // the deferred cross-rank finish: -1 not agreed on yet, 0 no, 1 every rank runs it
+    DeviceBuffer gs;                                     // two tagged granules: the global words a launch's designated wave publishes for its other waves (deferred cross-rank finish)
+    thallo_dist_t d_iter[2];
+    // ---- Flat
     long rowlen = 0;                                     // floats per image row
     thallo_segs_t seg_rows_fl, seg_rows_top, seg_rows_bot;   // first / last `ghost` owned rows; the ghost rows above / below
     thallo_segs_t seg_rows_first, seg_rows_last;             // ... the first and the last owned rows separately (device-side exchange: one goes up, one goes down)
-    thallo_xrows_t xr;                                       // device-side exchange of the flat form (thallo_hip_dist_xrows): inbox geometry, neighbours
-    bool xrows_now = false;                                  // the transport dist_sum_slot / dist_sum_and_rows / dist_gn_flat use right now (= p2p_on outside the self-check)
-    // range form (graph domains: ARAP): every rank holds the whole problem and FULL-length vectors and owns the contiguous unit range [row0, row1)
-    // (units = vertices); equal ranges on all ranks.  pieces = rank 0's owned slice of every plane of the flat vector (rank r's: + r * len)
-    bool range = false;
+    // ---- Range and Partition.  pieces = rank 0's owned slice of every plane of the flat vector (rank r's: + r * len)
     thallo_segs_t pieces_first, pieces_mine;
-    // ... or, partition form (ThalloX_PlanSetGhostExchange): the rank holds its owned units [0, row1) + ghost units; only the boundary units' values travel
-    bool part = false;
-    DeviceBuffer g_boundary, g_ghost, g_src1, g_src7, g_srcx;   // (g_srcx: the ghosts' sources inside this rank's device-side inbox)
-    thallo_units_t u_recvx; long unit_slot = 0;              // device-side exchange of the partition form (thallo_hip_dist_xunits)       // device copies of the index lists; element offsets of the ghosts' sources for the two message kinds
-    thallo_units_t u_send, u_recv1, u_recv7;
     long piece_floats = 0;                               // floats a rank owns in a flat vector
-    // shard form (bundle adjustment: camera shards): the unknowns [sh_off, sh_off + sh_len) (the points) are replicated; their J^T F / diag / A p are
-    // partial sums over the rank's residuals and are all-reduced; sums over them are taken after that, by every rank for itself
-    bool shard = false;
+    // ---- Partition
+    DeviceBuffer g_boundary, g_ghost, g_src1, g_src7, g_srcx;   // device copies of the index lists; element offsets of the ghosts' sources for the two message kinds
+                                                                // (g_srcx: the ghosts' sources inside this rank's device-side inbox)
+    thallo_units_t u_send, u_recv1, u_recv7;
+    thallo_units_t u_recvx; long unit_slot = 0;          // device-side exchange of the partition form (thallo_hip_dist_xunits)
+    // ---- Shard
     long sh_off = 0, sh_len = 0;
     DeviceBuffer sh_aD, sh_s3;                           // the shared block's partials of an iteration
     DeviceBuffer sh_lm;                                  // ... of the second sum of an LM exchange (q next to betaN, delta.b next to delta.J^T J delta)
     thallo_xreduce_t xa;                                 // device-side all-reduce of the shared block (thallo_hip_dist_allreduce): inbox geometry
-    // device-side exchange
+    // ---- device-side exchange, every form that has one
     bool want_p2p = false, mapped = false, p2p_on = false, checked = false;
-    bool resident_all = false;                           // EVERY rank's slab fits the resident PCG kernel (agreed once per Init: a rank whose last segment cannot be a full one says no)
-    void* mail = nullptr; int mail_L = 0;
-    long ghost_off = 0;                                  // byte offset of the resident kernel's ghost area inside every rank's mailbox block (0: none)
+    thallo_xrows_t xr;                                   // Flat, Partition, Shard: inbox geometry, neighbours (thallo_hip_dist_xrows / xunits / xscalars_shard)
+    bool xrows_now = false;                              // Flat, Partition: the transport dist_sum_slot / dist_sum_and_rows / dist_gn_flat / dist_ghosts use right now (= p2p_on outside the self-check)
+    void* mail = nullptr;
+    unsigned char handle_mail[64];
+    int mem_kind[2] = { -1, -1 };                        // of the block, of the mailbox: 1 fine-grained
     DeviceBuffer ctl;
-    int defer_state = -1;                                 // the deferred cross-rank finish: -1 not agreed on yet, 0 no, 1 every rank runs it
-    DeviceBuffer gs;                                      // two tagged granules: the global words a launch's designated wave publishes for its other waves (deferred cross-rank finish)
-    thallo_dist_t d, d_iter[2];
+    thallo_dist_t d;
     std::vector<void*> opened;
-    std::string info;                                    // JSON: transport, memory kind, self-check outcome
+    // ---- what distributed_info() says: facts here, the JSON rendered from them (Plan::dist_render_info) after set-up, after the self-check and after a switch-off
+    std::string form_text;                               // "form" (the Slab form has none)
+    struct SelfCheck {                                   // the outcome of dist_self_check, if it ran
+        bool ran = false, pass = false, all = false, resident_loop = false;
+        int count = 0, timeout = 0;                      // exchanges (Slab: PCG iterations) run; 0, or which bounded wait ran out
+        double rel = 0.0;                                // Slab: largest relative difference of the alpha / beta scalars between the two transports
+        unsigned pm[5] = { 0, 0, 0, 0, 0 };
+    } check;
+    bool switched_off = false;                           // dist_control(1, 0) took a passing device-side exchange out of use
+    std::string info;
     // A rank-local failure (a launch, a copy, an allocation at Step time) must not end this rank's part of the collective sequence -- the other
     // ranks would wait in the matching all-gather forever.  From the first failure on the rank skips its own launches, keeps issuing every
     // collective of the sequence with a poisoned payload (NaN header: every rank's alpha / beta / cost turn NaN), and the error becomes
@@ -96,6 +125,7 @@ struct DistState {
     bool stopped = false;                                // the failure was agreed on: every rank's plan refuses further steps, its cost reads NaN
     int inject = 0;                                      // tests (ThalloX_DistributedControl what = 2): the n-th rank-local launch / copy from now on reports a failure
 };
+struct DistPeerInfo;        // what a rank publishes about itself when the device-side exchange is set up (solver_dist.cpp)
 
 class Plan {
 public:
@@ -245,30 +275,52 @@ private:
     // solver_dist.cpp
     DistState* dist_ = nullptr;
     RcclComm* rccl_ = nullptr;
-    int  set_distributed_impl(const ThalloX_Distributed& cfg);
     struct GhostSpec { bool given = false; std::vector<int> boundary, ghost, src_rank, src_pos; } ghost_spec_;
-    int  dist_ghosts(float* vec, int sum_slot);
+    // set-up: set_distributed_impl = dist_pick_form, dist_world_ok, one dist_setup_* (the shared steps below, each in the form's own place), dist_render_info
+    int  set_distributed_impl(const ThalloX_Distributed& cfg);
+    int  dist_pick_form(DistForm& form);
+    int  dist_world_ok(const ThalloX_Distributed& cfg, bool needs_allreduce);
+    int  dist_setup_shard(const ThalloX_Distributed& cfg), dist_setup_range(const ThalloX_Distributed& cfg, bool part), dist_setup_flat(const ThalloX_Distributed& cfg), dist_setup_slab(const ThalloX_Distributed& cfg);
+    DistState* dist_new_state(const ThalloX_Distributed& cfg, DistForm form);
+    DistState* dist_new_row_state(const ThalloX_Distributed& cfg, DistForm form);      // Slab and Flat: the rows checked and handed to the plugin first
+    int  dist_alloc_messages(size_t words);             // rank-local: there is nothing to agree through without them
+    int  dist_agree_or_fail(bool mine, const char* mine_no, const char* others_no);     // ONE collective: 0, or every rank returns -1 (the rank that said no with mine_no)
+    bool dist_p2p_requested() const;                    // cfg.device_exchange, unless THALLO_DIST_P2P=0
+    bool dist_alloc_ctl();
+    int  dist_agree_p2p(bool mine);                     // ONE collective: want_p2p = every rank wants (and can have) the device-side exchange
+    bool dist_partition_lists_ok(const ThalloX_Distributed& cfg, long U);
+    void dist_partition_upload(const int* counts, const thallo_units_t& planes, long per_unit, bool& lists_ok, bool& mem_ok);
+    void dist_render_info();
+    // device-side exchange: the mailboxes (ONE all-gather of one DistPeerInfo, then ONE agreement); the Slab form adds its neighbours' blocks in between
+    int  dist_exchange_mail(long bytes, bool same_bytes, DistPeerInfo& mine, DistPeerInfo* infos, bool& ok);
+    int  dist_agree_mapped(bool ok);
+    int  dist_map_peers();                              // Slab: mailbox + the resident kernel's ghost area; the neighbours' blocks
+    int  dist_map_mail(long bytes);                     // Flat, Partition, Shard: only the mailbox is shared between ranks
+    // its self-check at the first Init: dist_self_check = one of four checks, each inside the frame dist_check_begin / _read_error / _finish
+    int  dist_self_check(), dist_check_units(), dist_check_allreduce(), dist_check_rows(), dist_check_slab();
+    void dist_check_begin(), dist_check_read_error();
+    int  dist_check_finish(bool pass, float* scratch, size_t scratch_floats, bool xrows);
+    template <class Fill, class Exchange, class Verify> int dist_check_pattern(float* vec, size_t n, bool with_sum, bool xrows, Fill fill, Exchange exchange, Verify verify);
+    // the exchanges
     int  dist_allgather(const void* send, void* recv, long bytes);
     int  dist_agree(bool flag, bool& all);
     void dist_fail(const char* fmt, ...);               // first rank-local failure: report it, switch this rank to "collectives only" (DistState::failed)
     bool dist_skip() const { return dist_ && dist_->failed; }
-    int  dist_map_peers();
-    int  dist_map_peers_flat();
-    int  dist_map_mail(long bytes);                     // the mailbox allocation of the flat / shard forms: allocate, exchange handles, map every peer's, agree
     int  dist_xrows_lm(float* vec, int jN, int jD, int jB, int nb, float* lm_state, int k);      // the ONE exchange of a slab's one-launch LM iteration
     int  dist_two_sums_and_rows(int j1, int j2, float* vec, float* zeta_state = nullptr, int zeta_k = 0, bool* zeta_done = nullptr);
     int  dist_xrows(float* vec, bool rows, int mode, thallo_sum_t s, const float* aD_part, const double* s3, int nb, float* out0, float* out1, float* zeta_state = nullptr, int zeta_k = 0);
-    int  dist_self_check();
-    int  dist_gn(int L, bool p2p);                      // PCGInit + L iterations + linear update + ghost refresh, no bookkeeping
-    int  step_gn_slab(int ev_iter);
-    int  dist_gn_flat(int L);
-    int  dist_gn_range(int L);
-    int  dist_gn_shard(int L);                          // shard form: applyJTJ on the rank's residuals, all-reduce of the shared block of A p, one tiny all-gather
-    int  dist_allreduce(float* buf, long count);                          // range form: full-length pcg_update + applyJTJ over the owned units + ONE exchange per PCG iteration
-    int  dist_replicate(float* vec, int sum_slot);      // every rank's owned pieces of `vec` to every rank (and, sum_slot >= 0, that slot's global sum)                           // flat form: pcg_update + apply_jtj_sums + ONE exchange per PCG iteration
     int  dist_sum_slot(int j);                          // slot j (local partials) -> scal(j) = rank-ordered global sum
     int  dist_sum_and_rows(int j, float* vec);          // ... and the ghost rows of a flat vector from the neighbours' boundary rows (j < 0: rows only)
     int  dist_exchange_unknown_rows();
+    int  dist_replicate(float* vec, int sum_slot);      // Range: every rank's owned pieces of `vec` to every rank (and, sum_slot >= 0, that slot's global sum)
+    int  dist_ghosts(float* vec, int sum_slot);         // Partition: `vec` at my boundary units to the ranks that hold them as ghosts (and the sum)
+    int  dist_allreduce(float* buf, long count);        // Shard: the shared block's partial sums added over the ranks, in place
+    // the Gauss-Newton step, per form
+    int  step_gn_slab(int ev_iter);
+    int  dist_gn(int L, bool p2p);                      // Slab: PCGInit + L iterations + linear update + ghost refresh, no bookkeeping
+    int  dist_gn_flat(int L);                           // Flat: pcg_update + apply_jtj_sums + ONE exchange per PCG iteration
+    int  dist_gn_range(int L);                          // Range, Partition: full-length pcg_update + applyJTJ over the owned units + ONE exchange per PCG iteration
+    int  dist_gn_shard(int L);                          // Shard: applyJTJ on the rank's residuals, all-reduce of the shared block of A p, one tiny all-gather
     float dist_cost();
     void dist_release();
 };

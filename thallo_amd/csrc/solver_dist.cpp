@@ -24,12 +24,12 @@ thallo_segs_t segs(const std::vector<std::pair<long, long>>& pieces)
     s.n = (int)pieces.size();
     return s;
 }
-struct PeerInfo {              // what a rank publishes about itself when the device-side exchange is set up
+}  // namespace
+struct DistPeerInfo {          // what a rank publishes about itself when the device-side exchange is set up
     unsigned char block[64], mail[64];
     int row0, row1, Hl, ok;
     long na;
 };
-}  // namespace
 
 // ---- rank-local failures (DistState::failed).  Every function below keeps ONE rule: collectives are issued unconditionally and in the same
 // order on every rank; everything rank-local sits behind `if (!D.failed)`.  What stays rank-local (cannot be agreed on): a failing collective
@@ -130,152 +130,46 @@ int Plan::set_ghost_exchange(int n_boundary, const int* boundary_units, int n_gh
     return 0;
 }
 
+// ---- set-up.  THE INVARIANT every form keeps, from ThalloX_PlanSetDistributed through the first Thallo_ProblemInit: every rank issues the same collectives, of the
+// same byte sizes, in the same order, and on success and on every AGREED failure no rank returns between two of them.  What a rank finds wrong with itself after the first
+// collective of its form is its "no" in the next agreement (dist_agree_or_fail: every rank returns there, in step), never a return of its own.  What may return alone:
+// the refusals in front of the first collective (properties of the plan and of cfg that every caller gets wrong alike, or that leave the other ranks in a collective the
+// caller's own time-out ends); a collective that itself fails; dist_alloc_messages (nothing to agree through without the buffers -- the partition form allocates them a
+// second time BEHIND its first two collectives, and that one stays rank-local too).  Collectives per form (agree = 16 bytes per rank, mail = one DistPeerInfo + agree,
+// only if every rank still wants the device-side exchange):
+//   Shard       agree(memory)                                                agree(device exchange + control words)   [mail]
+//   Range       agree(memory)
+//   Partition   all-gather(4: boundary count, -1 = bad lists)  agree(lists + their upload)  agree(memory)  agree(device exchange + control words)   [mail]
+//   Flat        agree(memory + control words + slab kernels)                 agree(device exchange)                   [mail]
+//   Slab        agree(memory + control words; the IPC block comes first)     agree(device exchange)                   [mail: + the neighbours' blocks]
+// Where the control words count differs between the forms as listed, and is kept: it decides which collective carries which answer.
 int Plan::set_distributed_impl(const ThalloX_Distributed& cfg)
 {
+    DistForm form;
+    if (dist_pick_form(form) || dist_world_ok(cfg, form == DistForm::Shard)) return -1;
+    int rc = -1;
+    switch (form) {
+    case DistForm::Shard:     rc = dist_setup_shard(cfg); break;
+    case DistForm::Range:     rc = dist_setup_range(cfg, false); break;
+    case DistForm::Partition: rc = dist_setup_range(cfg, true); break;
+    case DistForm::Flat:      rc = dist_setup_flat(cfg); break;
+    case DistForm::Slab:      rc = dist_setup_slab(cfg); break;
+    }
+    if (rc == 0) dist_render_info();
+    return rc;
+}
+
+int Plan::dist_pick_form(DistForm& form)
+{   // from what the plugin can do (and whether ghost lists were given): the same answer, or the same refusal, on every rank
     if (plugin->shared_block_floats() > 0 && !plugin->supports_row_slabs() && plugin->range_units() == 0) {      // bundle adjustment: camera shards
         if (!plugin->apply_returns_sums()) { set_error("distributed: %s has no shard form", plugin->name()); return -1; }
-        if (cfg.world < 1 || cfg.world > THALLO_DIST_MAX_WORLD || cfg.rank < 0 || cfg.rank >= cfg.world) { set_error("distributed: rank %d of %d (at most %d ranks)", cfg.rank, cfg.world, THALLO_DIST_MAX_WORLD); return -1; }
-        if (cfg.world > 1 && (!cfg.allgather || !cfg.allreduce) && !(rccl_ && rccl_->world == cfg.world && rccl_->rank == cfg.rank)) { set_error("distributed: the shard form needs an all-gather and an all-reduce callback (or ThalloX_PlanUseRccl)"); return -1; }
-        const long off = plugin->shared_block_offset(), len = plugin->shared_block_floats();
-        if ((off & 3) || (len & 3) || off + len != v_.n) { set_error("distributed: shared block [%ld, %ld) of %ld unknowns (offset and length must be multiples of 4: pad the cameras to a multiple of 4)", off, off + len, v_.n); return -1; }
-        hipDeviceSynchronize();
-        DistState* Dp = new DistState(); DistState& D = *Dp; dist_ = Dp;
-        D.cfg = cfg; D.shard = true; D.range = true;            // (range: linear updates and the like cover the whole local vector)
-        plugin->forbid_renumbering();                            // (the replicated point block keeps the caller's order on every rank)
-        D.sh_off = off; D.sh_len = len;
-        if (D.send.alloc(64 * sizeof(float)) || D.gath.alloc(64 * sizeof(float) * cfg.world)) { set_error("distributed: out of device memory for the message buffers"); return -1; }   // (rank-local: nothing to agree through yet)
-        bool mem = !(ensure_sums_buffer() || D.sh_aD.alloc(THALLO_HIP_MAX_PARTIALS * sizeof(float)) || D.sh_s3.alloc((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)));
-        if (mem && !v_.diag) { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); if (b->alloc((size_t)v_.n_alloc * sizeof(float))) mem = false; else v_.diag = (float*)b->ptr; }      // raw diag(J^T J): all-reduced before it is inverted
-        bool all = false;
-        if (dist_agree(mem, all)) return -1;                             // every rank has its buffers, or every rank returns the error
-        if (!all) { set_error(mem ? "distributed: another rank ran out of device memory" : "distributed: out of device memory"); return -1; }
-        // ---- device-side all-reduce of the shared block (thallo_hip_dist_allreduce): scalar ring + two inboxes in one IPC allocation per rank
-        D.want_p2p = cfg.device_exchange != 0;
-        {   const char* e = env_switch("THALLO_DIST_P2P"); if (e && e[0] == '0') D.want_p2p = false; }
-        bool ctl_ok = !(D.ctl.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(D.ctl.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess);
-        all = false;
-        if (dist_agree(D.want_p2p && ctl_ok, all)) return -1;
-        D.want_p2p = all;
-        if (D.want_p2p) {
-            memset(&D.xa, 0, sizeof(D.xa));
-            D.xa.ring0 = 0; D.xa.chunk = ((len + cfg.world - 1) / cfg.world + 3) / 4 * 4;
-            D.xa.inbox_off = (8L * 72 * cfg.world + 255) / 256 * 256;       // behind 8 (all-reduce) + 64 (scalars) granule slots
-            memset(&D.xr, 0, sizeof(D.xr)); D.xr.ring0 = 8; D.xr.inbox_off = D.xa.inbox_off; D.xr.above = D.xr.below = -1;
-            if (dist_map_mail(D.xa.inbox_off + 4L * cfg.world * D.xa.chunk * (long)sizeof(float))) return -1;
-        }
-        char buf[256];
-        snprintf(buf, sizeof(buf), "{\"exchange\": \"allreduce + allgather\", \"form\": \"residual shards, shared block of %ld unknowns\", \"rank\": %d, \"world\": %d, \"device_exchange_requested\": %s}",
-                 len, cfg.rank, cfg.world, cfg.device_exchange ? "true" : "false");
-        D.info = buf;
+        form = DistForm::Shard;
         return 0;
     }
     if (plugin->range_units() > 0) {                           // graph domains: vertex ranges, whole problem and full-length vectors on every rank
-        const long U = plugin->range_units(), u0 = cfg.row0, u1 = cfg.row1;
         if (lm_) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); return -1; }
         if (!plugin->apply_returns_sums()) { set_error("distributed: %s has no range form", plugin->name()); return -1; }
-        if (cfg.world < 1 || cfg.world > THALLO_DIST_MAX_WORLD || cfg.rank < 0 || cfg.rank >= cfg.world) { set_error("distributed: rank %d of %d (at most %d ranks)", cfg.rank, cfg.world, THALLO_DIST_MAX_WORLD); return -1; }
-        if (cfg.world > 1 && !cfg.allgather && !(rccl_ && rccl_->world == cfg.world && rccl_->rank == cfg.rank)) { set_error("distributed: world > 1 needs an all-gather callback (or ThalloX_PlanUseRccl)"); return -1; }
-        const bool part = ghost_spec_.given;
-        bool part_bad = false;             // partition form: this rank's lists are inconsistent -- said in the first collective below, where every rank returns the error
-        if (!part && (U % cfg.world || u1 - u0 != U / cfg.world || u0 != (U / cfg.world) * cfg.rank)) {
-            set_error("distributed: rank %d of %d must own units [%ld,%ld) of %ld (equal contiguous ranges), got [%ld,%ld)", cfg.rank, cfg.world, (U / cfg.world) * cfg.rank, (U / cfg.world) * (cfg.rank + 1), U, u0, u1);
-            return -1;
-        }
-        if (part) {       // partition form: owned units first, every other local unit is a ghost with a source
-            const GhostSpec& G = ghost_spec_;
-            bool ok = u0 == 0 && u1 >= 1 && u1 <= U && (long)G.ghost.size() == U - u1;
-            std::vector<char> seen((size_t)U, 0);
-            for (int b : G.boundary) ok = ok && b >= 0 && b < u1;
-            for (size_t g = 0; ok && g < G.ghost.size(); ++g) {
-                ok = G.ghost[g] >= u1 && G.ghost[g] < U && !seen[(size_t)G.ghost[g]] && G.src_rank[g] >= 0 && G.src_rank[g] < cfg.world && G.src_rank[g] != cfg.rank && G.src_pos[g] >= 0;
-                if (ok) seen[(size_t)G.ghost[g]] = 1;
-            }
-            std::vector<char> seen_b((size_t)std::max(1L, u1), 0);
-            for (int b : G.boundary) { if (ok && seen_b[(size_t)b]) ok = false; if (ok) seen_b[(size_t)b] = 1; }        // (a boundary unit listed twice would be sent twice)
-            //  NOT an early return: the other ranks are about to enter the first collective of this set-up -- a bad list is this rank's "no" in it
-            if (!ok) { set_error("distributed: the ghost exchange lists do not describe local units [0,%ld) owned + [%ld,%ld) ghosts (or list a boundary unit twice)", u1, u1, U); part_bad = true; }
-        }
-        if (plugin->set_owned_range(u0, u1)) return -1;
-        hipDeviceSynchronize();
-        DistState* Dp = new DistState(); DistState& D = *Dp; dist_ = Dp;
-        D.cfg = cfg; D.range = true; D.part = part; D.row0 = (int)u0; D.row1 = (int)u1; D.Hl = (int)U;
-        std::vector<std::pair<long, long>> first, mine;
-        long off = 0;
-        thallo_units_t un; memset(&un, 0, sizeof(un));
-        long per_unit = 0;
-        for (auto& im : plugin->unknown_images()) {
-            const long per = im.n_floats / U, len = per * (u1 - u0);
-            if (im.n_floats % U || (!part && (len & 3))) {
-                set_error("distributed: an unknown image of %ld floats over %ld units, an owned slice of %ld floats (must divide / be a multiple of 4)", im.n_floats, U, len);
-                if (!part) return -1;
-                part_bad = true;
-            }
-            first.push_back({ off, len }); mine.push_back({ off + per * u0, len });
-            if (un.nplanes < 8) { un.base[un.nplanes] = off; un.len[un.nplanes] = (int)per; ++un.nplanes; }
-            per_unit += per;
-            D.piece_floats += len; off += im.n_floats;
-        }
-        if (first.size() > 8) { set_error("distributed: more than 8 unknown images"); return -1; }
-        D.pieces_first = segs(first); D.pieces_mine = segs(mine);
-        D.msg = 1 + D.piece_floats; D.msg_iter = 7 + D.piece_floats;
-        if (part) {
-            // every rank's boundary count (messages are padded to the largest; a ghost's source position must exist on its source rank)
-            const GhostSpec& G = ghost_spec_;
-            int counts[THALLO_DIST_MAX_WORLD]; const int mine_n = part_bad ? -1 : (int)G.boundary.size();
-            if (D.send.alloc(64 * sizeof(float)) || D.gath.alloc(64 * sizeof(float) * cfg.world)) { set_error("distributed: out of device memory for the message buffers"); return -1; }
-            if (host_allgather(*this, D, &Plan::dist_allgather, &mine_n, counts, sizeof(int))) return -1;
-            long maxb = 1; bool ok = true;
-            for (int r = 0; r < cfg.world; ++r) {
-                if (counts[r] < 0) {        // some rank's lists are inconsistent: EVERY rank returns here, in step
-                    if (!part_bad) set_error("distributed: rank %d's ghost exchange lists are inconsistent", r);
-                    return -1;
-                }
-                maxb = std::max(maxb, (long)counts[r]);
-            }
-            for (size_t g = 0; g < G.ghost.size(); ++g) ok = ok && G.src_pos[g] < counts[G.src_rank[g]];
-            D.msg = 1 + per_unit * maxb; D.msg_iter = 7 + per_unit * maxb;
-            std::vector<long> s1(G.ghost.size()), s7(G.ghost.size());
-            for (size_t g = 0; g < G.ghost.size(); ++g) { s1[g] = (long)G.src_rank[g] * D.msg + 1 + (long)G.src_pos[g] * per_unit; s7[g] = (long)G.src_rank[g] * D.msg_iter + 7 + (long)G.src_pos[g] * per_unit; }
-            auto up = [&](DeviceBuffer& b, const void* src, size_t bytes) { return b.alloc(bytes + 16) || (bytes && hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess); };
-            bool mem = !(up(D.g_boundary, G.boundary.data(), G.boundary.size() * sizeof(int)) || up(D.g_ghost, G.ghost.data(), G.ghost.size() * sizeof(int)) ||
-                         up(D.g_src1, s1.data(), s1.size() * sizeof(long)) || up(D.g_src7, s7.data(), s7.size() * sizeof(long)));
-            D.u_send = un; D.u_send.units = (const int*)D.g_boundary.ptr; D.u_send.n = (int)G.boundary.size();
-            D.u_recv1 = un; D.u_recv1.units = (const int*)D.g_ghost.ptr; D.u_recv1.src = (const long*)D.g_src1.ptr; D.u_recv1.n = (int)G.ghost.size();
-            D.u_recv7 = D.u_recv1; D.u_recv7.src = (const long*)D.g_src7.ptr;
-            D.unit_slot = per_unit * maxb;
-            std::vector<long> sx(G.ghost.size());
-            for (size_t g = 0; g < G.ghost.size(); ++g) sx[g] = (long)G.src_rank[g] * D.unit_slot + (long)G.src_pos[g] * per_unit;
-            mem = mem && !up(D.g_srcx, sx.data(), sx.size() * sizeof(long));
-            D.u_recvx = D.u_recv1; D.u_recvx.src = (const long*)D.g_srcx.ptr;
-            bool all = false;
-            if (dist_agree(ok && mem, all)) return -1;
-            if (!all) { set_error(!ok ? "distributed: a ghost's source position lies outside its source rank's boundary list" : mem ? "distributed: another rank's ghost exchange lists are inconsistent (or it ran out of device memory)" : "distributed: out of device memory"); return -1; }
-            D.send.release(); D.gath.release();
-        }
-        const size_t words = (size_t)std::max(D.msg_iter, 64L);
-        if (D.send.alloc(words * sizeof(float)) || D.gath.alloc(words * sizeof(float) * cfg.world)) { set_error("distributed: out of device memory for the message buffers"); return -1; }
-        const bool mem = ensure_sums_buffer() == 0;
-        bool all = false;
-        if (dist_agree(mem, all)) return -1;
-        if (!all) { set_error(mem ? "distributed: another rank ran out of device memory" : "distributed: out of device memory"); return -1; }
-        char buf[256];
-        if (part) {       // device-side exchange of the boundary units (thallo_hip_dist_xunits): scalar ring + one inbox area per (parity, source rank)
-            D.want_p2p = cfg.device_exchange != 0 && D.unit_slot <= 32768;
-            {   const char* e = env_switch("THALLO_DIST_P2P"); if (e && e[0] == '0') D.want_p2p = false; }
-            const bool ctl_ok = !(D.ctl.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(D.ctl.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess);
-            bool allp = false;
-            if (dist_agree(D.want_p2p && ctl_ok, allp)) return -1;
-            D.want_p2p = allp;
-            if (D.want_p2p) {
-                memset(&D.xr, 0, sizeof(D.xr)); D.xr.ring0 = 0; D.xr.above = D.xr.below = -1;
-                D.xr.inbox_off = (8L * 64 * cfg.world + 255) / 256 * 256;
-                if (dist_map_mail(D.xr.inbox_off + 2L * cfg.world * D.unit_slot * (long)sizeof(float))) return -1;
-            }
-        }
-        if (part) snprintf(buf, sizeof(buf), "{\"exchange\": \"allgather\", \"form\": \"unit partition: %ld owned + %ld ghost units, %d boundary units sent\", \"rank\": %d, \"world\": %d, \"device_exchange_requested\": %s}",
-                           u1, U - u1, D.u_send.n, cfg.rank, cfg.world, cfg.device_exchange ? "true" : "false");
-        else snprintf(buf, sizeof(buf), "{\"exchange\": \"allgather\", \"form\": \"unit ranges, full-length vectors\", \"rank\": %d, \"world\": %d}", cfg.rank, cfg.world);
-        D.info = buf;
+        form = ghost_spec_.given ? DistForm::Partition : DistForm::Range;
         return 0;
     }
     const bool flat = plugin->dist_flat_form();         // single-image energies in the single-reduction form (shape_from_shading); else image_warping's one-kernel form
@@ -285,79 +179,256 @@ int Plan::set_distributed_impl(const ThalloX_Distributed& cfg)
         return -1;
     }
     if (lm_ && !flat) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); return -1; }
+    form = flat ? DistForm::Flat : DistForm::Slab;
+    return 0;
+}
+
+// ---- the steps the set-ups share (each form calls them in its own place)
+int Plan::dist_world_ok(const ThalloX_Distributed& cfg, bool needs_allreduce)
+{
     if (cfg.world < 1 || cfg.world > THALLO_DIST_MAX_WORLD || cfg.rank < 0 || cfg.rank >= cfg.world) { set_error("distributed: rank %d of %d (at most %d ranks)", cfg.rank, cfg.world, THALLO_DIST_MAX_WORLD); return -1; }
-    if (cfg.world > 1 && !cfg.allgather && !(rccl_ && rccl_->world == cfg.world && rccl_->rank == cfg.rank)) { set_error("distributed: world > 1 needs an all-gather callback (or ThalloX_PlanUseRccl)"); return -1; }
+    if (cfg.world <= 1 || (cfg.allgather && (cfg.allreduce || !needs_allreduce)) || (rccl_ && rccl_->world == cfg.world && rccl_->rank == cfg.rank)) return 0;
+    set_error(needs_allreduce ? "distributed: the shard form needs an all-gather and an all-reduce callback (or ThalloX_PlanUseRccl)" : "distributed: world > 1 needs an all-gather callback (or ThalloX_PlanUseRccl)");
+    return -1;
+}
+DistState* Plan::dist_new_state(const ThalloX_Distributed& cfg, DistForm form)
+{   // from here on a failing set-up leaves the plan unusable (set_distributed)
+    hipDeviceSynchronize();
+    dist_ = new DistState(); dist_->cfg = cfg; dist_->form = form;
+    return dist_;
+}
+int Plan::dist_alloc_messages(size_t words)
+{
+    if (!dist_->send.alloc(words * sizeof(float)) && !dist_->gath.alloc(words * sizeof(float) * dist_->cfg.world)) return 0;
+    set_error("distributed: out of device memory for the message buffers");
+    return -1;
+}
+int Plan::dist_agree_or_fail(bool mine, const char* mine_no, const char* others_no)
+{
+    bool all = false;
+    if (dist_agree(mine, all)) return -1;
+    if (!all) set_error("%s", mine ? others_no : mine_no);
+    return all ? 0 : -1;
+}
+bool Plan::dist_p2p_requested() const { const char* e = env_switch("THALLO_DIST_P2P"); return dist_->cfg.device_exchange != 0 && !(e && e[0] == '0'); }
+bool Plan::dist_alloc_ctl() { DeviceBuffer& c = dist_->ctl; return !(c.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(c.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess); }
+int Plan::dist_agree_p2p(bool mine)
+{   // decided by every rank alike (Flat, Slab: also the first use of the caller's all-gather by itself -- it fails here, not mid-solve)
+    return dist_agree(mine, dist_->want_p2p);
+}
+static const char* const kNoMemory = "distributed: out of device memory";
+static const char* const kOtherNoMemory = "distributed: another rank ran out of device memory";
+
+// ---- the set-ups, one per form
+int Plan::dist_setup_shard(const ThalloX_Distributed& cfg)
+{
+    const long off = plugin->shared_block_offset(), len = plugin->shared_block_floats();
+    if ((off & 3) || (len & 3) || off + len != v_.n) { set_error("distributed: shared block [%ld, %ld) of %ld unknowns (offset and length must be multiples of 4: pad the cameras to a multiple of 4)", off, off + len, v_.n); return -1; }
+    DistState& D = *dist_new_state(cfg, DistForm::Shard);
+    plugin->forbid_renumbering();                            // (the replicated point block keeps the caller's order on every rank)
+    D.sh_off = off; D.sh_len = len;
+    if (dist_alloc_messages(64)) return -1;
+    bool mem = !(ensure_sums_buffer() || D.sh_aD.alloc(THALLO_HIP_MAX_PARTIALS * sizeof(float)) || D.sh_s3.alloc((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)));
+    if (mem && !v_.diag) { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); if (b->alloc((size_t)v_.n_alloc * sizeof(float))) mem = false; else v_.diag = (float*)b->ptr; }      // raw diag(J^T J): all-reduced before it is inverted
+    if (dist_agree_or_fail(mem, kNoMemory, kOtherNoMemory)) return -1;   // every rank has its buffers, or every rank returns the error
+    // ---- device-side all-reduce of the shared block (thallo_hip_dist_allreduce): scalar ring + two inboxes in one IPC allocation per rank
+    const bool want = dist_p2p_requested(), ctl_ok = dist_alloc_ctl();
+    if (dist_agree_p2p(want && ctl_ok)) return -1;
+    if (D.want_p2p) {
+        memset(&D.xa, 0, sizeof(D.xa));
+        D.xa.ring0 = 0; D.xa.chunk = ((len + cfg.world - 1) / cfg.world + 3) / 4 * 4;
+        D.xa.inbox_off = (8L * 72 * cfg.world + 255) / 256 * 256;       // behind 8 (all-reduce) + 64 (scalars) granule slots
+        memset(&D.xr, 0, sizeof(D.xr)); D.xr.ring0 = 8; D.xr.inbox_off = D.xa.inbox_off; D.xr.above = D.xr.below = -1;
+        if (dist_map_mail(D.xa.inbox_off + 4L * cfg.world * D.xa.chunk * (long)sizeof(float))) return -1;
+    }
+    char buf[128];
+    snprintf(buf, sizeof(buf), "residual shards, shared block of %ld unknowns", len);
+    D.form_text = buf;
+    return 0;
+}
+
+bool Plan::dist_partition_lists_ok(const ThalloX_Distributed& cfg, long U)
+{   // owned units first, every other local unit is a ghost with a source
+    const GhostSpec& G = ghost_spec_;
+    const long u0 = cfg.row0, u1 = cfg.row1;
+    bool ok = u0 == 0 && u1 >= 1 && u1 <= U && (long)G.ghost.size() == U - u1;
+    std::vector<char> seen((size_t)U, 0);
+    for (int b : G.boundary) ok = ok && b >= 0 && b < u1;
+    for (size_t g = 0; ok && g < G.ghost.size(); ++g) {
+        ok = G.ghost[g] >= u1 && G.ghost[g] < U && !seen[(size_t)G.ghost[g]] && G.src_rank[g] >= 0 && G.src_rank[g] < cfg.world && G.src_rank[g] != cfg.rank && G.src_pos[g] >= 0;
+        if (ok) seen[(size_t)G.ghost[g]] = 1;
+    }
+    std::vector<char> seen_b((size_t)std::max(1L, u1), 0);
+    for (int b : G.boundary) { if (ok && seen_b[(size_t)b]) ok = false; if (ok) seen_b[(size_t)b] = 1; }        // (a boundary unit listed twice would be sent twice)
+    if (!ok) set_error("distributed: the ghost exchange lists do not describe local units [0,%ld) owned + [%ld,%ld) ghosts (or list a boundary unit twice)", u1, u1, U);
+    return ok;
+}
+
+void Plan::dist_partition_upload(const int* counts, const thallo_units_t& un, long per_unit, bool& lists_ok, bool& mem_ok)
+{   // messages are padded to the largest boundary list; a ghost's source position must exist on its source rank.  The index lists and the ghosts' source offsets
+    // (in the two message kinds, in this rank's device-side inbox) go to the device
+    DistState& D = *dist_;
+    const GhostSpec& G = ghost_spec_;
+    const size_t ng = G.ghost.size();
+    long maxb = 1;
+    for (int r = 0; r < D.cfg.world; ++r) maxb = std::max(maxb, (long)counts[r]);
+    lists_ok = true;
+    for (size_t g = 0; g < ng; ++g) lists_ok = lists_ok && G.src_pos[g] < counts[G.src_rank[g]];
+    D.unit_slot = per_unit * maxb;
+    D.msg = 1 + D.unit_slot; D.msg_iter = 7 + D.unit_slot;
+    std::vector<long> s1(ng), s7(ng), sx(ng);
+    for (size_t g = 0; g < ng; ++g) {
+        const long at = (long)G.src_pos[g] * per_unit;
+        s1[g] = (long)G.src_rank[g] * D.msg + 1 + at; s7[g] = (long)G.src_rank[g] * D.msg_iter + 7 + at; sx[g] = (long)G.src_rank[g] * D.unit_slot + at;
+    }
+    auto up = [&](DeviceBuffer& b, const void* src, size_t bytes) { return b.alloc(bytes + 16) || (bytes && hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess); };
+    mem_ok = !(up(D.g_boundary, G.boundary.data(), G.boundary.size() * sizeof(int)) || up(D.g_ghost, G.ghost.data(), ng * sizeof(int)) ||
+               up(D.g_src1, s1.data(), ng * sizeof(long)) || up(D.g_src7, s7.data(), ng * sizeof(long)));
+    mem_ok = mem_ok && !up(D.g_srcx, sx.data(), ng * sizeof(long));
+    D.u_send = un; D.u_send.units = (const int*)D.g_boundary.ptr; D.u_send.n = (int)G.boundary.size();
+    D.u_recv1 = un; D.u_recv1.units = (const int*)D.g_ghost.ptr; D.u_recv1.src = (const long*)D.g_src1.ptr; D.u_recv1.n = (int)ng;
+    D.u_recv7 = D.u_recv1; D.u_recv7.src = (const long*)D.g_src7.ptr;
+    D.u_recvx = D.u_recv1; D.u_recvx.src = (const long*)D.g_srcx.ptr;
+}
+
+int Plan::dist_setup_range(const ThalloX_Distributed& cfg, bool part)
+{
+    const long U = plugin->range_units(), u0 = cfg.row0, u1 = cfg.row1;
+    if (!part && (U % cfg.world || u1 - u0 != U / cfg.world || u0 != (U / cfg.world) * cfg.rank)) {
+        set_error("distributed: rank %d of %d must own units [%ld,%ld) of %ld (equal contiguous ranges), got [%ld,%ld)", cfg.rank, cfg.world, (U / cfg.world) * cfg.rank, (U / cfg.world) * (cfg.rank + 1), U, u0, u1);
+        return -1;
+    }
+    //  bad lists are NOT an early return: the other ranks are about to enter the first collective of this set-up -- they are this rank's "no" in it
+    bool part_bad = part && !dist_partition_lists_ok(cfg, U);
+    if (plugin->set_owned_range(u0, u1)) return -1;
+    DistState& D = *dist_new_state(cfg, part ? DistForm::Partition : DistForm::Range);
+    D.row0 = (int)u0; D.row1 = (int)u1; D.Hl = (int)U;
+    std::vector<std::pair<long, long>> first, mine;
+    long off = 0, per_unit = 0;
+    thallo_units_t un; memset(&un, 0, sizeof(un));
+    for (auto& im : plugin->unknown_images()) {
+        const long per = im.n_floats / U, len = per * (u1 - u0);
+        if (im.n_floats % U || (!part && (len & 3))) {
+            set_error("distributed: an unknown image of %ld floats over %ld units, an owned slice of %ld floats (must divide / be a multiple of 4)", im.n_floats, U, len);
+            if (!part) return -1;
+            part_bad = true;
+        }
+        first.push_back({ off, len }); mine.push_back({ off + per * u0, len });
+        if (un.nplanes < 8) { un.base[un.nplanes] = off; un.len[un.nplanes] = (int)per; ++un.nplanes; }
+        per_unit += per;
+        D.piece_floats += len; off += im.n_floats;
+    }
+    if (first.size() > 8) { set_error("distributed: more than 8 unknown images"); return -1; }
+    D.pieces_first = segs(first); D.pieces_mine = segs(mine);
+    D.msg = 1 + D.piece_floats; D.msg_iter = 7 + D.piece_floats;
+    if (part) {
+        int counts[THALLO_DIST_MAX_WORLD]; const int mine_n = part_bad ? -1 : (int)ghost_spec_.boundary.size();       // every rank's boundary count
+        if (dist_alloc_messages(64)) return -1;
+        if (host_allgather(*this, D, &Plan::dist_allgather, &mine_n, counts, sizeof(int))) return -1;
+        for (int r = 0; r < cfg.world; ++r)
+            if (counts[r] < 0) {        // some rank's lists are inconsistent: EVERY rank returns here, in step
+                if (!part_bad) set_error("distributed: rank %d's ghost exchange lists are inconsistent", r);
+                return -1;
+            }
+        bool ok = true, mem = true;
+        dist_partition_upload(counts, un, per_unit, ok, mem);
+        if (dist_agree_or_fail(ok && mem, !ok ? "distributed: a ghost's source position lies outside its source rank's boundary list" : kNoMemory,
+                               "distributed: another rank's ghost exchange lists are inconsistent (or it ran out of device memory)")) return -1;
+        D.send.release(); D.gath.release();
+    }
+    if (dist_alloc_messages((size_t)std::max(D.msg_iter, 64L))) return -1;
+    if (dist_agree_or_fail(ensure_sums_buffer() == 0, kNoMemory, kOtherNoMemory)) return -1;
+    if (!part) { D.form_text = "unit ranges, full-length vectors"; return 0; }
+    // ---- device-side exchange of the boundary units (thallo_hip_dist_xunits): scalar ring + one inbox area per (parity, source rank)
+    const bool want = dist_p2p_requested() && D.unit_slot <= 32768, ctl_ok = dist_alloc_ctl();
+    if (dist_agree_p2p(want && ctl_ok)) return -1;
+    if (D.want_p2p) {
+        memset(&D.xr, 0, sizeof(D.xr)); D.xr.ring0 = 0; D.xr.above = D.xr.below = -1;
+        D.xr.inbox_off = (8L * 64 * cfg.world + 255) / 256 * 256;
+        if (dist_map_mail(D.xr.inbox_off + 2L * cfg.world * D.unit_slot * (long)sizeof(float))) return -1;
+    }
+    char buf[160];
+    snprintf(buf, sizeof(buf), "unit partition: %ld owned + %ld ghost units, %d boundary units sent", u1, U - u1, D.u_send.n);
+    D.form_text = buf;
+    return 0;
+}
+
+DistState* Plan::dist_new_row_state(const ThalloX_Distributed& cfg, DistForm form)
+{
     const int W = plugin->slab_width(), Hl = (int)dims[1];
     const int g = plugin->slab_ghost_rows();
     const int top = (int)cfg.row0, bot = Hl - (int)cfg.row1;
     if ((top != 0 && top != g) || (bot != 0 && bot != g) || (int)cfg.row1 - (int)cfg.row0 < g ||
         (top == g) != (cfg.rank > 0) || (bot == g) != (cfg.rank < cfg.world - 1)) {
         set_error("distributed: rank %d of %d owns rows [%u,%u) of a %d-row local image; expected exactly %d ghost row(s) towards each neighbour and at least as many owned rows", cfg.rank, cfg.world, cfg.row0, cfg.row1, Hl, g);
-        return -1;
+        return nullptr;
     }
-    if (plugin->set_row_slab((int)cfg.row0, (int)cfg.row1)) return -1;
-    if (plugin->set_slab_global((int)cfg.global_row0, cfg.global_rows ? (int)cfg.global_rows : Hl)) return -1;
-    if (flat && cfg.world > 1 && cfg.global_rows == 0) { set_error("distributed: %s needs global_row0 / global_rows", plugin->name()); return -1; }
-    hipDeviceSynchronize();
-    DistState* Dp = new DistState();
-    DistState& D = *Dp;
-    dist_ = Dp;
-    D.cfg = cfg; D.W = W; D.Hl = Hl; D.row0 = (int)cfg.row0; D.row1 = (int)cfg.row1; D.top = top; D.bot = bot; D.ghost = g;
+    if (plugin->set_row_slab((int)cfg.row0, (int)cfg.row1)) return nullptr;
+    if (plugin->set_slab_global((int)cfg.global_row0, cfg.global_rows ? (int)cfg.global_rows : Hl)) return nullptr;
+    if (form == DistForm::Flat && cfg.world > 1 && cfg.global_rows == 0) { set_error("distributed: %s needs global_row0 / global_rows", plugin->name()); return nullptr; }
+    DistState& D = *dist_new_state(cfg, form);
+    D.W = W; D.Hl = Hl; D.row0 = (int)cfg.row0; D.row1 = (int)cfg.row1; D.top = top; D.bot = bot; D.ghost = g;
     D.N = (long)W * Hl; D.na = v_.n_alloc;
-    D.flat = flat;
-    if (flat) {
-        D.rowlen = plugin->unknown_images()[0].n_floats / Hl;
-        if (D.rowlen & 3) { set_error("distributed: image rows of %ld floats (must be a multiple of 4)", D.rowlen); return -1; }
-        const long gl = g * D.rowlen;
-        D.seg_rows_fl = segs({ { D.rowlen * D.row0, gl }, { D.rowlen * (D.row1 - g), gl } });
-        D.seg_rows_top = top ? segs({ { D.rowlen * (D.row0 - g), gl } }) : segs({});
-        D.seg_rows_bot = bot ? segs({ { D.rowlen * D.row1, gl } }) : segs({});
-        D.msg = 2 + 2 * gl; D.msg_iter = 7 + 2 * gl; D.msg_x = 2 * gl;
-        const size_t words = (size_t)std::max(D.msg_iter, 64L);
-        if (D.send.alloc(words * sizeof(float)) || D.gath.alloc(words * sizeof(float) * cfg.world)) { set_error("distributed: out of device memory for the message buffers"); return -1; }
-        D.seg_rows_first = segs({ { D.rowlen * D.row0, gl } }); D.seg_rows_last = segs({ { D.rowlen * (D.row1 - g), gl } });
-        bool mem = ensure_sums_buffer() == 0;
-        if (mem && plugin->one_kernel_slab() && !plugin->use_preconditioner() && ensure_iter_buffers()) mem = false;       // (r', Ap' of the one-launch-per-iteration slab loop)
-        if (mem && (D.ctl.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(D.ctl.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess)) mem = false;
-        const bool unit_ok = plugin->slab_setup_ok();                    // (generated energies: the slab unit compiled on this rank)
-        const std::string unit_err = unit_ok ? "" : plugin->slab_setup_error();
-        bool all = false;
-        if (dist_agree(mem && unit_ok, all)) return -1;                  // the first use of the caller's all-gather: fails here, not mid-solve
-        if (!all) {
-            if (!unit_ok) set_error("distributed: rank %d: %s", cfg.rank, unit_err.c_str());
-            else set_error(mem ? "distributed: another rank could not set up its row slab (out of device memory, or its generated slab kernels failed to build)" : "distributed: out of device memory");
-            return -1;
-        }
-        // ---- device-side exchange (thallo_hip_dist_xrows): scalar ring + row inbox in one IPC allocation per rank; decided by every rank alike
-        D.want_p2p = cfg.device_exchange != 0;
-        {   const char* e = env_switch("THALLO_DIST_P2P"); if (e && e[0] == '0') D.want_p2p = false; }
-        all = false;
-        if (dist_agree(D.want_p2p, all)) return -1;
-        D.want_p2p = all;
-        if (D.want_p2p && dist_map_peers_flat()) return -1;
-        char buf[256];
-        snprintf(buf, sizeof(buf), "{\"exchange\": \"allgather\", \"form\": \"single-image, %d ghost rows\", \"rank\": %d, \"world\": %d, \"device_exchange_requested\": %s}", g, cfg.rank, cfg.world,
-                 cfg.device_exchange ? "true" : "false");
-        D.info = buf;
-        return 0;
+    return &D;
+}
+
+int Plan::dist_setup_flat(const ThalloX_Distributed& cfg)
+{
+    DistState* Dp = dist_new_row_state(cfg, DistForm::Flat);
+    if (!Dp) return -1;
+    DistState& D = *Dp;
+    const int g = D.ghost;
+    D.rowlen = plugin->unknown_images()[0].n_floats / D.Hl;
+    if (D.rowlen & 3) { set_error("distributed: image rows of %ld floats (must be a multiple of 4)", D.rowlen); return -1; }
+    const long gl = g * D.rowlen;
+    D.seg_rows_fl = segs({ { D.rowlen * D.row0, gl }, { D.rowlen * (D.row1 - g), gl } });
+    D.seg_rows_top = D.top ? segs({ { D.rowlen * (D.row0 - g), gl } }) : segs({});
+    D.seg_rows_bot = D.bot ? segs({ { D.rowlen * D.row1, gl } }) : segs({});
+    D.seg_rows_first = segs({ { D.rowlen * D.row0, gl } }); D.seg_rows_last = segs({ { D.rowlen * (D.row1 - g), gl } });
+    D.msg = 2 + 2 * gl; D.msg_iter = 7 + 2 * gl; D.msg_x = 2 * gl;
+    if (dist_alloc_messages((size_t)std::max(D.msg_iter, 64L))) return -1;
+    bool mem = ensure_sums_buffer() == 0;
+    if (mem && plugin->one_kernel_slab() && !plugin->use_preconditioner() && ensure_iter_buffers()) mem = false;       // (r', Ap' of the one-launch-per-iteration slab loop)
+    mem = mem && dist_alloc_ctl();
+    const bool unit_ok = plugin->slab_setup_ok();                    // (generated energies: the slab unit compiled on this rank)
+    const std::string unit_err = unit_ok ? "" : "distributed: rank " + std::to_string(cfg.rank) + ": " + plugin->slab_setup_error();
+    if (dist_agree_or_fail(mem && unit_ok, !unit_ok ? unit_err.c_str() : kNoMemory,
+                           "distributed: another rank could not set up its row slab (out of device memory, or its generated slab kernels failed to build)")) return -1;
+    // ---- device-side exchange (thallo_hip_dist_xrows): scalar ring + row inbox in one IPC allocation per rank
+    if (dist_agree_p2p(dist_p2p_requested())) return -1;
+    if (D.want_p2p) {
+        memset(&D.xr, 0, sizeof(D.xr)); D.xr.ring0 = 0; D.xr.inbox_half = gl;
+        D.xr.inbox_off = (8L * 64 * cfg.world + 255) / 256 * 256;            // behind 4 x 16 scalar slots of `world` granules
+        D.xr.above = D.top ? cfg.rank - 1 : -1; D.xr.below = D.bot ? cfg.rank + 1 : -1;
+        if (dist_map_mail(D.xr.inbox_off + 4 * gl * (long)sizeof(float))) return -1;
     }
-    D.want_p2p = cfg.device_exchange != 0;
-    {   const char* e = env_switch("THALLO_DIST_P2P"); if (e && e[0] == '0') D.want_p2p = false; }
+    char buf[64];
+    snprintf(buf, sizeof(buf), "single-image, %d ghost rows", g);
+    D.form_text = buf;
+    return 0;
+}
+
+int Plan::dist_setup_slab(const ThalloX_Distributed& cfg)
+{
+    DistState* Dp = dist_new_row_state(cfg, DistForm::Slab);
+    if (!Dp) return -1;
+    DistState& D = *Dp;
+    const int W = D.W;
+    D.want_p2p = dist_p2p_requested();
     // ---- messages
     const long N = D.N, na = D.na;
     auto row = [&](long y, long base) { return std::vector<std::pair<long, long>>{ { base + 2L * W * y, 2L * W }, { base + 2 * N + (long)W * y, (long)W } }; };
     auto cat = [](std::vector<std::pair<long, long>> a, const std::vector<std::pair<long, long>>& c) { a.insert(a.end(), c.begin(), c.end()); return a; };
     D.seg_first_last = segs(cat(cat(row(D.row0, 0), row(D.row0, na)), cat(row(D.row1 - 1, 0), row(D.row1 - 1, na))));
-    D.seg_top = top ? segs(cat(row(D.row0 - 1, 0), row(D.row0 - 1, na))) : segs({});
-    D.seg_bot = bot ? segs(cat(row(D.row1, 0), row(D.row1, na))) : segs({});
+    D.seg_top = D.top ? segs(cat(row(D.row0 - 1, 0), row(D.row0 - 1, na))) : segs({});
+    D.seg_bot = D.bot ? segs(cat(row(D.row1, 0), row(D.row1, na))) : segs({});
     D.seg_iter_fl = segs(cat(row(D.row0, 0), row(D.row1 - 1, 0)));
-    D.seg_iter_top = top ? segs(row(D.row0 - 1, 0)) : segs({});
-    D.seg_iter_bot = bot ? segs(row(D.row1, 0)) : segs({});
+    D.seg_iter_top = D.top ? segs(row(D.row0 - 1, 0)) : segs({});
+    D.seg_iter_bot = D.bot ? segs(row(D.row1, 0)) : segs({});
     D.msg = 1 + 12L * W + 2 * (W / 4);          // [alphaN_0 | first row: r, z | last row: r, z | flags bytes of the first, of the last owned row]
     D.msg_iter = 7 + 6L * W;                    // [alphaD | N, S1, S2 as (hi, lo) | first row of Ap_out | last row of Ap_out]
     D.msg_x = 6L * W;                           // boundary rows of the unknowns
-    const size_t words = (size_t)std::max(std::max(D.msg, D.msg_iter), std::max(D.msg_x, 64L));
-    if (D.send.alloc(words * sizeof(float)) || D.gath.alloc(words * sizeof(float) * cfg.world)) { set_error("distributed: out of device memory for the message buffers"); return -1; }   // (rank-local: nothing to agree through yet)
+    if (dist_alloc_messages((size_t)std::max(std::max(D.msg, D.msg_iter), std::max(D.msg_x, 64L)))) return -1;
     // ---- r, z, r', Ap, Ap' in ONE block (peers map it; pack / unpack address r and z through one base)
     const size_t block_bytes = (size_t)5 * D.na * sizeof(float);
     bool mem = true;
@@ -375,90 +446,55 @@ int Plan::set_distributed_impl(const ThalloX_Distributed& cfg)
         v_.r = b; v_.z = b + D.na; v_.r2 = b + 2 * D.na; v_.Ap = b + 3 * D.na; v_.Ap2 = b + 4 * D.na;
         if (ensure_iter_buffers()) mem = false;
     }
-    if (mem && (D.ctl.alloc(THALLO_DIST_CTL_WORDS * sizeof(unsigned)) || hipMemset(D.ctl.ptr, 0, THALLO_DIST_CTL_WORDS * sizeof(unsigned)) != hipSuccess)) mem = false;
-    {   bool all_mem = false;
-        if (dist_agree(mem, all_mem)) return -1;                         // every rank has its vectors, or every rank returns the error
-        if (!all_mem) { set_error(mem ? "distributed: another rank ran out of device memory" : "distributed: out of device memory"); return -1; }
-    }
+    mem = mem && dist_alloc_ctl();
+    if (dist_agree_or_fail(mem, kNoMemory, kOtherNoMemory)) return -1;   // every rank has its vectors, or every rank returns the error
     // ---- device-side exchange: mailbox, peers' mailboxes, the neighbours' blocks
-    bool all = false;
-    if (dist_agree(D.want_p2p, all)) return -1;                          // (also the first use of the caller's all-gather: fails here, not mid-solve)
-    D.want_p2p = all;
-    if (D.want_p2p) { if (dist_map_peers()) return -1; }
-    char buf[256];
-    snprintf(buf, sizeof(buf), "{\"exchange\": \"allgather\", \"rank\": %d, \"world\": %d, \"device_exchange_requested\": %s}", cfg.rank, cfg.world, cfg.device_exchange ? "true" : "false");
-    D.info = buf;
+    if (dist_agree_p2p(D.want_p2p)) return -1;
+    if (D.want_p2p && dist_map_peers()) return -1;
     return 0;
 }
 
-int Plan::dist_map_peers()
-{
+void Plan::dist_render_info()
+{   // the ONE place distributed_info()'s JSON is written.  Irregular, and kept (callers compare it): the Slab form has no "form"; "device_exchange_requested" is there until a
+    // Shard / Flat / Slab self-check has run, which brings "memory" instead -- a Partition self-check keeps the one and never gains the other; the Range form has neither
     DistState& D = *dist_;
-    const int world = D.cfg.world, rank = D.cfg.rank, W = D.W;
-    D.mail_L = std::max(sp.lIterations, 256);
-    const long n_slots = 7L * (D.mail_L + 2);                            // 7 granules per PCG iteration
-    PeerInfo mine; memset(&mine, 0, sizeof(mine));
-    // behind the scalar granules: the ghost area the resident PCG kernel's boundary waves of the neighbouring ranks store into (same offset on every rank)
-    const long gbytes = plugin->resident_ghost_bytes();
-    D.ghost_off = gbytes > 0 ? (8 * n_slots * world + 255) / 256 * 256 : 0;
-    mine.ok = thallo_hip_ipc_alloc2(gbytes > 0 ? D.ghost_off + gbytes : 8 * n_slots * world, &D.mail, D.handle_mail, &D.mem_kind[1]) >= 0 ? 1 : 0;
-    if (!mine.ok) D.mail = nullptr;
-    memcpy(mine.block, D.handle_block, 64); memcpy(mine.mail, D.handle_mail, 64);
-    mine.row0 = D.row0; mine.row1 = D.row1; mine.Hl = D.Hl; mine.na = D.na;
-    PeerInfo infos[THALLO_DIST_MAX_WORLD];
-    if (host_allgather(*this, D, &Plan::dist_allgather, &mine, infos, sizeof(PeerInfo))) return -1;
-    bool ok = true;
-    for (int r = 0; r < world; ++r) ok = ok && infos[r].ok == 1;
-    thallo_dist_t d; memset(&d, 0, sizeof(d));
-    d.world = world; d.rank = rank; d.mail = (unsigned long long*)D.mail; d.ctl = (unsigned*)D.ctl.ptr;
-    if (ok) {
-        for (int r = 0; r < world && ok; ++r) {
-            if (r == rank) { d.peer_mail[r] = d.mail; continue; }
-            void* p = nullptr;
-            if (thallo_hip_ipc_open(infos[r].mail, &p) < 0) { ok = false; break; }
-            D.opened.push_back(p); d.peer_mail[r] = (unsigned long long*)p;
-        }
-        D.d_iter[0] = D.d_iter[1] = d;
-        const int nbr[2] = { D.top ? rank - 1 : -1, D.bot ? rank + 1 : -1 };
-        for (int k = 0; k < 2 && ok; ++k) {
-            if (nbr[k] < 0) continue;
-            const PeerInfo& inf = infos[nbr[k]];
-            void* p = nullptr;
-            if (thallo_hip_ipc_open(inf.block, &p) < 0) { ok = false; break; }
-            D.opened.push_back(p);
-            // my first owned row lands in the upper neighbour's BOTTOM ghost row, my last owned row in the lower neighbour's TOP ghost row
-            const long ghost_row = k == 0 ? inf.row1 : inf.row0 - 1;
-            d.peer_r[k] = (float*)p; d.peer_off_o[k] = 2L * W * ghost_row; d.peer_off_a[k] = 2L * W * inf.Hl + (long)W * ghost_row;
-            for (int out = 0; out < 2; ++out) {                          // ... inside ITS Ap / Ap' (block layout [r | z | r' | Ap | Ap'], its own padded length)
-                const long base = (3 + out) * inf.na;
-                D.d_iter[out].peer_r[k] = (float*)p;
-                D.d_iter[out].peer_off_o[k] = base + 2L * W * ghost_row;
-                D.d_iter[out].peer_off_a[k] = base + 2L * W * inf.Hl + (long)W * ghost_row;
-            }
-        }
-        for (int out = 0; out < 2; ++out) for (int r = 0; r < world; ++r) D.d_iter[out].peer_mail[r] = d.peer_mail[r];
+    const DistState::SelfCheck& C = D.check;
+    const DistForm f = D.form;
+    const char* plain = f == DistForm::Shard ? "allreduce + allgather" : "allgather";
+    const char* p2p = f == DistForm::Shard ? "p2p-allreduce + allgather" : f == DistForm::Partition ? "p2p-units" : f == DistForm::Flat ? "p2p-rows" : "p2p-mailbox";
+    auto kind = [&](int i) { return D.mem_kind[i] == 1 ? "fine-grained" : "coarse-grained"; };
+    auto yes = [](bool b) { return b ? "true" : "false"; };
+    std::string s;
+    auto add = [&](const char* fmt, ...) __attribute__((format(printf, 2, 3))) { char buf[320]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap); s += buf; };
+    add("{\"exchange\": \"%s\"%s", D.p2p_on ? p2p : plain, D.switched_off ? ", \"switched_off\": true" : "");
+    if (!D.form_text.empty()) add(", \"form\": \"%s\"", D.form_text.c_str());
+    add(", \"rank\": %d, \"world\": %d", D.cfg.rank, D.cfg.world);
+    const bool rewritten = C.ran && f != DistForm::Partition;
+    if (f != DistForm::Range && !rewritten) add(", \"device_exchange_requested\": %s", yes(D.cfg.device_exchange != 0));
+    if (rewritten) add(", \"memory\": [\"%s\", \"%s\"]", f == DistForm::Slab ? kind(0) : "plan", kind(1));
+    if (C.ran) {
+        if (f == DistForm::Slab) add(", \"resident_loop\": %s", yes(C.resident_loop));
+        add(", \"self_check\": {\"%s\": %d, \"timeout\": %d", f == DistForm::Slab ? "iterations" : f == DistForm::Shard ? "allreduces" : "exchanges", C.count, C.timeout);
+        if (f == DistForm::Slab && std::isfinite(C.rel)) add(", \"max_rel_scalar_diff\": %.3g", C.rel);
+        else if (f == DistForm::Slab) add(", \"max_rel_scalar_diff\": null");               // (a timed-out run leaves NaNs: "nan" is not JSON)
+        add(", \"pass\": %s, \"all_ranks_pass\": %s, \"post_mortem\": [%u, %u, %u, %u, %u]}", yes(C.pass), yes(C.all), C.pm[0], C.pm[1], C.pm[2], C.pm[3], C.pm[4]);
     }
-    D.d = d;
-    bool all = false;
-    if (dist_agree(ok, all)) return -1;                                  // every rank mapped every peer, or nobody launches a kernel that touches one
-    D.mapped = all;
-    if (!all) D.want_p2p = false;
-    return 0;
+    D.info = s + "}";
 }
 
-int Plan::dist_map_mail(long bytes)
-{   // only the mailbox allocation is shared between ranks; the solver vectors stay where the Plan allocated them
+// ---- device-side exchange: the mailboxes
+int Plan::dist_exchange_mail(long bytes, bool same_bytes, DistPeerInfo& mine, DistPeerInfo* infos, bool& ok)
+{   // my mailbox allocated; `mine` (what the caller put in + the mailbox's handle) to every rank: ONE all-gather; every peer's mailbox opened, thallo_dist_t filled, what was
+    // opened recorded.  ok: every rank has its mailbox (same_bytes: of mine.na bytes) and this rank mapped them all.  The caller ends with dist_agree_mapped
     DistState& D = *dist_;
     const int world = D.cfg.world, rank = D.cfg.rank;
-    PeerInfo mine; memset(&mine, 0, sizeof(mine));
     mine.ok = thallo_hip_ipc_alloc2(bytes, &D.mail, D.handle_mail, &D.mem_kind[1]) >= 0 ? 1 : 0;
     if (!mine.ok) D.mail = nullptr;
     memcpy(mine.mail, D.handle_mail, 64);
-    mine.row0 = D.row0; mine.row1 = D.row1; mine.Hl = D.Hl; mine.na = bytes;
-    PeerInfo infos[THALLO_DIST_MAX_WORLD];
-    if (host_allgather(*this, D, &Plan::dist_allgather, &mine, infos, sizeof(PeerInfo))) return -1;
-    bool ok = true;
-    for (int r = 0; r < world; ++r) ok = ok && infos[r].ok == 1 && infos[r].na == bytes;
+    mine.row0 = D.row0; mine.row1 = D.row1; mine.Hl = D.Hl;
+    if (host_allgather(*this, D, &Plan::dist_allgather, &mine, infos, sizeof(DistPeerInfo))) return -1;
+    ok = true;
+    for (int r = 0; r < world; ++r) ok = ok && infos[r].ok == 1 && (!same_bytes || infos[r].na == mine.na);
     thallo_dist_t d; memset(&d, 0, sizeof(d));
     d.world = world; d.rank = rank; d.mail = (unsigned long long*)D.mail; d.ctl = (unsigned*)D.ctl.ptr;
     for (int r = 0; r < world && ok; ++r) {
@@ -468,24 +504,59 @@ int Plan::dist_map_mail(long bytes)
         D.opened.push_back(p); d.peer_mail[r] = (unsigned long long*)p;
     }
     D.d = d;
-    bool all = false;
-    if (dist_agree(ok, all)) return -1;
-    D.mapped = all;
-    if (!all) D.want_p2p = false;
     return 0;
 }
 
-int Plan::dist_map_peers_flat()
-{   // flat form: scalar ring + row inbox
+int Plan::dist_agree_mapped(bool ok)
+{   // every rank mapped every peer, or nobody launches a kernel that touches one
+    if (dist_agree(ok, dist_->mapped)) return -1;
+    if (!dist_->mapped) dist_->want_p2p = false;
+    return 0;
+}
+
+int Plan::dist_map_mail(long bytes)
+{   // only the mailbox allocation is shared between ranks; the solver vectors stay where the Plan allocated them
+    DistPeerInfo mine, infos[THALLO_DIST_MAX_WORLD]; memset(&mine, 0, sizeof(mine));
+    mine.na = bytes;
+    bool ok = false;
+    if (dist_exchange_mail(bytes, true, mine, infos, ok)) return -1;
+    return dist_agree_mapped(ok);
+}
+
+int Plan::dist_map_peers()
+{   // Slab form: the mailbox, and on top the neighbours' blocks (their ghost rows are where this rank's kernels store its boundary rows)
     DistState& D = *dist_;
-    const long gl = D.ghost * D.rowlen;
-    thallo_xrows_t x; memset(&x, 0, sizeof(x));
-    x.ring0 = 0;
-    x.inbox_off = (8L * 64 * D.cfg.world + 255) / 256 * 256;            // behind 4 x 16 scalar slots of `world` granules
-    x.inbox_half = gl;
-    x.above = D.top ? D.cfg.rank - 1 : -1; x.below = D.bot ? D.cfg.rank + 1 : -1;
-    D.xr = x;
-    return dist_map_mail(x.inbox_off + 4 * gl * (long)sizeof(float));
+    const int rank = D.cfg.rank, W = D.W;
+    D.mail_L = std::max(sp.lIterations, 256);
+    const long n_slots = 7L * (D.mail_L + 2);                            // 7 granules per PCG iteration
+    // behind the scalar granules: the ghost area the resident PCG kernel's boundary waves of the neighbouring ranks store into (same offset on every rank)
+    const long gbytes = plugin->resident_ghost_bytes();
+    D.ghost_off = gbytes > 0 ? (8 * n_slots * D.cfg.world + 255) / 256 * 256 : 0;
+    DistPeerInfo mine, infos[THALLO_DIST_MAX_WORLD]; memset(&mine, 0, sizeof(mine));
+    memcpy(mine.block, D.handle_block, 64); mine.na = D.na;
+    bool ok = false;
+    if (dist_exchange_mail(gbytes > 0 ? D.ghost_off + gbytes : 8 * n_slots * D.cfg.world, false, mine, infos, ok)) return -1;
+    if (ok) {
+        D.d_iter[0] = D.d_iter[1] = D.d;
+        const int nbr[2] = { D.top ? rank - 1 : -1, D.bot ? rank + 1 : -1 };
+        for (int k = 0; k < 2 && ok; ++k) {
+            if (nbr[k] < 0) continue;
+            const DistPeerInfo& inf = infos[nbr[k]];
+            void* p = nullptr;
+            if (thallo_hip_ipc_open(inf.block, &p) < 0) { ok = false; break; }
+            D.opened.push_back(p);
+            // my first owned row lands in the upper neighbour's BOTTOM ghost row, my last owned row in the lower neighbour's TOP ghost row
+            const long ghost_row = k == 0 ? inf.row1 : inf.row0 - 1;
+            D.d.peer_r[k] = (float*)p; D.d.peer_off_o[k] = 2L * W * ghost_row; D.d.peer_off_a[k] = 2L * W * inf.Hl + (long)W * ghost_row;
+            for (int out = 0; out < 2; ++out) {                          // ... inside ITS Ap / Ap' (block layout [r | z | r' | Ap | Ap'], its own padded length)
+                const long base = (3 + out) * inf.na;
+                D.d_iter[out].peer_r[k] = (float*)p;
+                D.d_iter[out].peer_off_o[k] = base + 2L * W * ghost_row;
+                D.d_iter[out].peer_off_a[k] = base + 2L * W * inf.Hl + (long)W * ghost_row;
+            }
+        }
+    }
+    return dist_agree_mapped(ok);
 }
 
 int Plan::dist_xrows(float* vec, bool rows, int mode, thallo_sum_t sm, const float* aD_part, const double* s3, int nb, float* out0, float* out1, float* zeta_state, int zeta_k)
@@ -515,12 +586,12 @@ float Plan::dist_cost()
         if (plugin->resident_status(ctx, 1, pm) != 0 && (plugin->resident_disable(), true))
             dist_fail("a bounded wait inside the resident PCG kernel ran out (wait kind %u, workgroup %u, wave %u, index %u, tag %u)", pm[0], pm[1], pm[2], pm[3], pm[4]);
     }
-    if ((D.flat || D.shard || D.part) && D.p2p_on && !D.failed) {  // the device-side row exchange's (all-reduce's) waits are bounded too
+    if (D.flat_exchange() && D.p2p_on && !D.failed) {  // the device-side row exchange's (all-reduce's) waits are bounded too
         const int err = thallo_hip_dist_error(D.d, 1, s);
         if (err != 0) {
             unsigned pm[5] = { 0, 0, 0, 0, 0 };
             hipMemcpy(pm, (unsigned*)D.ctl.ptr + 4, sizeof(pm), hipMemcpyDeviceToHost);
-            dist_fail("a bounded wait of the device-side %s ran out (slot %u, source rank %u, tag %u, found %u)", D.shard ? "all-reduce" : D.part ? "boundary exchange" : "row exchange", pm[0], pm[1], pm[2], pm[3]);
+            dist_fail("a bounded wait of the device-side %s ran out (slot %u, source rank %u, tag %u, found %u)", D.form == DistForm::Shard ? "all-reduce" : D.form == DistForm::Partition ? "boundary exchange" : "row exchange", pm[0], pm[1], pm[2], pm[3]);
         }
     }
     int nb = 0;
@@ -716,7 +787,7 @@ int Plan::dist_exchange_unknown_rows()
     float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
     TimedLaunch t(ctx, "SlabExchangeUnknowns");
     const auto& imgs = plugin->unknown_images();
-    if (D.flat && D.xrows_now && imgs.size() == 1 && imgs[0].n_floats == D.rowlen * D.Hl)      // (the unknown image has the flat vector's layout: the same row segments)
+    if (D.form == DistForm::Flat && D.xrows_now && imgs.size() == 1 && imgs[0].n_floats == D.rowlen * D.Hl)      // (the unknown image has the flat vector's layout: the same row segments)
         return dist_xrows(plugin->unknown_ptr(0), true, 0, thallo_sum_t{ nullptr, 0 }, nullptr, nullptr, 0, nullptr, nullptr);
     long pos = 0;
     for (size_t k = 0; k < imgs.size(); ++k) pos += 2 * g * (imgs[k].n_floats / D.Hl);
@@ -929,6 +1000,7 @@ int Plan::dist_gn_range(int L)
     float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
     const bool pc = plugin->use_preconditioner();
     const thallo_segs_t none = segs({});
+    const bool part = D.form == DistForm::Partition;
     cur_ = 0;
     const size_t bytes = (size_t)v_.n_alloc * sizeof(float);
     DCOPY(hipMemsetAsync(v_.p[0], 0, bytes, s), "p clear");              // (pcg_init clears the owned units only)
@@ -937,8 +1009,8 @@ int Plan::dist_gn_range(int L)
     if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }
     if (!D.failed) set_nb(B, nb);
     {   TimedLaunch t(ctx, "RangeExchangeInit");
-        if (D.part ? dist_ghosts(v_.r, B) : dist_replicate(v_.r, B)) return -1;       // alphaN_0; r of every unit (partition form: of the ghost units)
-        if (pc && (D.part ? dist_ghosts(v_.pre, -1) : dist_replicate(v_.pre, -1))) return -1;
+        if (part ? dist_ghosts(v_.r, B) : dist_replicate(v_.r, B)) return -1;       // alphaN_0; r of every unit (partition form: of the ghost units)
+        if (pc && (part ? dist_ghosts(v_.pre, -1) : dist_replicate(v_.pre, -1))) return -1;
     }
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
@@ -953,7 +1025,7 @@ int Plan::dist_gn_range(int L)
         }
         cur_ ^= 1;
         TimedLaunch t(ctx, "RangeExchange");
-        if (D.part && D.xrows_now) {
+        if (part && D.xrows_now) {
             const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };
             int rc = thallo_hip_dist_xunits(D.d, D.xr, v_.Ap, D.u_send, D.u_recvx, D.unit_slot, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12,
                                             D.failed ? 1 : nb, D.failed ? 1 : 0, scal(jD), scal(jB), s);
@@ -962,7 +1034,7 @@ int Plan::dist_gn_range(int L)
             if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
             continue;
         }
-        if (D.part) {       // [alphaD | N, S1, S2 | A p at my boundary units] -> the ghosts' A p (r, p, delta of a ghost then follow from the same arithmetic as its owner's)
+        if (part) {       // [alphaD | N, S1, S2 | A p at my boundary units] -> the ghosts' A p (r, p, delta of a ghost then follow from the same arithmetic as its owner's)
             DLOCAL(thallo_hip_units_pack_iter(v_.Ap, D.u_send, slot(jD), v_.s12, nb, send, s), "boundary pack");
             if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
             DLOCAL(thallo_hip_units_unpack_iter(v_.Ap, D.u_recv7, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "ghost unpack");
@@ -983,7 +1055,7 @@ int Plan::dist_gn_range(int L)
 int Plan::dist_allreduce(float* buf, long count)
 {
     DistState& D = *dist_;
-    if (D.shard && D.p2p_on && count == D.sh_len && (D.cfg.world > 1 || !D.checked)) {      // peer stores only (world size 1: nothing to add; the set-up's self-check still runs it): reduce-scatter + all-gather in one launch, sums in rank order (the same bits on every rank and in every run)
+    if (D.form == DistForm::Shard && D.p2p_on && count == D.sh_len && (D.cfg.world > 1 || !D.checked)) {      // peer stores only (world size 1: nothing to add; the set-up's self-check still runs it): reduce-scatter + all-gather in one launch, sums in rank order (the same bits on every rank and in every run)
         int rc = thallo_hip_dist_allreduce(D.d, D.xa, buf, count, D.failed ? 1 : 0, ctx.stream);
         if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
         if (rc < 0 && !D.failed) dist_fail("device-side all-reduce failed (%d)", rc);
@@ -1191,146 +1263,135 @@ int Plan::step_lm_shard(int ev_iter)
     return lm_accept_or_revert(rep[3], rep[4], newCost, lm_iterations_done(rep, L), ev_fin, ev_iter);
 }
 
+// ---- the device-side exchange's self-check.  It is used only if, ON THIS TOPOLOGY, it moves known patterns (Slab: reproduces the all-gather path's scalars) and no
+// bounded wait timed out.  Every rank takes the same decision: a rank-local failure in here (memory, a copy, a launch) is a "no" in the agreement at the end
+// (dist_check_finish), never an early return in front of the other ranks' collectives.
 int Plan::dist_self_check()
-{   // The device-side exchange is used only if, ON THIS TOPOLOGY, one GN step through it reproduces the all-gather path's alpha / beta
-    // scalars from the same unknowns (a stale ghost row or a lost granule shows up there; the two paths round identically except for the
-    // order of the cross-rank additions), and no bounded wait timed out.  Every rank takes the same decision: a rank-local failure in here
-    // (memory, a copy, a launch) is a "no" in the agreement at the end, never an early return in front of the other ranks' collectives.
+{
     DistState& D = *dist_;
     D.checked = true;
-    if (!D.mapped) { D.p2p_on = false; return 0; }                       // (agreed in dist_map_peers: the same on every rank)
+    if (!D.mapped) { D.p2p_on = false; return 0; }                       // (agreed in dist_agree_mapped: the same on every rank)
+    int rc = 0;
+    switch (D.form) {
+    case DistForm::Partition: rc = dist_check_units(); break;
+    case DistForm::Shard:     rc = dist_check_allreduce(); break;
+    case DistForm::Flat:      rc = dist_check_rows(); break;
+    case DistForm::Slab:      rc = dist_check_slab(); break;
+    case DistForm::Range:     return 0;                                  // (has no device-side exchange: never mapped)
+    }
+    if (rc == 0) dist_render_info();
+    return rc;                                                           // (a rank that failed in here says so at the cost evaluation that follows in Init)
+}
+
+// the frame of every check: the 500 ms spin bound (a topology where granules never become visible costs 0.5 s here, not the production bound), the form's exchanges,
+// the error word and the five post-mortem words, then dist_check_finish
+void Plan::dist_check_begin()
+{
+    const unsigned spin_ms = 500;
+    DistState& D = *dist_;
+    DCOPY(hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &spin_ms, sizeof(unsigned), hipMemcpyHostToDevice, ctx.stream), "spin bound");
+}
+void Plan::dist_check_read_error()
+{
+    DistState& D = *dist_;
+    D.check.timeout = !D.failed ? thallo_hip_dist_error(D.d, 1, ctx.stream) : -1;
+    hipMemcpy(D.check.pm, (unsigned*)D.ctl.ptr + 4, sizeof(D.check.pm), hipMemcpyDeviceToHost);
+}
+int Plan::dist_check_finish(bool pass, float* scratch, size_t scratch_floats, bool xrows)
+{   // the production spin bound again, the scratch vector clean, and the ONE agreement: the transport is on if every rank passed
+    DistState& D = *dist_;
     hipStream_t s = ctx.stream;
-    if (D.part) {
-        // partition form: three exchanges of a pattern: the boundary unit at position `pos` of rank r's list carries (r * 4096 + pos) * 8 + c + t in its c-th float
-        const unsigned spin_ms = 500, zero = 0;
-        int per = 0; for (int k = 0; k < D.u_send.nplanes; ++k) per += D.u_send.len[k];
-        const GhostSpec& G = ghost_spec_;
-        std::vector<float> host((size_t)v_.n, 0.0f), back((size_t)v_.n);
-        auto put = [&](std::vector<float>& v, int unit, int c, float x) { int k = 0; while (c >= D.u_send.len[k]) { c -= D.u_send.len[k]; ++k; } v[(size_t)(D.u_send.base[k] + (long)unit * D.u_send.len[k] + c)] = x; };
-        auto get = [&](const std::vector<float>& v, int unit, int c) { int k = 0; while (c >= D.u_send.len[k]) { c -= D.u_send.len[k]; ++k; } return v[(size_t)(D.u_send.base[k] + (long)unit * D.u_send.len[k] + c)]; };
-        bool pass = true; float got_sum = 0.0f;
-        DCOPY(hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &spin_ms, sizeof(unsigned), hipMemcpyHostToDevice, s), "spin bound");
-        D.xrows_now = true;
-        for (int t = 0; t < 3; ++t) {
+    const unsigned zero = 0;
+    hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &zero, sizeof(unsigned), hipMemcpyHostToDevice, s);
+    if (scratch) hipMemsetAsync(scratch, 0, scratch_floats * sizeof(float), s);
+    hipStreamSynchronize(s);
+    D.check.pass = pass && !D.failed && D.check.timeout == 0;
+    if (dist_agree(D.check.pass, D.check.all)) return -1;
+    D.check.ran = true;
+    D.p2p_on = D.check.all;
+    if (xrows) D.xrows_now = D.check.all;
+    return 0;
+}
+
+template <class Fill, class Exchange, class Verify>
+int Plan::dist_check_pattern(float* vec, size_t n, bool with_sum, bool xrows, Fill fill, Exchange exchange, Verify verify)
+{   // Partition, Shard, Flat: three exchanges (both parities, three ring positions) of a pattern in `vec` (scratch outside a step) whose outcome is known without asking
+    // anybody -- fill(host, t) writes it, verify(back, t) says whether the right values arrived -- and, with_sum, of one scalar per rank: rank + 1 + t
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    std::vector<float> host(n), back(n);
+    bool pass = true; float got_sum = 0.0f;
+    dist_check_begin();
+    D.check.count = 3;
+    for (int t = 0; t < 3; ++t) {
+        fill(host, t);
+        const float mine = (float)(D.cfg.rank + 1 + t);
+        DCOPY(hipMemcpyAsync(vec, host.data(), n * sizeof(float), hipMemcpyHostToDevice, s), "self-check pattern");
+        if (with_sum) DCOPY(hipMemcpyAsync(D.send.ptr, &mine, sizeof(float), hipMemcpyHostToDevice, s), "self-check scalar");
+        if (exchange()) return -1;
+        DCOPY(hipMemcpyAsync(back.data(), vec, n * sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
+        if (with_sum) DCOPY(hipMemcpyAsync(&got_sum, (float*)D.send.ptr + 8, sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
+        DCOPY(hipStreamSynchronize(s), "synchronise");
+        if (D.failed) { pass = false; continue; }
+        float want_sum = 0.0f;
+        for (int r = 0; r < D.cfg.world; ++r) want_sum += (float)(r + 1 + t);
+        if (with_sum && got_sum != want_sum) pass = false;
+        pass = pass && verify(back, t);
+    }
+    dist_check_read_error();
+    return dist_check_finish(pass, vec, n, xrows);
+}
+
+int Plan::dist_check_units()
+{   // the boundary unit at position `pos` of rank r's list carries (r * 4096 + pos) * 8 + c + t in its c-th float; every other unit -1
+    DistState& D = *dist_;
+    const GhostSpec& G = ghost_spec_;
+    int per = 0; for (int k = 0; k < D.u_send.nplanes; ++k) per += D.u_send.len[k];
+    auto at = [&](int unit, int c) { int k = 0; while (c >= D.u_send.len[k]) { c -= D.u_send.len[k]; ++k; } return (size_t)(D.u_send.base[k] + (long)unit * D.u_send.len[k] + c); };
+    return dist_check_pattern(v_.Ap, (size_t)v_.n, true, true,
+        [&](std::vector<float>& host, int t) {
             std::fill(host.begin(), host.end(), -1.0f);
-            for (size_t b = 0; b < G.boundary.size(); ++b) for (int c = 0; c < per; ++c) put(host, G.boundary[b], c, (float)((D.cfg.rank * 4096 + (int)b) * 8 + c + t));
-            const float mine = (float)(D.cfg.rank + 1 + t);
-            DCOPY(hipMemcpyAsync(v_.Ap, host.data(), (size_t)v_.n * sizeof(float), hipMemcpyHostToDevice, s), "self-check pattern");
-            DCOPY(hipMemcpyAsync(D.send.ptr, &mine, sizeof(float), hipMemcpyHostToDevice, s), "self-check scalar");
-            int rc = thallo_hip_dist_xunits(D.d, D.xr, v_.Ap, D.u_send, D.u_recvx, D.unit_slot, 0, thallo_sum_t{ (const float*)D.send.ptr, 1 }, nullptr, nullptr, 0, D.failed ? 1 : 0,
-                                            (float*)D.send.ptr + 8, nullptr, s);
+            for (size_t b = 0; b < G.boundary.size(); ++b) for (int c = 0; c < per; ++c) host[at(G.boundary[b], c)] = (float)((D.cfg.rank * 4096 + (int)b) * 8 + c + t);
+        },
+        [&]() {
+            const int rc = thallo_hip_dist_xunits(D.d, D.xr, v_.Ap, D.u_send, D.u_recvx, D.unit_slot, 0, thallo_sum_t{ (const float*)D.send.ptr, 1 }, nullptr, nullptr, 0, D.failed ? 1 : 0,
+                                                  (float*)D.send.ptr + 8, nullptr, ctx.stream);
             if (rc < 0 && !D.failed) dist_fail("device-side boundary exchange failed (%d)", rc);
-            DCOPY(hipMemcpyAsync(back.data(), v_.Ap, (size_t)v_.n * sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
-            DCOPY(hipMemcpyAsync(&got_sum, (float*)D.send.ptr + 8, sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
-            DCOPY(hipStreamSynchronize(s), "synchronise");
-            if (D.failed) { pass = false; continue; }
-            float want_sum = 0.0f; for (int r = 0; r < D.cfg.world; ++r) want_sum += (float)(r + 1 + t);
-            if (got_sum != want_sum) pass = false;
-            for (size_t g = 0; g < G.ghost.size() && pass; ++g)
-                for (int c = 0; c < per; ++c) if (get(back, G.ghost[g], c) != (float)((G.src_rank[g] * 4096 + G.src_pos[g]) * 8 + c + t)) { pass = false; break; }
-        }
-        D.xrows_now = false;
-        int err = !D.failed ? thallo_hip_dist_error(D.d, 1, s) : -1;
-        unsigned pm[5] = { 0, 0, 0, 0, 0 };
-        hipMemcpy(pm, (unsigned*)D.ctl.ptr + 4, sizeof(pm), hipMemcpyDeviceToHost);
-        hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &zero, sizeof(unsigned), hipMemcpyHostToDevice, s);
-        hipMemsetAsync(v_.Ap, 0, (size_t)v_.n * sizeof(float), s);
-        hipStreamSynchronize(s);
-        pass = pass && !D.failed && err == 0;
-        bool all = false;
-        if (dist_agree(pass, all)) return -1;
-        D.p2p_on = all; D.xrows_now = all;
-        const size_t at = D.info.find("\"allgather\"");
-        if (all && at != std::string::npos) D.info.replace(at, 11, "\"p2p-units\"");
-        char buf[256];
-        snprintf(buf, sizeof(buf), ", \"self_check\": {\"exchanges\": 3, \"timeout\": %d, \"pass\": %s, \"all_ranks_pass\": %s, \"post_mortem\": [%u, %u, %u, %u, %u]}}", err, pass ? "true" : "false",
-                 all ? "true" : "false", pm[0], pm[1], pm[2], pm[3], pm[4]);
-        if (!D.info.empty() && D.info.back() == '}') { D.info.pop_back(); D.info += buf; }
-        return 0;
-    }
-    if (D.shard) {
-        // shard form: three all-reduces (both parities, three ring positions) of a pattern whose sum is known exactly: rank r contributes (r + 1) * (i % 7 + 1)
-        const long len = D.sh_len;
-        const unsigned spin_ms = 500, zero = 0;
-        std::vector<float> host((size_t)len), back((size_t)len);
-        bool pass = true;
-        DCOPY(hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &spin_ms, sizeof(unsigned), hipMemcpyHostToDevice, s), "spin bound");
-        D.p2p_on = true;
-        for (int t = 0; t < 3; ++t) {
-            for (long i = 0; i < len; ++i) host[(size_t)i] = (float)((D.cfg.rank + 1) * (int)((i + t) % 7 + 1));
-            DCOPY(hipMemcpyAsync(v_.Ap + D.sh_off, host.data(), len * sizeof(float), hipMemcpyHostToDevice, s), "self-check pattern");
-            if (dist_allreduce(v_.Ap + D.sh_off, len)) return -1;
-            DCOPY(hipMemcpyAsync(back.data(), v_.Ap + D.sh_off, len * sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
-            DCOPY(hipStreamSynchronize(s), "synchronise");
-            if (D.failed) { pass = false; continue; }
-            const float S = (float)(D.cfg.world * (D.cfg.world + 1) / 2);
-            for (long i = 0; i < len && pass; ++i) if (back[(size_t)i] != S * (float)((i + t) % 7 + 1)) pass = false;
-        }
-        D.p2p_on = false;
-        int err = !D.failed ? thallo_hip_dist_error(D.d, 1, s) : -1;
-        unsigned pm[5] = { 0, 0, 0, 0, 0 };
-        hipMemcpy(pm, (unsigned*)D.ctl.ptr + 4, sizeof(pm), hipMemcpyDeviceToHost);
-        hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &zero, sizeof(unsigned), hipMemcpyHostToDevice, s);
-        hipMemsetAsync(v_.Ap + D.sh_off, 0, len * sizeof(float), s);
-        hipStreamSynchronize(s);
-        pass = pass && !D.failed && err == 0;
-        bool all = false;
-        if (dist_agree(pass, all)) return -1;
-        D.p2p_on = all;
-        char buf[512];
-        snprintf(buf, sizeof(buf), "{\"exchange\": \"%s\", \"form\": \"residual shards, shared block of %ld unknowns\", \"rank\": %d, \"world\": %d, \"memory\": [\"plan\", \"%s\"], \"self_check\": {\"allreduces\": 3, "
-                 "\"timeout\": %d, \"pass\": %s, \"all_ranks_pass\": %s, \"post_mortem\": [%u, %u, %u, %u, %u]}}",
-                 all ? "p2p-allreduce + allgather" : "allreduce + allgather", len, D.cfg.rank, D.cfg.world, D.mem_kind[1] == 1 ? "fine-grained" : "coarse-grained", err, pass ? "true" : "false",
-                 all ? "true" : "false", pm[0], pm[1], pm[2], pm[3], pm[4]);
-        D.info = buf;
-        return 0;
-    }
-    if (D.flat) {
-        // flat form: three exchanges (both parities, three ring positions) of a pattern that is a function of the GLOBAL row -- what has to arrive in the
-        // ghost rows is known without asking the neighbour -- and a scalar per rank; v_.Ap is scratch outside a step
-        const long rl = D.rowlen, nloc = rl * D.Hl;
-        const unsigned spin_ms = 500, zero = 0;
-        std::vector<float> host((size_t)nloc), back((size_t)nloc);
-        auto value = [&](long grow, long col, int t) { return (float)(((grow * rl + col) * 31 + t * 101) % 65521); };
-        bool pass = true; int err = 0; float got_sum = 0.0f;
-        DCOPY(hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &spin_ms, sizeof(unsigned), hipMemcpyHostToDevice, s), "spin bound");
-        for (int t = 0; t < 3; ++t) {
-            for (long y = 0; y < D.Hl; ++y) {
-                const bool owned = y >= D.row0 && y < D.row1;
-                for (long c = 0; c < rl; ++c) host[y * rl + c] = owned ? value((long)D.cfg.global_row0 + y, c, t) : -1.0f;
-            }
-            const float mine = (float)(D.cfg.rank + 1 + t);
-            DCOPY(hipMemcpyAsync(v_.Ap, host.data(), nloc * sizeof(float), hipMemcpyHostToDevice, s), "self-check pattern");
-            DCOPY(hipMemcpyAsync(D.send.ptr, &mine, sizeof(float), hipMemcpyHostToDevice, s), "self-check scalar");
-            if (dist_xrows(v_.Ap, true, 0, thallo_sum_t{ (const float*)D.send.ptr, 1 }, nullptr, nullptr, 0, (float*)D.send.ptr + 8, nullptr)) return -1;
-            DCOPY(hipMemcpyAsync(back.data(), v_.Ap, nloc * sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
-            DCOPY(hipMemcpyAsync(&got_sum, (float*)D.send.ptr + 8, sizeof(float), hipMemcpyDeviceToHost, s), "self-check read-back");
-            DCOPY(hipStreamSynchronize(s), "synchronise");
-            if (D.failed) { pass = false; continue; }
-            float want_sum = 0.0f;
-            for (int r = 0; r < D.cfg.world; ++r) want_sum += (float)(r + 1 + t);
-            if (got_sum != want_sum) pass = false;
-            for (long y = 0; y < D.Hl && pass; ++y)
-                for (long c = 0; c < rl; ++c) if (back[y * rl + c] != value((long)D.cfg.global_row0 + y, c, t)) { pass = false; break; }
-        }
-        err = !D.failed ? thallo_hip_dist_error(D.d, 1, s) : -1;
-        unsigned pm[5] = { 0, 0, 0, 0, 0 };
-        hipMemcpy(pm, (unsigned*)D.ctl.ptr + 4, sizeof(pm), hipMemcpyDeviceToHost);
-        hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &zero, sizeof(unsigned), hipMemcpyHostToDevice, s);
-        hipMemsetAsync(v_.Ap, 0, nloc * sizeof(float), s);
-        hipStreamSynchronize(s);
-        pass = pass && !D.failed && err == 0;
-        bool all = false;
-        if (dist_agree(pass, all)) return -1;
-        D.p2p_on = all; D.xrows_now = all;
-        char buf[512];
-        snprintf(buf, sizeof(buf), "{\"exchange\": \"%s\", \"form\": \"single-image, %d ghost rows\", \"rank\": %d, \"world\": %d, \"memory\": [\"plan\", \"%s\"], \"self_check\": {\"exchanges\": 3, \"timeout\": %d, "
-                 "\"pass\": %s, \"all_ranks_pass\": %s, \"post_mortem\": [%u, %u, %u, %u, %u]}}",
-                 all ? "p2p-rows" : "allgather", D.ghost, D.cfg.rank, D.cfg.world, D.mem_kind[1] == 1 ? "fine-grained" : "coarse-grained", err, pass ? "true" : "false", all ? "true" : "false",
-                 pm[0], pm[1], pm[2], pm[3], pm[4]);
-        D.info = buf;
-        return 0;
-    }
+            return 0;
+        },
+        [&](const std::vector<float>& back, int t) {
+            for (size_t g = 0; g < G.ghost.size(); ++g)
+                for (int c = 0; c < per; ++c) if (back[at(G.ghost[g], c)] != (float)((G.src_rank[g] * 4096 + G.src_pos[g]) * 8 + c + t)) return false;
+            return true;
+        });
+}
+
+int Plan::dist_check_allreduce()
+{   // a pattern whose sum is known exactly: rank r contributes (r + 1) * (i % 7 + 1)
+    DistState& D = *dist_;
+    const float S = (float)(D.cfg.world * (D.cfg.world + 1) / 2);
+    return dist_check_pattern(v_.Ap + D.sh_off, (size_t)D.sh_len, false, false,
+        [&](std::vector<float>& host, int t) { for (size_t i = 0; i < host.size(); ++i) host[i] = (float)((D.cfg.rank + 1) * (int)((i + t) % 7 + 1)); },
+        [&]() { D.p2p_on = true; const int rc = dist_allreduce(v_.Ap + D.sh_off, D.sh_len); D.p2p_on = false; return rc; },      // (the transport under test, for this call only)
+        [&](const std::vector<float>& back, int t) { for (size_t i = 0; i < back.size(); ++i) if (back[i] != S * (float)((i + t) % 7 + 1)) return false; return true; });
+}
+
+int Plan::dist_check_rows()
+{   // a pattern that is a function of the GLOBAL row -- what has to arrive in the ghost rows is known without asking the neighbour; ghost rows start as -1
+    DistState& D = *dist_;
+    const long rl = D.rowlen, g0 = (long)D.cfg.global_row0;
+    auto value = [&](long grow, long col, int t) { return (float)(((grow * rl + col) * 31 + t * 101) % 65521); };
+    return dist_check_pattern(v_.Ap, (size_t)(rl * D.Hl), true, true,
+        [&](std::vector<float>& host, int t) { for (long y = 0; y < D.Hl; ++y) for (long c = 0; c < rl; ++c) host[y * rl + c] = y >= D.row0 && y < D.row1 ? value(g0 + y, c, t) : -1.0f; },
+        [&]() { return dist_xrows(v_.Ap, true, 0, thallo_sum_t{ (const float*)D.send.ptr, 1 }, nullptr, nullptr, 0, (float*)D.send.ptr + 8, nullptr); },
+        [&](const std::vector<float>& back, int t) { for (long y = 0; y < D.Hl; ++y) for (long c = 0; c < rl; ++c) if (back[y * rl + c] != value(g0 + y, c, t)) return false; return true; });
+}
+
+int Plan::dist_check_slab()
+{   // one GN step through the device-side exchange must reproduce the all-gather path's alpha / beta scalars from the same unknowns (a stale ghost row or a lost
+    // granule shows up there; the two paths round identically except for the order of the cross-rank additions)
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
     const int Lc = std::max(1, std::min(6, sp.lIterations)), B = 2, nw = 2 * Lc + 1;
     {   // does EVERY rank's slab fit the resident PCG kernel?  (asked before the first device-side step: dist_gn reads the answer)
         bool all = false;
@@ -1347,11 +1408,9 @@ int Plan::dist_self_check()
             DCOPY(hipMemcpyAsync(save ? keep[k].ptr : (void*)plugin->unknown_ptr((int)k), save ? (void*)plugin->unknown_ptr((int)k) : keep[k].ptr, bytes, hipMemcpyDeviceToDevice, s), "unknowns copy");
         }
     };
-    const unsigned spin_ms = 500;       // a topology where granules never become visible costs 0.5 s here, not the production bound
-    const unsigned zero = 0;
     std::vector<float> ref(nw, 0.0f), got(nw, 1.0f);
     restore(true);
-    DCOPY(hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &spin_ms, sizeof(unsigned), hipMemcpyHostToDevice, s), "spin bound");
+    dist_check_begin();
     if (dist_gn(Lc, false)) return -1;
     if (!D.failed) DCOPY(hipMemcpyAsync(ref.data(), scal(B), nw * sizeof(float), hipMemcpyDeviceToHost, s), "scalar read-back");
     DCOPY(hipStreamSynchronize(s), "synchronise");
@@ -1359,34 +1418,22 @@ int Plan::dist_self_check()
     if (dist_gn(Lc, true)) return -1;
     if (!D.failed) DCOPY(hipMemcpyAsync(got.data(), scal(B), nw * sizeof(float), hipMemcpyDeviceToHost, s), "scalar read-back");
     DCOPY(hipStreamSynchronize(s), "synchronise");
-    int err = !D.failed ? thallo_hip_dist_error(D.d, 1, s) : -1;
-    unsigned pm[5] = { 0, 0, 0, 0, 0 };
-    hipMemcpy(pm, (unsigned*)D.ctl.ptr + 4, sizeof(pm), hipMemcpyDeviceToHost);
+    dist_check_read_error();
     if (resident_used_) {      // the device-side run went through the resident slab kernel: a bounded wait that ran out in THERE is a "no" of this check (and is
         resident_used_ = false;                                              // cleared here: the cost evaluation that follows must not take it for a failure of the solve)
         unsigned rpm[5] = { 0, 0, 0, 0, 0 };
-        if (!D.failed && plugin->resident_status(ctx, 1, rpm) != 0) { err = err ? err : 2; for (int i = 0; i < 5; ++i) pm[i] = rpm[i]; }
+        if (!D.failed && plugin->resident_status(ctx, 1, rpm) != 0) { if (!D.check.timeout) D.check.timeout = 2; for (int i = 0; i < 5; ++i) D.check.pm[i] = rpm[i]; }
     }
     restore(false);
-    hipMemcpyAsync((unsigned*)D.ctl.ptr + 2, &zero, sizeof(unsigned), hipMemcpyHostToDevice, s);
-    hipStreamSynchronize(s);
     double rel = 0.0;
     for (int i = 0; i < nw; ++i) {
         const double e = std::fabs((double)got[i] - (double)ref[i]) / std::fmax(std::fabs((double)ref[i]), 1e-30);
         if (!(e <= rel)) rel = e;                                        // NaN-propagating max
     }
-    const bool pass = !D.failed && err == 0 && rel <= 1e-3;
-    bool all = false;
-    if (dist_agree(pass, all)) return -1;
-    D.p2p_on = all;
-    char buf[512], relbuf[32];
-    if (std::isfinite(rel)) snprintf(relbuf, sizeof(relbuf), "%.3g", rel); else snprintf(relbuf, sizeof(relbuf), "null");      // (a timed-out run leaves NaNs: "nan" is not JSON)
-    snprintf(buf, sizeof(buf), "{\"exchange\": \"%s\", \"rank\": %d, \"world\": %d, \"memory\": [\"%s\", \"%s\"], \"resident_loop\": %s, \"self_check\": {\"iterations\": %d, \"timeout\": %d, "
-             "\"max_rel_scalar_diff\": %s, \"pass\": %s, \"all_ranks_pass\": %s, \"post_mortem\": [%u, %u, %u, %u, %u]}}",
-             all ? "p2p-mailbox" : "allgather", D.cfg.rank, D.cfg.world, D.mem_kind[0] == 1 ? "fine-grained" : "coarse-grained", D.mem_kind[1] == 1 ? "fine-grained" : "coarse-grained",
-             (all && D.resident_all) ? "true" : "false", Lc, err, relbuf, pass ? "true" : "false", all ? "true" : "false", pm[0], pm[1], pm[2], pm[3], pm[4]);
-    D.info = buf;
-    return 0;                                                            // (a rank that failed in here says so at the cost evaluation that follows in Init)
+    D.check.count = Lc; D.check.rel = rel;
+    if (dist_check_finish(rel <= 1e-3, nullptr, 0, false)) return -1;
+    D.check.resident_loop = D.check.all && D.resident_all;
+    return 0;
 }
 
 int Plan::step_gn_slab(int ev_iter)
@@ -1397,7 +1444,15 @@ int Plan::step_gn_slab(int ev_iter)
     const int ev_lin = timer_.start("Linear Solve", s);
     const bool p2p = D.p2p_on && L <= D.mail_L;                          // (same L on every rank: same decision)
     // (nonzero only when the collective itself failed; a rank-local failure leaves this rank in step with the others until the next cost evaluation)
-    if (D.shard ? dist_gn_shard(L) : D.range ? dist_gn_range(L) : D.flat ? dist_gn_flat(L) : dist_gn(L, p2p)) return 0;
+    int rc = 0;
+    switch (D.form) {
+    case DistForm::Shard:     rc = dist_gn_shard(L); break;
+    case DistForm::Range:
+    case DistForm::Partition: rc = dist_gn_range(L); break;
+    case DistForm::Flat:      rc = dist_gn_flat(L); break;
+    case DistForm::Slab:      rc = dist_gn(L, p2p); break;
+    }
+    if (rc) return 0;
     timer_.stop(ev_lin, s);
     sp.nIter++;
     timer_.stop(ev_iter, s);
@@ -1411,17 +1466,7 @@ int Plan::dist_control(int what, int value)
     if (what == 0) return D.mapped ? thallo_hip_dist_error(D.d, value ? 1 : 0, ctx.stream) : 0;
     if (what == 2) { D.inject = value; return 0; }
     if (what == 1) {
-        if (value == 0 && D.p2p_on) {
-            D.p2p_on = false; D.xrows_now = false;
-            size_t at = D.info.find("\"p2p-mailbox\"");
-            if (at != std::string::npos) D.info.replace(at, 13, "\"allgather\", \"switched_off\": true");
-            at = D.info.find("\"p2p-rows\"");
-            if (at != std::string::npos) D.info.replace(at, 10, "\"allgather\", \"switched_off\": true");
-            at = D.info.find("\"p2p-units\"");
-            if (at != std::string::npos) D.info.replace(at, 11, "\"allgather\", \"switched_off\": true");
-            at = D.info.find("\"p2p-allreduce + allgather\"");
-            if (at != std::string::npos) D.info.replace(at, 27, "\"allreduce + allgather\", \"switched_off\": true");
-        }
+        if (value == 0 && D.p2p_on) { D.p2p_on = false; D.xrows_now = false; D.switched_off = true; dist_render_info(); }
         return 0;
     }
     return -1;
@@ -1429,7 +1474,7 @@ int Plan::dist_control(int what, int value)
 
 int Plan::dist_kernel_only(int reps)
 {
-    if (!dist_ || !ready_ || dist_->flat || dist_->range) return -1;
+    if (!dist_ || !ready_ || dist_->form != DistForm::Slab) return -1;
     const int B = 2;
     for (int i = 0; i < reps; ++i) {
         const int nb = plugin->pcg_iter(ctx, v_, 0, 0, sum(B), sum(B + 1), sum(B + 2), sum(B), sum(B + 1), slot(B + 3), nullptr, nullptr);
