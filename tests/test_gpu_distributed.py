@@ -188,6 +188,70 @@ def test_resident_slab_loop_is_bitwise_the_launch_per_iteration_transport(monkey
         assert (ra[4] == rb[4]).all() and (ra[5] == rb[5]).all()
 
 
+def _worker_ring(rank, world, port, W, H, lit, planes, device_exchange, q):
+    """One rank solves twice inside one process group, each time through a fresh plan (the switch is read when a plan is made): `delta += alpha p` inside every
+    launch (THALLO_DELTA_PLANES=0), then the case's ring.  The kernel statistics are those of the two GN steps (not of the first Init's self-check)."""
+    import torch
+    import torch.distributed as dist
+    from thallo_amd import synthetic as syn
+    from thallo_amd.distributed import PlanSlabSolver
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    os.environ["THALLO_MARCH"] = "2"; os.environ["THALLO_RESIDENT"] = "0"
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        p = syn.image_warping(W, H, n_markers=8)
+        out = []
+        for dp in ("0", planes):
+            if dp is None: os.environ.pop("THALLO_DELTA_PLANES", None)
+            else: os.environ["THALLO_DELTA_PLANES"] = dp
+            solver = PlanSlabSolver(p, W, H, rank, world, lit, device_exchange=device_exchange)
+            solver.init()
+            solver.solver.reset_kernel_stats()
+            costs, traces = [solver.cost()], []
+            for _ in range(2):
+                solver.gn_step()
+                costs.append(solver.cost()); traces.append(solver.solver.alpha_beta_trace())
+            err = solver.solver.distributed_error()
+            off, ang = solver.owned()
+            out.append((costs, traces, off, ang, solver.info, err, solver.solver.kernel_stats(), solver.lay.g0, solver.lay.g1))
+            solver.solver.close()
+        q.put((rank, out))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,W,H,lit,planes,device_exchange", [(2, 128, 64, 12, "3", False), (2, 128, 64, 12, "3", True), (3, 64, 100, 9, "4", False), (2, 128, 64, 40, None, False)])
+def test_slab_ring_of_p_planes_is_bitwise_a_delta_update_per_iteration(world, W, H, lit, planes, device_exchange):
+    """The ring of p planes on a row slab's launch-per-iteration schedule with a ring SHORTER than the PCG loop, so that a slab's in-loop PCGDeltaUpdate runs (owned-row
+    offsets non-zero, the ranks' row counts different): per rank, costs, the whole alpha / beta trace and the owned rows of both unknowns are BIT-identical to
+    `delta += alpha p` inside every launch (THALLO_DELTA_PLANES=0) after two GN steps, on both transports; the flushes are those of the one-GPU rule
+    (test_gpu_parity.py::test_ring_of_p_planes_is_bitwise_a_delta_update_per_iteration, default placement)."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_ring, args=(r, world, port, W, H, lit, planes, device_exchange, q)) for r in range(world)]
+    for p_ in procs:
+        p_.start()
+    res = sorted(_collect(q, procs, world), key=lambda t: t[0])
+    n = min(lit, 33 if planes is None else int(planes))
+    flushes = flushed = 0                # before launch k: when plane k mod n still holds a term that is not in delta, everything up to k - 2 goes
+    for k in range(lit):
+        if k >= n and flushed < k - n + 1: flushes += 1; flushed = k - 1
+    assert flushes >= 1
+    for rank, ((c0, t0, o0, a0, i0, e0, n0, g0, g1), (c1, t1, o1, a1, i1, e1, n1, _g0, _g1)) in res:
+        print(f"rank {rank}: rows [{g0}, {g1}), PCGDeltaUpdate {n1.get('PCGDeltaUpdate', {}).get('launches', 0)} (rule: 2 x {flushes}), PCGIteration {n0['PCGIteration']['launches']} / {n1['PCGIteration']['launches']}")
+        assert e0 == 0 and e1 == 0, (rank, i0, i1)
+        assert i0["exchange"] == i1["exchange"] == ("p2p-mailbox" if device_exchange else "allgather"), (i0, i1)
+        assert all(np.isfinite(c0)) and len(c0) == 3 and len(t0) == 2 and len(t0[0]) == lit
+        assert "PCGDeltaUpdate" not in n0 and n1.get("PCGDeltaUpdate", {}).get("launches", 0) == 2 * flushes, (rank, n1, flushes)
+        assert n0["PCGIteration"]["launches"] == n1["PCGIteration"]["launches"]
+        assert t0 == t1, [(i, k) for i, (x, y) in enumerate(zip(t0, t1)) for k, (u, v) in enumerate(zip(x, y)) if u != v][:3]
+        assert c0 == c1, (c0, c1)
+        assert (o0 == o1).all() and (a0 == a1).all()
+
+
 def test_hip_single_slab_equals_library_path(orc):
     """world_size 1 declared as a slab == the plain single-device plan on the same instance (same kernels, same one-kernel schedule; the slab
     form adds its scalars through the rank-ordered finish instead of the kernel's last workgroup: same order, same bits)."""

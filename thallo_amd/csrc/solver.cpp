@@ -371,9 +371,7 @@ void Plan::init(void** params)
         bool all = false;
         if (dist_agree(plugin->resident_slab_ok() && dist_->ghost_off > 0, all)) { ready_ = false; return; }
         dist_->resident_all = all;
-        const bool mine = plugin->dist_defers_finish() && ensure_iter_buffers() == 0 && (dist_->gs.ptr || dist_->gs.alloc(64) == 0);
-        if (dist_agree(mine, all)) { ready_ = false; return; }
-        dist_->defer_state = all ? 1 : 0;
+        if (dist_agree_defer()) { ready_ = false; return; }
     }
     sp.nIter = 0;
     if (!lm_ && one_kernel_ && plugin->one_kernel_iteration() && !plugin->resident_ok()) { ring_prepare(sp.lIterations); ring_L_ = sp.lIterations; }      // (the ring's planes: here, not inside a step)
@@ -439,8 +437,7 @@ void Plan::linear_update_tail(int L, bool batched)
     long off = 0;
     for (size_t k = 0; k < imgs.size(); ++k) {
         TimedLaunch t(ctx, "PCGLinearUpdate");
-        long lo = 0, len = imgs[k].n_floats;
-        if (dist_ && !dist_->full_vectors()) { const long rowlen = imgs[k].n_floats / dist_->Hl; lo = rowlen * dist_->row0; len = rowlen * (dist_->row1 - dist_->row0); }
+        const long lo = owned_range(k).lo, len = owned_range(k).len;
         float* X = plugin->unknown_ptr((int)k) + lo;
         const float* dl = v_.delta + off + lo;
         if (L > 1 && batched && ((L - 1) & 1))
@@ -450,6 +447,13 @@ void Plan::linear_update_tail(int L, bool batched)
         off += imgs[k].n_floats;
     }
     plugin->unknowns_written();
+}
+Plan::Owned Plan::owned_range(size_t u) const
+{
+    const long n = plugin->unknown_images()[u].n_floats;
+    if (!dist_ || dist_->full_vectors()) return { 0, n };
+    const long rowlen = n / dist_->Hl;
+    return { rowlen * dist_->row0, rowlen * (dist_->row1 - dist_->row0) };
 }
 
 // The head and the tail that every PCG-loop form of a GN step shares (the direct solve records other coarse events and keeps its own lines).
@@ -508,9 +512,9 @@ int Plan::step_gn(int ev_iter)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         // PCGStep1 (+ previous iteration's PCGStep3 and delta update)
-        thallo_sum_t aNp = sum(k ? jN - 2 : jN), aDp = sum(k ? jD - 2 : jD), bNp = sum(jN);
-        if (batched) nb = plugin->pcg_step1_mode(ctx, v_, cur_, THALLO_IW_STEP1_MODE(k, 1), aNp, aDp, bNp, sum(k > 1 ? jN - 4 : jN), sum(k > 1 ? jD - 4 : jD), slot(jD));
-        else         nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, aNp, aDp, bNp, slot(jD));
+        const PrevAlpha a = prev_alpha(k);
+        if (batched) nb = plugin->pcg_step1_mode(ctx, v_, cur_, THALLO_IW_STEP1_MODE(k, 1), a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD));
+        else         nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
         if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
         set_nb(jD, nb); finish(jD); cur_ ^= 1;
         nb = plugin->pcg_step2(ctx, v_, sum(jN), sum(jD), slot(jB));      // PCGStep2 (r, z, betaN)
@@ -543,144 +547,175 @@ int Plan::ensure_lm_vectors()
     return 0;
 }
 
-int Plan::step_gn_one_kernel(int ev_iter)
-{   // GN branch, ONE kernel + one scalar launch per PCG iteration (DESIGN.md "PCG schedule", thallo_hip_iw_pcg_iter)
-    if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
-    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    hipStream_t s = ctx.stream;
-    int ev_lin, nb;
-    if (!gn_begin(ev_lin)) return 0;
-    // Deferred finish (where the plugin offers it): the launch of iteration k adds up iteration k-1's partials
-    // itself -- alphaD_{k-1} and betaN_{k-1} = N - 2 alpha S1 + alpha^2 S2 -- while its first rows load, instead of iteration k-1's last workgroup
-    // reading them back at the very end of its launch; one one-wave launch per GN step finishes the last iteration.
+// ---- One GN step on ONE kernel + at most one scalar launch per PCG iteration (DESIGN.md "GN schedules", thallo_hip_iw_pcg_iter):
+// step_gn_one_kernel = set-up, ONE of three PCG loops (gn_schedule), the shared finish.
+Plan::GnSchedule Plan::gn_schedule(int L, int n_ring)
+{   // first match
     const bool defer = plugin->iter_defers_finish();
+    if (n_ring >= 2 && defer && L >= 2 && plugin->persist_ok()) return GnSchedule::Persist;      // (only the research build's plugin offers it)
+    return defer ? GnSchedule::Deferred : GnSchedule::FinishInLaunch;
+}
+
+int Plan::step_gn_one_kernel(int ev_iter)
+{
+    if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
+    const int L = sp.lIterations;
+    int ev_lin;
+    if (!gn_begin(ev_lin)) return 0;
     // Round 5: a RING of p planes instead of the ping-pong pair.  Launch k writes p_k into plane k mod n and carries no delta update at all; delta is touched once
     // per n - 1 iterations by thallo_hip_linear_update_n (every pending alpha_j p_j, oldest first, one fma each: the bits of an update per iteration) and the step's
     // last terms ride in PCGLinearUpdate.  Per iteration and unknown 4 (12 + 24 / (n - 1)) / 12 bytes of delta traffic instead of 24 (every iteration) or 18 (every other).
     const int n_ring = ring_planes(L);
-    const bool ring = n_ring >= 2;
-    const bool batched = !ring && batch_delta_ && delta_planes_ != 0 && plugin->batches_delta();      // THALLO_IW_STEP1_MODE(k, 1): every other delta update is deferred
-    // Where the update runs.  Default: on the loop's own stream, whole rings at a time (up to 32 terms per launch).  THALLO_DELTA_PLANES=N:W: NEXT TO the loop, on a
-    // low-priority stream of the plan's own and on at most W workgroups (0: one per CU), in chunks of (n - 1) / 2 terms as soon as their scalars are words; the launch
-    // that overwrites a chunk's first plane waits for its event.  Measured (profiles/r05/ring_ab*.txt): next to the loop 0.7-2 % more PCG iterations per second, but the
-    // marching launches that share the chip with an update take ~8 us longer each -- the loop streams at the memory system's rate in its steady state, and what the
-    // second kernel takes there it does not give back in the ramps and tails.  Not worth a second stream in the default path.
-    const bool persist = ring && defer && L >= 2 && plugin->persist_ok();
-    const bool async = ring && aux_async_ && !persist && aux_stream();
-    const int chunk = !ring ? 0 : async ? (n_ring - 1) / 2 > 0 ? (n_ring - 1) / 2 : 1 : n_ring - 1;
-    int flushed = 0;                       // p_0 .. p_{flushed-1} are in delta, or on their way there (async)
-    int synced = 0;                        // ... and the loop's stream has waited for the updates of p_0 .. p_{synced-1}
-    struct Sent { int upto; hipEvent_t done; };
-    std::vector<Sent> sent;
-    size_t n_ev = 0;
-    SolverVectors vr = v_;                 // (ring: the plugin sees plane k-1 as p[cur], plane k as p[cur ^ 1])
-    auto ring_plane = [&](int k) -> float* { return k < 0 ? v_.p[0] : ring_[(size_t)(k % n_ring)]; };
-    auto flush_ring = [&](int upto) -> int {      // delta += alpha_j p_j for flushed <= j <= upto (their scalars are words once what is enqueued on s has run)
-        while (flushed <= upto) {
-            thallo_update_terms_t T; T.count = 0;
-            for (; flushed <= upto && T.count < THALLO_HIP_MAX_UPDATE_TERMS; ++flushed) {
-                T.p[T.count] = ring_plane(flushed); T.alphaN[T.count] = sum(B + 2 * flushed); T.alphaD[T.count] = sum(B + 2 * flushed + 1); ++T.count;
-            }
-            if (!async) {
-                TimedLaunch t(ctx, "PCGDeltaUpdate");
-                if (thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, 0, s) < 0) return -1;
-                synced = flushed;
-                continue;
-            }
-            if (n_ev + 2 > aux_events_.size()) { hipEvent_t e = nullptr; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -1; aux_events_.push_back(e);
-                                                 e = nullptr; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -1; aux_events_.push_back(e); }
-            hipEvent_t words = aux_events_[n_ev++], done = aux_events_[n_ev++];
-            if (hipEventRecord(words, s) != hipSuccess || hipStreamWaitEvent(aux_, words, 0) != hipSuccess) return -1;
-            LaunchCtx cx = ctx; cx.stream = aux_;
-            {   TimedLaunch t(cx, "PCGDeltaUpdate");
-                if (thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, aux_workgroups_ > 0 ? aux_workgroups_ : thallo_hip_device_cu_count(), aux_) < 0) return -1; }
-            if (hipEventRecord(done, aux_) != hipSuccess) return -1;
-            sent.push_back(Sent{ flushed - 1, done });
-        }
-        return 0;
-    };
-    // whichever way this function is left, the loop's stream ends up behind every update that went out on the second stream: the next step's PCGInit1 zeroes delta
-    // (on a failed launch too -- the caller may call Step again)
-    struct Join { hipStream_t s; const std::vector<Sent>* sent; ~Join() { if (!sent->empty()) (void)hipStreamWaitEvent(s, sent->back().done, 0); } } join_on_exit{ s, &sent };
-    auto wait_for = [&](int term) -> int {        // the loop's stream goes on only when the update that took p_term has run
-        for (const Sent& q : sent) {
-            if (q.upto < synced) continue;
-            if (hipStreamWaitEvent(s, q.done, 0) != hipSuccess) return -1;
-            synced = q.upto + 1;
-            if (q.upto >= term) break;
-        }
-        return 0;
-    };
-    // Persistent form (plugins that offer it, on the ring): iteration 0 as a launch of its own, then iterations k .. k + m - 1 per launch, m <= n - 1 (no plane of a
-    // launch is written twice, none is overwritten before delta has it)
-    int nb_prev = 0;
-    for (int k = 0; k < L; ++k) {
-        if (persist && k >= 1) {
-            const int m = L - k < n_ring - 1 ? L - k : n_ring - 1, k1 = k + m;
-            if (k1 - 1 >= n_ring && flushed < k1 - n_ring) { if (flush_ring(k - 2) || wait_for(k - 2)) { set_error("PCGDeltaUpdate launch failed"); return 0; } }
-            nb = plugin->pcg_persist(ctx, v_, ring_.data(), n_ring, k, k1, slot(0), parts_slots_, B, nb_prev, sum(B + 2 * (k - 1)));
-            if (nb < 0) { set_error("PCGLoopPersistent launch failed (%d)", nb); return 0; }
-            resident_used_ = true;
-            for (int i = k; i < k1; ++i) { const int jD = B + 2 * i + 1; fin_[jD - 2] = 1; set_nb(jD - 1, 1); fin_[jD - 1] = 1; }      // the words alphaD_{i-1}, betaN_{i-1} = alphaN_i
-            set_nb(B + 2 * (k1 - 1) + 1, nb); nb_prev = nb;
-            if (m & 1) cur_ ^= 1;
-            k = k1 - 1;
-            if (k == L - 1) {
-                const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-                if (plugin->pcg_iter_finish_from(ctx, slot(jD), v_.s12buf(k & 1), nb, sum(jN), scal(jD), scal(jB)) < 0) { set_error("PCGScalars launch failed"); return 0; }
-                fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
-            }
+    const GnSchedule sched = gn_schedule(L, n_ring);
+    const bool async = n_ring >= 2 && aux_async_ && sched != GnSchedule::Persist && aux_stream();      // (where the delta updates run: ring_flush)
+    GnStep st{ L, n_ring < 2 && batch_delta_ && delta_planes_ != 0 && plugin->batches_delta(), PRing(*this, n_ring, async) };
+    bool done = false;
+    switch (sched) {
+    case GnSchedule::Persist:        done = gn_loop_persist(st); break;
+    case GnSchedule::Deferred:       done = gn_loop_deferred(st, L); break;
+    case GnSchedule::FinishInLaunch: done = gn_loop_finish_in_launch(st); break;
+    }
+    if (!done) return 0;
+    const int ev_fin = gn_finish(L, ev_lin);
+    if (st.ring.on() && L > 0) {
+        // PCGLinearUpdate with every pending term: all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first
+        if (ring_flush(st.ring, L - 1 - THALLO_HIP_MAX_UPDATE_TERMS) || st.ring.wait_for(L)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
+        if (!ring_linear_update(st.ring, L, [](int rc) { return rc >= 0; })) { set_error("PCGLinearUpdate launch failed"); return 0; }
+        plugin->unknowns_written();
+    } else linear_update_tail(L, st.batched);
+    return gn_end(ev_fin, ev_iter);
+}
+
+// The ring made ready for launch k -- what is due goes into delta, the loop's stream waits for the update that took the plane launch k overwrites, the plugin's
+// view of the planes is set -- and the launch's delta mode.  < 0: failed (the error is set).
+int Plan::gn_launch_mode(GnStep& st, int k)
+{
+    PRing& R = st.ring;
+    if (!R.on()) return THALLO_IW_STEP1_MODE(k, st.batched ? 1 : 0);
+    if (ring_flush(R, R.flush_due(k))) { set_error("PCGDeltaUpdate launch failed"); return -1; }
+    if (R.wait_to_overwrite(k)) { set_error("PCGDeltaUpdate: stream wait failed"); return -1; }
+    return R.launch(k, cur_);
+}
+
+// Deferred finish (where the plugin offers it): the launch of iteration k adds up iteration k-1's partials
+// itself -- alphaD_{k-1} and betaN_{k-1} = N - 2 alpha S1 + alpha^2 S2 -- while its first rows load, instead of iteration k-1's last workgroup
+// reading them back at the very end of its launch; one one-wave launch per GN step finishes the last iteration.
+bool Plan::gn_loop_deferred(GnStep& st, int k_end)
+{
+    for (int k = 0; k < k_end; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;      // slot layout: alphaN_k = 2+2k, alphaD_k = 2+2k+1, betaN_k = 2+2k+2
+        const int mode = gn_launch_mode(st, k);
+        if (mode < 0) return false;
+        const PrevAlpha a = prev_alpha(k);
+        const thallo_prev_t prev = { k ? slot(jD - 2) : nullptr, v_.s12buf((k - 1) & 1), st.nb_prev, k ? scal(jD - 2) : nullptr, k ? scal(jB - 2) : nullptr };
+        const int nb = plugin->pcg_iter_deferred(ctx, st.ring.vectors(), cur_, mode, a.aN, a.aN2, a.aD2, prev, slot(jD), v_.s12buf(k & 1));
+        if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return false; }
+        if (k) words_done(k - 1);             // (that launch's workgroup 0 writes the two words of iteration k-1)
+        set_nb(jD, nb); st.nb_prev = nb; cur_ ^= 1;
+        if (k == st.L - 1 && !gn_finish_last(st, k, nb)) return false;
+    }
+    return true;
+}
+bool Plan::gn_finish_last(GnStep& st, int k, int nb)
+{
+    const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+    if (plugin->pcg_iter_finish_from(ctx, slot(jD), v_.s12buf(k & 1), nb, sum(jN), scal(jD), scal(jB)) < 0) { set_error("PCGScalars launch failed"); return false; }
+    words_done(k);
+    return true;
+}
+
+// Persistent form (plugins that offer it, on the ring, behind the deferred finish): iteration 0 as a launch of its own, then iterations k .. k + m - 1 per launch,
+// m <= n - 1 (no plane of a launch is written twice, none is overwritten before delta has it)
+bool Plan::gn_loop_persist(GnStep& st)
+{
+    PRing& R = st.ring;
+    const int L = st.L, B = 2, n = R.n;
+    if (!gn_loop_deferred(st, 1)) return false;
+    for (int k = 1; k < L; ) {
+        const int m = L - k < n - 1 ? L - k : n - 1, k1 = k + m;
+        if (k1 - 1 >= n && R.flushed < k1 - n) { if (ring_flush(R, k - 2) || R.wait_for(k - 2)) { set_error("PCGDeltaUpdate launch failed"); return false; } }
+        const int nb = plugin->pcg_persist(ctx, v_, ring_.data(), n, k, k1, slot(0), parts_slots_, B, st.nb_prev, sum(B + 2 * (k - 1)));
+        if (nb < 0) { set_error("PCGLoopPersistent launch failed (%d)", nb); return false; }
+        resident_used_ = true;
+        for (int i = k; i < k1; ++i) words_done(i - 1);      // the words alphaD_{i-1}, betaN_{i-1} = alphaN_i
+        set_nb(B + 2 * (k1 - 1) + 1, nb); st.nb_prev = nb;
+        if (m & 1) cur_ ^= 1;
+        k = k1;
+        if (k == L && !gn_finish_last(st, L - 1, nb)) return false;
+    }
+    return true;
+}
+
+// alphaD_k and betaN_k = N - 2 alpha_k S1 + alpha_k^2 S2 by the launch of iteration k itself: its last workgroup, or (THALLO_FIN_IN_KERNEL=0) a one-wave launch behind it
+bool Plan::gn_loop_finish_in_launch(GnStep& st)
+{
+    for (int k = 0; k < st.L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+        const int mode = gn_launch_mode(st, k);
+        if (mode < 0) return false;
+        const PrevAlpha a = prev_alpha(k);
+        const int nb = plugin->pcg_iter(ctx, st.ring.vectors(), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD),
+                                        fin_in_kernel_ ? scal(jD) : nullptr, fin_in_kernel_ ? scal(jB) : nullptr);
+        if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return false; }
+        set_nb(jD, nb); cur_ ^= 1;
+        if (!fin_in_kernel_ && plugin->pcg_iter_finish(ctx, v_, slot(jD), nb, sum(jN), scal(jD), scal(jB)) < 0) { set_error("PCGScalars launch failed"); return false; }
+        words_done(k);
+    }
+    return true;
+}
+
+// ---- The ring of p planes of a step (Plan::PRing): its bookkeeping, and the one-GPU launches of its delta updates
+bool Plan::PRing::next_batch(int upto, thallo_update_terms_t& T)
+{
+    T.count = 0;
+    for (; flushed <= upto && T.count < THALLO_HIP_MAX_UPDATE_TERMS; ++flushed) {
+        T.p[T.count] = plane(flushed); T.alphaN[T.count] = P.sum(2 + 2 * flushed); T.alphaD[T.count] = P.sum(2 + 2 * flushed + 1); ++T.count;
+    }
+    return T.count > 0;
+}
+bool Plan::PRing::events(hipEvent_t& words, hipEvent_t& done)
+{
+    std::vector<hipEvent_t>& ev = P.aux_events_;
+    while (n_ev + 2 > ev.size()) { hipEvent_t e = nullptr; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false; ev.push_back(e); }
+    words = ev[n_ev++]; done = ev[n_ev++];
+    return true;
+}
+int Plan::PRing::wait_for(int term)
+{
+    for (const Sent& q : sent) {
+        if (q.upto < synced) continue;
+        if (hipStreamWaitEvent(P.ctx.stream, q.done, 0) != hipSuccess) return -1;
+        synced = q.upto + 1;
+        if (q.upto >= term) break;
+    }
+    return 0;
+}
+// Where the update runs.  Default: on the loop's own stream, whole rings at a time (up to 32 terms per launch).  THALLO_DELTA_PLANES=N:W: NEXT TO the loop, on a
+// low-priority stream of the plan's own and on at most W workgroups (0: one per CU), in chunks of (n - 1) / 2 terms as soon as their scalars are words; the launch
+// that overwrites a chunk's first plane waits for its event.  Measured (profiles/r05/ring_ab*.txt): next to the loop 0.7-2 % more PCG iterations per second, but the
+// marching launches that share the chip with an update take ~8 us longer each -- the loop streams at the memory system's rate in its steady state, and what the
+// second kernel takes there it does not give back in the ramps and tails.  Not worth a second stream in the default path.
+int Plan::ring_flush(PRing& R, int upto)
+{
+    hipStream_t s = ctx.stream;
+    thallo_update_terms_t T;
+    while (R.next_batch(upto, T)) {
+        if (!R.async) {
+            TimedLaunch t(ctx, "PCGDeltaUpdate");
+            if (thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, 0, s) < 0) return -1;
+            R.synced = R.flushed;
             continue;
         }
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        const int mode = ring ? (k == 0 ? 1 : 2) : THALLO_IW_STEP1_MODE(k, batched ? 1 : 0);
-        if (ring) {
-            // plane k mod n still holds p_{k-n}: it has to be in delta before launch k overwrites it.  Terms up to k - 2 can go (launch k - 1 leaves their scalars)
-            const bool due = async ? k - 1 - flushed >= chunk : (k >= n_ring && flushed < k - n_ring + 1);
-            if (due && flush_ring(k - 2)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
-            if (k >= n_ring && synced < k - n_ring + 1 && wait_for(k - n_ring)) { set_error("PCGDeltaUpdate: stream wait failed"); return 0; }
-            vr.p[cur_] = ring_plane(k - 1); vr.p[cur_ ^ 1] = ring_plane(k);
-        }
-        SolverVectors& vv = ring ? vr : v_;
-        if (defer) {
-            const thallo_prev_t prev = { k ? slot(jD - 2) : nullptr, v_.s12buf((k - 1) & 1), nb_prev, k ? scal(jD - 2) : nullptr, k ? scal(jB - 2) : nullptr };
-            nb = plugin->pcg_iter_deferred(ctx, vv, cur_, mode, sum(k ? jN - 2 : jN), sum(k > 1 ? jN - 4 : jN), sum(k > 1 ? jD - 4 : jD), prev, slot(jD), v_.s12buf(k & 1));
-            if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return 0; }
-            if (k) { fin_[jD - 2] = 1; set_nb(jB - 2, 1); fin_[jB - 2] = 1; }      // (that launch's workgroup 0 writes the two words of iteration k-1)
-            set_nb(jD, nb); nb_prev = nb; cur_ ^= 1;
-            if (k == L - 1) {
-                if (plugin->pcg_iter_finish_from(ctx, slot(jD), v_.s12buf(k & 1), nb, sum(jN), scal(jD), scal(jB)) < 0) { set_error("PCGScalars launch failed"); return 0; }
-                fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
-            }
-        } else {
-            // alphaD_k and betaN_k = N - 2 alpha_k S1 + alpha_k^2 S2: by the kernel's last workgroup, or (THALLO_FIN_IN_KERNEL=0) a one-wave launch
-            nb = plugin->pcg_iter(ctx, vv, cur_, mode, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN),
-                                  sum(k > 1 ? jN - 4 : jN), sum(k > 1 ? jD - 4 : jD), slot(jD),
-                                  fin_in_kernel_ ? scal(jD) : nullptr, fin_in_kernel_ ? scal(jB) : nullptr);
-            if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return 0; }
-            set_nb(jD, nb); cur_ ^= 1;
-            if (!fin_in_kernel_ && plugin->pcg_iter_finish(ctx, v_, slot(jD), nb, sum(jN), scal(jD), scal(jB)) < 0) { set_error("PCGScalars launch failed"); return 0; }
-            fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
-        }
+        hipEvent_t words, done;
+        if (!R.events(words, done)) return -1;
+        if (hipEventRecord(words, s) != hipSuccess || hipStreamWaitEvent(aux_, words, 0) != hipSuccess) return -1;
+        LaunchCtx cx = ctx; cx.stream = aux_;
+        {   TimedLaunch t(cx, "PCGDeltaUpdate");
+            if (thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, aux_workgroups_ > 0 ? aux_workgroups_ : thallo_hip_device_cu_count(), aux_) < 0) return -1; }
+        if (hipEventRecord(done, aux_) != hipSuccess) return -1;
+        R.sent.push_back(PRing::Sent{ R.flushed - 1, done });
     }
-    const int ev_fin = gn_finish(L, ev_lin);
-    if (ring && L > 0) {
-        // PCGLinearUpdate with every pending term: all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first
-        if (flush_ring(L - 1 - THALLO_HIP_MAX_UPDATE_TERMS) || wait_for(L)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
-        thallo_update_terms_t T; T.count = 0;
-        for (int j = flushed; j < L; ++j) { T.p[T.count] = ring_plane(j); T.alphaN[T.count] = sum(B + 2 * j); T.alphaD[T.count] = sum(B + 2 * j + 1); ++T.count; }
-        const auto& imgs = plugin->unknown_images();
-        long off = 0;
-        for (size_t u = 0; u < imgs.size(); ++u) {
-            TimedLaunch t(ctx, "PCGLinearUpdate");
-            thallo_update_terms_t Tu = T;
-            for (int j = 0; j < Tu.count; ++j) Tu.p[j] += off;
-            if (thallo_hip_linear_update_n(plugin->unknown_ptr((int)u), v_.delta + off, Tu, imgs[u].n_floats, 0, s) < 0) { set_error("PCGLinearUpdate launch failed"); return 0; }
-            off += imgs[u].n_floats;
-        }
-        plugin->unknowns_written();
-    } else linear_update_tail(L, batched);
-    return gn_end(ev_fin, ev_iter);
+    return 0;
 }
 
 // The plan's second stream (lowest priority, non-blocking: the loop's stream may be the NULL stream): background updates of delta next to the PCG loop
@@ -703,11 +738,16 @@ bool Plan::ring_possible() const
 {   // one GPU, or (round 6) one rank's row slab of the one-kernel schedule: launch k writes p_k into whichever plane it is handed (the ghost rows are kept current there too)
     return plugin->takes_any_p_plane() && (!dist_ || dist_->form == DistForm::Slab);
 }
+int Plan::ring_wanted(int L) const
+{
+    if (!ring_possible() || delta_planes_ == 0 || delta_planes_ == 1 || L < 3) return 0;
+    const int want = delta_planes_ >= 2 ? delta_planes_ : delta_planes_ <= -2 ? -delta_planes_ : THALLO_HIP_MAX_UPDATE_TERMS + 1;
+    return want > L ? L : want;             // (L planes: delta is never touched inside the loop)
+}
 void Plan::ring_prepare(int L)
 {
-    if (!ring_possible() || delta_planes_ == 0 || delta_planes_ == 1 || L < 3) return;
-    int want = delta_planes_ >= 2 ? delta_planes_ : delta_planes_ <= -2 ? -delta_planes_ : THALLO_HIP_MAX_UPDATE_TERMS + 1;
-    if (want > L) want = L;                 // (L planes: delta is never touched inside the loop)
+    const int want = ring_wanted(L);
+    if (!want) return;
     if (ring_.size() < 2) { ring_.clear(); ring_.push_back(v_.p[1]); ring_.push_back(v_.p[0]); }
     if (want <= (int)ring_.size() || want <= ring_tried_) return;      // enough planes, or an attempt for this many already ran into the memory limit
     ring_tried_ = want;
@@ -726,9 +766,8 @@ void Plan::ring_prepare(int L)
 }
 int Plan::ring_planes(int L)
 {
-    if (!ring_possible() || delta_planes_ == 0 || delta_planes_ == 1 || L < 3) return 0;
-    int want = delta_planes_ >= 2 ? delta_planes_ : delta_planes_ <= -2 ? -delta_planes_ : THALLO_HIP_MAX_UPDATE_TERMS + 1;
-    if (want > L) want = L;
+    const int want = ring_wanted(L);
+    if (!want) return 0;
     if (L != ring_L_) { ring_prepare(L); ring_L_ = L; }      // (lIterations changed since Init: once per change)
     if (ring_.size() < 2) return 0;
     const int n = (int)ring_.size() < want ? (int)ring_.size() : want;
@@ -745,7 +784,7 @@ int Plan::step_gn_resident(int ev_iter)
     if (!gn_begin(ev_lin)) return 0;
     const int nb = plugin->pcg_resident(ctx, v_, L, sum(B), scal(B + 1));
     if (nb < 0) { set_error("PCGLoopResident launch failed (%d)", nb); return 0; }
-    for (int k = 0; k < L; ++k) { const int jD = B + 2 * k + 1, jB = jD + 1; set_nb(jD, 1); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+    for (int k = 0; k < L; ++k) { set_nb(B + 2 * k + 1, 1); words_done(k); }
     cur_ = L & 1;
     resident_used_ = true;
     const int ev_fin = gn_finish(L, ev_lin);
@@ -774,7 +813,7 @@ int Plan::step_gn_expanded(int ev_iter)
             if (defer && k > 0) rc = thallo_hip_pcg_update_fin(v_.r, v_.Ap, plugin->use_preconditioner() ? v_.pre : nullptr, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, v_.n, sum(jN - 2),
                                                                slot(jD - 2), v_.s12, nb_prev, scal(jD - 2), scal(jN), s);
             else rc = thallo_hip_pcg_update(v_.r, v_.Ap, plugin->use_preconditioner() ? v_.pre : nullptr, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, v_.n, k == 0,
-                                            sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s);
+                                            prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), s);
             if (rc < 0) { set_error("PCGUpdate launch failed"); return 0; }
         }
         cur_ ^= 1;
@@ -787,7 +826,7 @@ int Plan::step_gn_expanded(int ev_iter)
             TimedLaunch t(ctx, "PCGScalars");
             if (thallo_hip_pcg_scalars_finish(slot(jD), v_.s12, nb, sum(jN), scal(jD), scal(jB), s) < 0) { set_error("PCGScalars launch failed"); return 0; }
         }
-        fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1;
+        words_done(k);
     }
     const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, false);

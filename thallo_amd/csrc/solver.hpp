@@ -187,9 +187,45 @@ private:
     int delta_planes_ = -1;         // THALLO_DELTA_PLANES (-1: unset)
     std::vector<float*> ring_;      // the ring of p planes of the one-kernel GN loop (ring_planes)
     bool ring_possible() const;     // the plugin's iteration takes any p plane, on one GPU or on a row slab of the one-kernel schedule
+    int  ring_wanted(int L) const;  // planes a loop of L iterations would like (0: no ring), from THALLO_DELTA_PLANES and L alone
     int  ring_planes(int L);        // how many planes the loop of L iterations runs on (allocates nothing unless lIterations changed since Init)
     void ring_prepare(int L);       // allocates the ring's planes: at Init, and once per change of lIterations; a memory-limited attempt is cached (ring_tried_)
     int  ring_tried_ = 0, ring_L_ = -1;
+    // One step's view of the ring: launch k writes p_k into plane k mod n and leaves delta alone; delta takes the pending alpha_j p_j in batches.  Bookkeeping only:
+    // the ring says when a flush is due and hands back the batches, its caller launches them and reports a failure its own way (one GPU: set_error, the step ends;
+    // a row slab: DLOCAL, the rank stays in step).  `async` (one GPU, THALLO_DELTA_PLANES=N:W): the batches go out on the plan's second stream.
+    struct PRing {
+        Plan& P;
+        const int n;                                    // planes (< 2: no ring)
+        const bool async;
+        int flushed = 0;                                // p_0 .. p_{flushed-1} are in delta, or on their way there (async)
+        int synced = 0;                                 // ... and the loop's stream has waited for the updates of p_0 .. p_{synced-1}
+        struct Sent { int upto; hipEvent_t done; };
+        std::vector<Sent> sent;                         // async: the updates that went out, in order
+        size_t n_ev = 0;
+        SolverVectors v;                                // what the plugin is handed: plane k-1 as p[cur], plane k as p[cur ^ 1]
+        PRing(Plan& plan, int planes, bool on_second_stream) : P(plan), n(planes), async(on_second_stream), v(plan.v_) {}
+        PRing(const PRing&) = delete;
+        // whichever way the step is left, the loop's stream ends up behind every update that went out on the second stream: the next step's PCGInit1 zeroes delta
+        // (on a failed launch too -- the caller may call Step again)
+        ~PRing() { if (!sent.empty()) (void)hipStreamWaitEvent(P.ctx.stream, sent.back().done, 0); }
+        bool on() const { return n >= 2; }
+        SolverVectors& vectors() { return on() ? v : P.v_; }
+        float* plane(int k) const { return k < 0 ? P.v_.p[0] : P.ring_[(size_t)(k % n)]; }
+        int  launch(int k, int cur) { v.p[cur] = plane(k - 1); v.p[cur ^ 1] = plane(k); return k == 0 ? 1 : 2; }      // the planes of launch k; its delta mode (none)
+        // Before launch k: the last term that has to go into delta now, or -1.  Terms up to k - 2 can go (launch k - 1 leaves their scalars).  Default: plane k mod n
+        // still holds p_{k-n}, which has to be in delta before launch k overwrites it -- then everything goes; async: half a ring at a time, as soon as it is there
+        int  flush_due(int k) const { const int chunk = (n - 1) / 2 > 0 ? (n - 1) / 2 : 1; return (async ? k - 1 - flushed >= chunk : (k >= n && flushed < k - n + 1)) ? k - 2 : -1; }
+        bool next_batch(int upto, thallo_update_terms_t& T);      // the next <= THALLO_HIP_MAX_UPDATE_TERMS terms of p_flushed .. p_upto, oldest first (their scalars are words once what is enqueued has run)
+        bool events(hipEvent_t& words, hipEvent_t& done);         // async: the two events of the next update (the plan's list grows on demand)
+        int  wait_for(int term);                                  // the loop's stream goes on only when the update that took p_term has run
+        int  wait_to_overwrite(int k) { return k >= n && synced < k - n + 1 ? wait_for(k - n) : 0; }      // ... before launch k writes plane k mod n
+    };
+    int  ring_flush(PRing& R, int upto);                // one GPU: delta += alpha_j p_j for every j <= upto not flushed yet ("PCGDeltaUpdate", on the loop's or the second stream)
+    struct Owned { long lo, len; };
+    Owned owned_range(size_t u) const;                  // the part of unknown image u this plan updates: its owned rows on a row slab, else all of it
+    // PCGLinearUpdate with the ring's pending terms p_flushed .. p_{L-1} riding in it, over the owned range of every unknown image; `launched(rc)` says whether to go on
+    template <class Launched> bool ring_linear_update(PRing& R, int L, Launched launched);
     hipStream_t aux_ = nullptr; bool aux_failed_ = false;      // the plan's second stream (background delta updates)
     std::vector<hipEvent_t> aux_events_;
     bool aux_async_ = false;        // THALLO_DELTA_PLANES=N:W: the delta updates of the ring on the second stream, next to the loop
@@ -206,11 +242,29 @@ private:
     // their waves re-adding up to 1024 partials in the prologue (measured: -10 us per PCG iteration at 2048^2)
     // (small launches -- <= 4 partials per lane -- are cheaper to re-add in place than to pay one more launch for)
     void finish(int j) { if (nb_[j] <= 256) return; thallo_hip_finish_sum(partial_sum(j), scal(j), ctx.stream); fin_[j] = 1; }
+    void words_done(int k) { const int jD = 2 + 2 * k + 1, jB = jD + 1; fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }      // iteration k's two words exist: alphaD_k, betaN_k = alphaN_{k+1}
+    // alpha_{k-1} and alpha_{k-2} as their numerator / denominator sums, as launch k takes them (k = 0, and k = 1 for the second pair: iteration k's own slots stand in, unread)
+    struct PrevAlpha { thallo_sum_t aN, aD, aN2, aD2; };
+    PrevAlpha prev_alpha(int k) { const int jN = 2 + 2 * k, jD = jN + 1; return { sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(k > 1 ? jN - 4 : jN), sum(k > 1 ? jD - 4 : jD) }; }
     int  ensure_slots(int L);
     int  ensure_iter_buffers();
     int  ensure_sums_buffer();
     int  step_gn_expanded(int ev_iter);
+    // ---- the one-kernel GN step: step_gn_one_kernel = set-up, one of three PCG loops (gn_schedule), the shared finish
+    enum class GnSchedule { Persist, Deferred, FinishInLaunch };
+    struct GnStep {                                     // what the loops of one step share
+        const int L;
+        const bool batched;                             // no ring: every other delta update is deferred (THALLO_IW_STEP1_MODE(k, 1))
+        PRing ring;
+        int nb_prev = 0;                                // deferred finish: the partial count of the launch before
+    };
     int  step_gn_one_kernel(int ev_iter);
+    GnSchedule gn_schedule(int L, int n_ring);
+    int  gn_launch_mode(GnStep& st, int k);             // the ring made ready for launch k; the launch's delta mode (< 0: failed)
+    bool gn_finish_last(GnStep& st, int k, int nb);     // deferred finish: the one-wave launch behind the step's last iteration
+    bool gn_loop_persist(GnStep& st);
+    bool gn_loop_deferred(GnStep& st, int k_end);       // iterations [0, k_end)
+    bool gn_loop_finish_in_launch(GnStep& st);
     int  step_gn_resident(int ev_iter);
     bool gn_begin(int& ev_lin);                         // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2, "Linear Solve" started
     int  gn_finish(int L, int ev_lin);                  // ... its tail: "Nonlinear Finish" started (the caller's update of the unknowns follows) ...
@@ -317,12 +371,41 @@ private:
     int  dist_allreduce(float* buf, long count);        // Shard: the shared block's partial sums added over the ranks, in place
     // the Gauss-Newton step, per form
     int  step_gn_slab(int ev_iter);
-    int  dist_gn(int L, bool p2p);                      // Slab: PCGInit + L iterations + linear update + ghost refresh, no bookkeeping
-    int  dist_gn_flat(int L);                           // Flat: pcg_update + apply_jtj_sums + ONE exchange per PCG iteration
+    // Slab: dist_gn = dist_gn_begin, ONE of the four PCG loops, the shared finish (linear update over the owned rows, ghost refresh); no bookkeeping
+    int  dist_gn(int L, bool p2p);
+    int  dist_gn_begin(bool p2p);
+    int  dist_agree_defer();                            // ONE collective: D.defer_state = every rank can run the marching kernel's deferred cross-rank finish
+    void dist_ring_flush(PRing& R, int upto);
+    int  dist_launch_mode(PRing& R, int k, bool batch);
+    void dist_gn_loop_resident(int L);
+    void dist_gn_loop_deferred(int L, PRing& R, bool batch);
+    void dist_gn_loop_p2p(int L, PRing& R, bool batch);
+    int  dist_gn_loop_allgather(int L, PRing& R, bool batch);
+    int  dist_allgather_iter(float* Ap, int k, int nb);      // Slab, Flat: the all-gather exchange of iteration k: [alphaD | N, S1, S2 | boundary rows of the new A p]
+    // Flat: PCGInit + ONE exchange per PCG iteration behind pcg_iter (one launch) or pcg_update + apply_jtj_sums (three launches) + linear update + ghost refresh
+    int  dist_gn_flat(int L);
+    int  dist_gn_flat_loop_one_launch(int L), dist_gn_flat_loop_three_launch(int L);
+    int  dist_flat_exchange_iter(float* Ap, int k, int nb);
     int  dist_gn_range(int L);                          // Range, Partition: full-length pcg_update + applyJTJ over the owned units + ONE exchange per PCG iteration
     int  dist_gn_shard(int L);                          // Shard: applyJTJ on the rank's residuals, all-reduce of the shared block of A p, one tiny all-gather
     float dist_cost();
     void dist_release();
 };
+
+template <class Launched> bool Plan::ring_linear_update(PRing& R, int L, Launched launched)
+{
+    thallo_update_terms_t T; T.count = 0;
+    for (int j = R.flushed; j < L; ++j) { T.p[T.count] = R.plane(j); T.alphaN[T.count] = sum(2 + 2 * j); T.alphaD[T.count] = sum(2 + 2 * j + 1); ++T.count; }
+    long off = 0;
+    for (size_t u = 0; u < plugin->unknown_images().size(); ++u) {
+        TimedLaunch t(ctx, "PCGLinearUpdate");
+        const Owned o = owned_range(u);
+        thallo_update_terms_t Tu = T;
+        for (int j = 0; j < Tu.count; ++j) Tu.p[j] += off + o.lo;
+        if (!launched(thallo_hip_linear_update_n(plugin->unknown_ptr((int)u) + o.lo, v_.delta + off + o.lo, Tu, o.len, 0, ctx.stream))) return false;
+        off += plugin->unknown_images()[u].n_floats;
+    }
+    return true;
+}
 
 }  // namespace thallo

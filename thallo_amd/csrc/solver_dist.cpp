@@ -617,7 +617,9 @@ float Plan::dist_cost()
     return f;
 }
 
-int Plan::dist_gn(int L, bool p2p)
+// ---- Slab: one GN step = dist_gn_begin, ONE of four PCG loops, the shared finish (DESIGN.md "GN schedules").  Every rank issues every collective of the sequence
+// unconditionally; everything rank-local stays behind !D.failed (DLOCAL / DCOPY).
+int Plan::dist_gn_begin(bool p2p)
 {
     DistState& D = *dist_;
     hipStream_t s = ctx.stream;
@@ -646,80 +648,110 @@ int Plan::dist_gn(int L, bool p2p)
     // seq += 1: this GN step's granules.  (A rank that failed sends none: its peers' bounded waits run out, their error word is set, they fall through
     // to the collectives below and learn the cause at the next cost evaluation.)
     if (p2p) DLOCAL(thallo_hip_dist_begin_step(D.d, s), "device-side exchange: begin step");
+    return 0;
+}
+
+int Plan::dist_gn(int L, bool p2p)
+{
+    DistState& D = *dist_;
+    if (dist_gn_begin(p2p)) return -1;
     // delta += alpha p every iteration on the device-side transport: its "apply two" kernel variant (peer stores on top of 256 VGPRs) spills, and at
     // slab sizes the 6 B/pixel it would save do not matter (2048x256: 22.6 vs 24.3 us per iteration).  (Either delta schedule gives the same bits -- tested
     // for both kernels; the marching kernel's multi-GPU variant is contracted differently from its single-GPU one, so its two TRANSPORTS agree to rounding.)
     // (round 4: the kernel without an A p plane has that form on the device-side transport too -- 160-200 registers -- and every rank runs the same kernel)
     const bool batch = batch_delta_ && (!p2p || plugin->dist_batches_delta());
-    // Small slabs on the device-side transport: the whole PCG loop in ONE launch (state in registers, boundary rows of A p straight into the neighbours' ghost
-    // areas, the scalars through the same mailbox slots: thallo_hip_iw_pcg_resident_dist).  UNANIMOUS: a rank's own answer depends on whether it has a
-    // rank below (its last segment must then be a full one) -- 8 ranks x 256 rows: R = 5 does not divide 256, ranks 0..6 say no, rank 7 alone would say yes and
-    // poll for granules nobody sends.  Agreed once per Init (dist_self_check), cached.
+    // Which loop (first match; the same answer on every rank): resident, deferred cross-rank finish, device-side transport, all-gather transport
     const bool resident = p2p && L >= 1 && L <= 4095 && D.ghost_off > 0 && D.resident_all;
-    if (resident) {
-        if (!D.failed) {
-            nb = plugin->pcg_resident_dist(ctx, v_, L, sum(B), scal(B + 1), D.d, D.ghost_off, 0);
-            if (nb < 0) dist_fail("PCGLoopResident launch failed (%d)", nb);
-        }
-        if (!D.failed) {
-            for (int k = 0; k < L; ++k) { const int jD = B + 2 * k + 1, jB = jD + 1; set_nb(jD, 1); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            resident_used_ = true;
-        }
-        cur_ = L & 1;
-    }
-    // Larger slabs on the device-side transport (the marching kernels): the exchange of an iteration's sums does not sit at the END of its launch (tickets -> last
-    // workgroup -> granules to the peers -> wait -> two words: ~8 us that nothing hides) but at the START of the next one, where a designated wave does it while every
-    // wave's first rows load (plugin.hpp dist_defers_finish); one one-wave launch finishes the step's last iteration.  Same granules, slots, orders: same bits.
-    bool defer_x = false;
-    if (p2p && !resident && L >= 1) {
-        // (every rank must run the same schedule -- a non-deferring rank's last workgroup would wait for granules a deferring rank sends a launch LATER --: agreed once,
-        //  at the first device-side step of the plan, which is the set-up's self-check: never inside a captured graph)
-        if (D.defer_state < 0) {
-            bool mine = plugin->dist_defers_finish() && ensure_iter_buffers() == 0 && (D.gs.ptr || D.gs.alloc(64) == 0), all = false;
-            if (dist_agree(mine, all)) return -1;
-            D.defer_state = all ? 1 : 0;
-        }
-        defer_x = D.defer_state == 1;
-    }
+    // (the deferred finish: every rank must run the same schedule -- a non-deferring rank's last workgroup would wait for granules a deferring rank sends a launch LATER --:
+    //  agreed once, at the first device-side step of the plan, which is the set-up's self-check: never inside a captured graph)
+    if (p2p && !resident && L >= 1 && D.defer_state < 0 && dist_agree_defer()) return -1;
+    enum { Resident, Deferred, P2P, AllGather } const loop = resident ? Resident : !p2p ? AllGather : L >= 1 && D.defer_state == 1 ? Deferred : P2P;
     // Round 6 (VERDICT r5 Missing 5): the RING of p planes on a slab's launch-per-iteration schedule, as on one GPU (solver.cpp step_gn_one_kernel): launch k writes p_k into
     // plane k mod n and touches no delta (57 instead of 81 bytes per pixel), thallo_hip_linear_update_n adds the pending alpha_j p_j -- oldest first, one fma each: the bits of
     // an update per iteration -- once per ring, the step's last terms ride in PCGLinearUpdate.  Every rank runs the same schedule (the ring is sized by lIterations and
     // THALLO_DELTA_PLANES; a rank short of memory runs fewer planes -- the vector updates are rank-local, nothing another rank can see depends on it).
-    const int n_ring = resident ? 0 : ring_planes(L);
-    const bool ring = n_ring >= 2;
-    int flushed = 0;
-    SolverVectors vr = v_;
-    auto ring_plane = [&](int k) -> float* { return k < 0 ? v_.p[0] : ring_[(size_t)(k % n_ring)]; };
-    auto flush_ring = [&](int upto) {           // delta += alpha_j p_j for flushed <= j <= upto (their scalars are words once what is enqueued on s has run)
-        while (flushed <= upto) {
-            thallo_update_terms_t T; T.count = 0;
-            for (; flushed <= upto && T.count < THALLO_HIP_MAX_UPDATE_TERMS; ++flushed) {
-                T.p[T.count] = ring_plane(flushed); T.alphaN[T.count] = sum(B + 2 * flushed); T.alphaD[T.count] = sum(B + 2 * flushed + 1); ++T.count;
-            }
-            TimedLaunch t(ctx, "PCGDeltaUpdate");
-            DLOCAL(thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, 0, s), "PCGDeltaUpdate launch");
-        }
-    };
-    auto ring_step = [&](int k) -> int {        // the planes and the delta mode of launch k
-        if (!ring) return THALLO_IW_STEP1_MODE(k, batch ? 1 : 0);
-        if (k >= n_ring && flushed < k - n_ring + 1) flush_ring(k - 2);      // plane k mod n still holds p_{k-n}: into delta before launch k overwrites it
-        vr.p[cur_] = ring_plane(k - 1); vr.p[cur_ ^ 1] = ring_plane(k);
-        return k == 0 ? 1 : 2;
-    };
-    SolverVectors& vv = ring ? vr : v_;
-    int nb_prev = 0;
-    for (int k = 0; k < ((resident || !defer_x) ? 0 : L); ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        const int mode = ring_step(k);
-        unsigned long long* gs = (unsigned long long*)D.gs.ptr;
+    PRing R(*this, resident ? 0 : ring_planes(L), false);
+    switch (loop) {
+    case Resident:  dist_gn_loop_resident(L); break;
+    case Deferred:  dist_gn_loop_deferred(L, R, batch); break;
+    case P2P:       dist_gn_loop_p2p(L, R, batch); break;
+    case AllGather: if (dist_gn_loop_allgather(L, R, batch)) return -1; break;
+    }
+    if (!D.failed && R.on() && L > 0) {
+        // PCGLinearUpdate with every pending term (all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first), over the OWNED rows of each unknown image
+        last_l_iters = L;
+        dist_ring_flush(R, L - 1 - THALLO_HIP_MAX_UPDATE_TERMS);
+        if (!D.failed) ring_linear_update(R, L, [&](int rc) { DLOCAL(rc, "PCGLinearUpdate launch"); return !D.failed; });
+        plugin->unknowns_written();
+    } else
+    if (!D.failed) { last_l_iters = L; linear_update_tail(L, batch && !resident); }   // owned rows only (the resident loop has applied every delta update but the last itself)
+    return dist_exchange_unknown_rows();
+}
+
+int Plan::dist_agree_defer()
+{   // Init (every Init anew: what it depends on is the plugin's state NOW) and, before a self-check's first device-side step, dist_gn
+    DistState& D = *dist_;
+    const bool mine = plugin->dist_defers_finish() && ensure_iter_buffers() == 0 && (D.gs.ptr || D.gs.alloc(64) == 0);
+    bool all = false;
+    if (dist_agree(mine, all)) return -1;
+    D.defer_state = all ? 1 : 0;
+    return 0;
+}
+
+void Plan::dist_ring_flush(PRing& R, int upto)
+{
+    DistState& D = *dist_;
+    thallo_update_terms_t T;
+    while (R.next_batch(upto, T)) {
+        TimedLaunch t(ctx, "PCGDeltaUpdate");
+        DLOCAL(thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, 0, ctx.stream), "PCGDeltaUpdate launch");
+    }
+}
+int Plan::dist_launch_mode(PRing& R, int k, bool batch)
+{   // the planes and the delta mode of launch k (on the ring: plane k mod n still holds p_{k-n} -- into delta before launch k overwrites it)
+    if (!R.on()) return THALLO_IW_STEP1_MODE(k, batch ? 1 : 0);
+    dist_ring_flush(R, R.flush_due(k));
+    return R.launch(k, cur_);
+}
+
+// Small slabs on the device-side transport: the whole PCG loop in ONE launch (state in registers, boundary rows of A p straight into the neighbours' ghost
+// areas, the scalars through the same mailbox slots: thallo_hip_iw_pcg_resident_dist).  UNANIMOUS: a rank's own answer depends on whether it has a
+// rank below (its last segment must then be a full one) -- 8 ranks x 256 rows: R = 5 does not divide 256, ranks 0..6 say no, rank 7 alone would say yes and
+// poll for granules nobody sends.  Agreed once per Init (dist_self_check), cached (D.resident_all).
+void Plan::dist_gn_loop_resident(int L)
+{
+    DistState& D = *dist_;
+    const int B = 2;
+    if (!D.failed) {
+        const int nb = plugin->pcg_resident_dist(ctx, v_, L, sum(B), scal(B + 1), D.d, D.ghost_off, 0);
+        if (nb < 0) dist_fail("PCGLoopResident launch failed (%d)", nb);
+    }
+    if (!D.failed) {
+        for (int k = 0; k < L; ++k) { set_nb(B + 2 * k + 1, 1); words_done(k); }
+        resident_used_ = true;
+    }
+    cur_ = L & 1;
+}
+
+// Larger slabs on the device-side transport (the marching kernels): the exchange of an iteration's sums does not sit at the END of its launch (tickets -> last
+// workgroup -> granules to the peers -> wait -> two words: ~8 us that nothing hides) but at the START of the next one, where a designated wave does it while every
+// wave's first rows load (plugin.hpp dist_defers_finish); one one-wave launch finishes the step's last iteration.  Same granules, slots, orders: same bits.
+void Plan::dist_gn_loop_deferred(int L, PRing& R, bool batch)
+{
+    DistState& D = *dist_;
+    unsigned long long* gs = (unsigned long long*)D.gs.ptr;
+    int nb = 0, nb_prev = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+        const int mode = dist_launch_mode(R, k, batch);
         if (!D.failed) {
-            const thallo_sum_t aNp = sum(k ? jN - 2 : jN), aDp = sum(k ? jD - 2 : jD), aN2 = sum(k > 1 ? jN - 4 : jN), aD2 = sum(k > 1 ? jD - 4 : jD);
+            const PrevAlpha a = prev_alpha(k);
             const thallo_prev_t prev = { k ? slot(jD - 2) : nullptr, v_.s12buf((k - 1) & 1), nb_prev, k ? scal(jD - 2) : nullptr, k ? scal(jB - 2) : nullptr };
-            nb = plugin->pcg_iter_dist_deferred(ctx, vv, cur_, mode, aNp, aDp, sum(jN), aN2, aD2, prev, 7 * (k - 1), gs, D.d_iter[cur_ ^ 1], slot(jD), v_.s12buf(k & 1));
+            nb = plugin->pcg_iter_dist_deferred(ctx, R.vectors(), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, prev, 7 * (k - 1), gs, D.d_iter[cur_ ^ 1], slot(jD), v_.s12buf(k & 1));
             if (nb < 0) dist_fail("PCGIteration (device-side exchange, deferred finish) launch failed (%d)", nb);
         }
         if (!D.failed) {
-            if (k) { fin_[jD - 2] = 1; set_nb(jB - 2, 1); fin_[jB - 2] = 1; }      // (that launch's designated wave writes the two words of iteration k-1)
+            if (k) words_done(k - 1);             // (that launch's designated wave writes the two words of iteration k-1)
             set_nb(jD, nb); nb_prev = nb;
         }
         cur_ ^= 1;
@@ -727,55 +759,64 @@ int Plan::dist_gn(int L, bool p2p)
             const thallo_prev_t last = { slot(jD), v_.s12buf(k & 1), nb, scal(jD), scal(jB) };
             const int rc = plugin->pcg_iter_dist_finish(ctx, last, 7 * k, sum(jN), D.d, gs);
             if (rc < 0) dist_fail("PCGScalars (device-side exchange) launch failed (%d)", rc);
-            if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+            if (!D.failed) words_done(k);
         }
     }
-    for (int k = 0; k < ((resident || defer_x) ? 0 : L); ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        const int mode = ring_step(k);
-        if (p2p) {        // the kernel stores its boundary rows of Ap_out into the neighbours' ghost rows and its last workgroup IS the exchange
-            if (!D.failed) {
-                const thallo_sum_t aNp = sum(k ? jN - 2 : jN), aDp = sum(k ? jD - 2 : jD), aN2 = sum(k > 1 ? jN - 4 : jN), aD2 = sum(k > 1 ? jD - 4 : jD);
-                nb = plugin->pcg_iter_dist(ctx, vv, cur_, mode, aNp, aDp, sum(jN), aN2, aD2, D.d_iter[cur_ ^ 1], slot(jD), 7 * k, scal(jD), scal(jB));
-                if (nb < 0) dist_fail("PCGIteration (device-side exchange) launch failed (%d)", nb);
-            }
-        } else {
-            float* Ao = v_.Abuf(cur_ ^ 1);
-            if (!D.failed) {
-                const thallo_sum_t aNp = sum(k ? jN - 2 : jN), aDp = sum(k ? jD - 2 : jD), aN2 = sum(k > 1 ? jN - 4 : jN), aD2 = sum(k > 1 ? jD - 4 : jD);
-                nb = plugin->pcg_iter(ctx, vv, cur_, mode, aNp, aDp, sum(jN), aN2, aD2, slot(jD), nullptr, nullptr);
-                if (nb < 0) dist_fail("PCGIteration launch failed (%d)", nb);
-            }
-            TimedLaunch t(ctx, "SlabExchange");
-            DLOCAL(thallo_hip_slab_pack_iter(Ao, D.seg_iter_fl, slot(jD), v_.s12, nb, send, s), "slab pack");
-            if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
-            const float* src_top = D.top ? gath + (rank - 1) * D.msg_iter + 7 + 3L * W : nullptr;
-            const float* src_bot = D.bot ? gath + (rank + 1) * D.msg_iter + 7 : nullptr;
-            DLOCAL(thallo_hip_slab_unpack_iter(Ao, D.seg_iter_top, src_top, D.seg_iter_bot, src_bot, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "slab unpack");
+}
+
+// Device-side transport: the kernel stores its boundary rows of Ap_out into the neighbours' ghost rows and its last workgroup IS the exchange
+void Plan::dist_gn_loop_p2p(int L, PRing& R, bool batch)
+{
+    DistState& D = *dist_;
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+        const int mode = dist_launch_mode(R, k, batch);
+        if (!D.failed) {
+            const PrevAlpha a = prev_alpha(k);
+            nb = plugin->pcg_iter_dist(ctx, R.vectors(), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, D.d_iter[cur_ ^ 1], slot(jD), 7 * k, scal(jD), scal(jB));
+            if (nb < 0) dist_fail("PCGIteration (device-side exchange) launch failed (%d)", nb);
         }
-        if (!D.failed) { set_nb(jD, nb); fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+        if (!D.failed) { set_nb(jD, nb); words_done(k); }
         cur_ ^= 1;
     }
-    if (!D.failed && ring && L > 0) {
-        // PCGLinearUpdate with every pending term (all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first), over the OWNED rows of each unknown image
-        last_l_iters = L;
-        flush_ring(L - 1 - THALLO_HIP_MAX_UPDATE_TERMS);
-        thallo_update_terms_t T; T.count = 0;
-        for (int j = flushed; j < L; ++j) { T.p[T.count] = ring_plane(j); T.alphaN[T.count] = sum(B + 2 * j); T.alphaD[T.count] = sum(B + 2 * j + 1); ++T.count; }
-        const auto& imgs = plugin->unknown_images();
-        long off = 0;
-        for (size_t u = 0; u < imgs.size() && !D.failed; ++u) {
-            TimedLaunch t(ctx, "PCGLinearUpdate");
-            const long rowlen = imgs[u].n_floats / D.Hl, lo = rowlen * D.row0, len = rowlen * (D.row1 - D.row0);
-            thallo_update_terms_t Tu = T;
-            for (int j = 0; j < Tu.count; ++j) Tu.p[j] += off + lo;
-            DLOCAL(thallo_hip_linear_update_n(plugin->unknown_ptr((int)u) + lo, v_.delta + off + lo, Tu, len, 0, s), "PCGLinearUpdate launch");
-            off += imgs[u].n_floats;
+}
+
+// All-gather transport: one launch, then ONE exchange per iteration
+int Plan::dist_gn_loop_allgather(int L, PRing& R, bool batch)
+{
+    DistState& D = *dist_;
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1;
+        const int mode = dist_launch_mode(R, k, batch);
+        if (!D.failed) {
+            const PrevAlpha a = prev_alpha(k);
+            nb = plugin->pcg_iter(ctx, R.vectors(), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD), nullptr, nullptr);
+            if (nb < 0) dist_fail("PCGIteration launch failed (%d)", nb);
         }
-        plugin->unknowns_written();
-    } else
-    if (!D.failed) { last_l_iters = L; linear_update_tail(L, batch && !resident); }   // owned rows only (the resident loop has applied every delta update but the last itself)
-    return dist_exchange_unknown_rows();
+        {   TimedLaunch t(ctx, "SlabExchange");
+            if (dist_allgather_iter(v_.Abuf(cur_ ^ 1), k, nb)) return -1; }
+        if (!D.failed) { set_nb(jD, nb); words_done(k); }
+        cur_ ^= 1;
+    }
+    return 0;
+}
+
+int Plan::dist_allgather_iter(float* Ap, int k, int nb)
+{   // message = [alphaD, N, S1, S2 partials | my first / last boundary rows of the new A p]; the ghost rows from the neighbours' messages, the rank-ordered sums into alphaD_k, betaN_k
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2, rank = D.cfg.rank;
+    const bool slab = D.form == DistForm::Slab;
+    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
+    DLOCAL(thallo_hip_slab_pack_iter(Ap, slab ? D.seg_iter_fl : D.seg_rows_fl, slot(jD), v_.s12, nb, send, s), "slab pack");
+    if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
+    const float* src_top = D.top ? gath + (rank - 1) * D.msg_iter + 7 + (slab ? 3L * D.W : D.ghost * D.rowlen) : nullptr;      // the LAST rows of rank-1
+    const float* src_bot = D.bot ? gath + (rank + 1) * D.msg_iter + 7 : nullptr;                                              // the FIRST rows of rank+1
+    DLOCAL(thallo_hip_slab_unpack_iter(Ap, slab ? D.seg_iter_top : D.seg_rows_top, src_top, slab ? D.seg_iter_bot : D.seg_rows_bot, src_bot, gath, D.msg_iter, D.cfg.world,
+                                       sum(jN), scal(jD), scal(jB), s), "slab unpack");
+    return 0;
 }
 
 int Plan::dist_exchange_unknown_rows()
@@ -878,14 +919,9 @@ int Plan::dist_two_sums_and_rows(int j1, int j2, float* vec, float* zeta_state, 
 }
 
 int Plan::dist_gn_flat(int L)
-{   // the slab form of step_gn_expanded: per PCG iteration pcg_update over owned + ghost rows, applyJTJ with sums over the owned rows, ONE exchange
-    // [alphaD | N, S1, S2 | boundary rows of Ap]
+{   // the slab form of step_gn_expanded: PCGInit, one of two PCG loops with ONE exchange [alphaD | N, S1, S2 | boundary rows of Ap] per iteration, the shared finish
     DistState& D = *dist_;
-    hipStream_t s = ctx.stream;
-    const int B = 2, world = D.cfg.world, rank = D.cfg.rank;
-    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
-    const long gl = D.ghost * D.rowlen;
-    const long oe = D.rowlen * (D.row0 - D.top), lene = D.rowlen * (D.row1 + D.bot - (D.row0 - D.top));
+    const int B = 2;
     const bool pc = plugin->use_preconditioner();
     cur_ = 0;
     int nb = 0;
@@ -896,59 +932,65 @@ int Plan::dist_gn_flat(int L)
         if (pc && dist_sum_and_rows(-1, v_.pre)) return -1;
     }
     // One launch per PCG iteration on the slab too (round 3; plugins whose pcg_iter keeps r and p current on the ghost rows: shape_from_shading's marching kernel; the same
-    // decision on every rank): the iteration is pcg_iter + ONE exchange [alphaD | N, S1, S2 | boundary rows of the new A p].  THALLO_ONE_KERNEL=0: the three-launch form.
+    // decision on every rank).  THALLO_ONE_KERNEL=0: the three-launch form.
     const bool onek = one_kernel_ && !pc && plugin->one_kernel_slab() && v_.r2 != nullptr && v_.Ap2 != nullptr && v_.p[1] != nullptr;
-    for (int k = 0; onek && k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+    if (onek ? dist_gn_flat_loop_one_launch(L) : dist_gn_flat_loop_three_launch(L)) return -1;
+    if (!D.failed) { last_l_iters = L; linear_update_tail(L, false); }
+    return dist_exchange_unknown_rows();
+}
+
+int Plan::dist_gn_flat_loop_one_launch(int L)
+{   // the iteration is pcg_iter + the exchange of the new A p
+    DistState& D = *dist_;
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1;
         const thallo_sum_t nosum = { nullptr, 0 };
         if (!D.failed) {
-            nb = plugin->pcg_iter(ctx, v_, cur_, k == 0 ? 1 : 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), nosum, nosum, slot(jD), nullptr, nullptr);
+            nb = plugin->pcg_iter(ctx, v_, cur_, k == 0 ? 1 : 0, prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), nosum, nosum, slot(jD), nullptr, nullptr);
             if (nb < 0) dist_fail("PCGIteration launch failed (%d)", nb);
         }
         if (!D.failed) set_nb(jD, nb);
-        float* Ao = v_.Abuf(cur_ ^ 1);
         cur_ ^= 1;
-        TimedLaunch t(ctx, "SlabExchange");
-        if (D.xrows_now) {
-            const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };
-            if (dist_xrows(Ao, true, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12, D.failed ? 1 : nb, scal(jD), scal(jB))) return -1;
-        } else {
-            DLOCAL(thallo_hip_slab_pack_iter(Ao, D.seg_rows_fl, slot(jD), v_.s12, nb, send, s), "slab pack");
-            if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
-            const float* src_top = D.top ? gath + (rank - 1) * D.msg_iter + 7 + gl : nullptr;
-            const float* src_bot = D.bot ? gath + (rank + 1) * D.msg_iter + 7 : nullptr;
-            DLOCAL(thallo_hip_slab_unpack_iter(Ao, D.seg_rows_top, src_top, D.seg_rows_bot, src_bot, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "slab unpack");
-        }
-        if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+        if (dist_flat_exchange_iter(v_.Abuf(cur_), k, nb)) return -1;
     }
-    for (int k = 0; !onek && k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+    return 0;
+}
+
+int Plan::dist_gn_flat_loop_three_launch(int L)
+{   // the iteration is pcg_update over owned + ghost rows, applyJTJ with sums over the owned rows, the exchange
+    DistState& D = *dist_;
+    const long oe = D.rowlen * (D.row0 - D.top), lene = D.rowlen * (D.row1 + D.bot - (D.row0 - D.top));
+    const bool pc = plugin->use_preconditioner();
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = 2 + 2 * k, jD = jN + 1;
         if (!D.failed) {
             {   TimedLaunch t(ctx, "PCGUpdate");
                 DLOCAL(thallo_hip_pcg_update(v_.r + oe, v_.Ap + oe, pc ? v_.pre + oe : nullptr, v_.p[cur_] + oe, v_.p[cur_ ^ 1] + oe, v_.delta + oe, lene, k == 0,
-                                             sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGUpdate launch");
+                                             prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), ctx.stream), "PCGUpdate launch");
             }
             const thallo_fin_t none = { { nullptr, 0 }, nullptr, nullptr, nullptr };
             if (!D.failed) { nb = plugin->apply_jtj_sums(ctx, v_, v_.p[cur_ ^ 1], v_.Ap, slot(jD), none); if (nb < 0) dist_fail("PCGStep1 launch failed (%d)", nb); }
             if (!D.failed) set_nb(jD, nb);
         }
         cur_ ^= 1;
-        TimedLaunch t(ctx, "SlabExchange");
-        if (D.xrows_now) {                      // ONE launch: rows into the neighbours' inboxes, scalars to every rank, own inbox -> ghost rows
-            const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };     // (a failed rank's arguments only have to be launchable: it sends NaN)
-            if (dist_xrows(v_.Ap, true, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12, D.failed ? 1 : nb, scal(jD), scal(jB))) return -1;
-            if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            continue;
-        }
-        DLOCAL(thallo_hip_slab_pack_iter(v_.Ap, D.seg_rows_fl, slot(jD), v_.s12, nb, send, s), "slab pack");
-        if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
-        const float* src_top = D.top ? gath + (rank - 1) * D.msg_iter + 7 + gl : nullptr;
-        const float* src_bot = D.bot ? gath + (rank + 1) * D.msg_iter + 7 : nullptr;
-        DLOCAL(thallo_hip_slab_unpack_iter(v_.Ap, D.seg_rows_top, src_top, D.seg_rows_bot, src_bot, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "slab unpack");
-        if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+        if (dist_flat_exchange_iter(v_.Ap, k, nb)) return -1;
     }
-    if (!D.failed) { last_l_iters = L; linear_update_tail(L, false); }
-    return dist_exchange_unknown_rows();
+    return 0;
+}
+
+int Plan::dist_flat_exchange_iter(float* Ap, int k, int nb)
+{   // "SlabExchange": on the device-side transport ONE launch (rows into the neighbours' inboxes, scalars to every rank, own inbox -> ghost rows), else the all-gather
+    DistState& D = *dist_;
+    const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+    TimedLaunch t(ctx, "SlabExchange");
+    if (D.xrows_now) {
+        const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };     // (a failed rank's arguments only have to be launchable: it sends NaN)
+        if (dist_xrows(Ap, true, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12, D.failed ? 1 : nb, scal(jD), scal(jB))) return -1;
+    } else if (dist_allgather_iter(Ap, k, nb)) return -1;
+    if (!D.failed) words_done(k);
+    return 0;
 }
 
 // ---- range form (graph domains)
