@@ -16,6 +16,7 @@ import pytest
 import thallo_amd
 from thallo_amd import api, synthetic as syn
 from helpers import to_device, to_host, rel_err, copy_params, oracle_fixture, set_ab
+from shim_kernels import _sum_partials_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -132,22 +133,6 @@ def test_kat_minimal_image_shipped_guard_matches_oracle(torch, orc):
 
 
 # ------------------------------------------------------------------ the reduction primitive (replaces util.t:40-50 + cuda_util.t:287-289,430-439)
-def _sum_partials_reference(part):
-    """sum_partials() of csrc/device_common.hpp in numpy float32: lane l adds part[l], part[l+64], ... in index order, then the wave64
-    butterfly v += shfl_xor(v, m) for m = 32, 16, ..., 1."""
-    lanes = np.zeros(64, np.float32)
-    for l in range(64):
-        acc = np.float32(0.0)
-        for x in part[l::64]:
-            acc = np.float32(acc + x)
-        lanes[l] = acc
-    m = 32
-    while m >= 1:
-        lanes = (lanes + lanes[np.arange(64) ^ m]).astype(np.float32)
-        m //= 2
-    return lanes[0]
-
-
 @pytest.mark.parametrize("nb", [1, 5, 64, 100, 513, 1024])
 def test_reduction_order_is_the_documented_one(torch, nb):
     """Every PCG scalar is `finish_sum` / `sum_partials` of per-workgroup partials: one FIXED association order, which is what makes the

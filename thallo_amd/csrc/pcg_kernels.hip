@@ -144,11 +144,13 @@ __global__ __launch_bounds__(BLOCK) void k_step2_full(float4* __restrict__ delta
                 Q1 = nb == 1 ? t[0] : wave_sum_all(Q1);
                 Q1 = __shfl(Q1, 0, THALLO_WAVE);                                          // (nb == 1: lane 0 holds it)
                 const float Q0 = zeta.state[0];
+                const bool frozen = reinterpret_cast<const unsigned*>(zeta.state)[1] != 0u;      // k_lm_zeta leaves a frozen state alone (an LM loop never gets here: its gate ends the launch)
                 const float zt = (float)(zeta.k + 1) * (Q1 - Q0) / Q1;
                 const bool stop = !isfinite(Q1) || !isfinite(zt) || zt < zeta.q_tolerance;
                 if (lane == 0) {
                     __hip_atomic_store(zeta.tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (stop) { reinterpret_cast<unsigned*>(zeta.state)[1] = 1u; reinterpret_cast<int*>(zeta.state)[2] = zeta.k + 1; }
+                    if (frozen) { }
+                    else if (stop) { reinterpret_cast<unsigned*>(zeta.state)[1] = 1u; reinterpret_cast<int*>(zeta.state)[2] = zeta.k + 1; }
                     else zeta.state[0] = Q1;
                 }
             }

@@ -219,8 +219,10 @@ __device__ __forceinline__ long inc_owner(const int* __restrict__ col, long el, 
 {
     if (S.base[q] < 0) return -1;
     const int u = col[el * K + q]; if (u < 0) return -1;
-    const long px = ((long)u - S.base[q]) / S.ch[q];
-    return px >= 0 && px < npix ? px : -1;
+    const long d = (long)u - S.base[q];
+    if (d < 0) return -1;                     // below the slot's image: the division would round (-ch, 0) towards owner 0
+    const long px = d / S.ch[q];
+    return px < npix ? px : -1;
 }
 template <bool FILL>
 __global__ __launch_bounds__(BLOCK) void k_inc_count_fill(const int* __restrict__ col, long n, int K, IncSlots S, long npix, int* __restrict__ ptr, int* __restrict__ cursor, int* __restrict__ els)
