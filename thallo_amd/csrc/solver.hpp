@@ -360,6 +360,10 @@ private:
     int  dist_agree(bool flag, bool& all);
     void dist_fail(const char* fmt, ...);               // first rank-local failure: report it, switch this rank to "collectives only" (DistState::failed)
     bool dist_skip() const { return dist_ && dist_->failed; }
+    void dist_exchange_rc(int rc, const char* what);    // the result of a device-side exchange's launch: an injection point; "<what> failed (rc)" on a healthy rank
+    // what a rank hands an iteration's device-side exchange: its own sums and slots or, once it has failed, dummies that only have to be launchable (it sends NaN)
+    struct DistPayload { thallo_sum_t sum; const float* slot; int nb, poison; };
+    DistPayload dist_payload(thallo_sum_t sum, const float* slot, int nb) { const float* dummy = (const float*)dist_->send.ptr; return dist_->failed ? DistPayload{ { dummy, 1 }, dummy, 1, 1 } : DistPayload{ sum, slot, nb, 0 }; }
     int  dist_xrows_lm(float* vec, int jN, int jD, int jB, int nb, float* lm_state, int k);      // the ONE exchange of a slab's one-launch LM iteration
     int  dist_two_sums_and_rows(int j1, int j2, float* vec, float* zeta_state = nullptr, int zeta_k = 0, bool* zeta_done = nullptr);
     int  dist_xrows(float* vec, bool rows, int mode, thallo_sum_t s, const float* aD_part, const double* s3, int nb, float* out0, float* out1, float* zeta_state = nullptr, int zeta_k = 0);
@@ -371,6 +375,8 @@ private:
     int  dist_allreduce(float* buf, long count);        // Shard: the shared block's partial sums added over the ranks, in place
     // the Gauss-Newton step, per form
     int  step_gn_slab(int ev_iter);
+    int  dist_pcg_init();                               // every form's head: cur_ = 0, PCGInit1 into slot 2 -> its partial count (the caller decides whether it is the slot's)
+    int  dist_three_launch_iter(int k, long o, long n); // Flat, Range, Partition, Shard: PCGUpdate over [o, o + n), applyJTJ with its sums into alphaD_k's slot -> its partial count
     // Slab: dist_gn = dist_gn_begin, ONE of the four PCG loops, the shared finish (linear update over the owned rows, ghost refresh); no bookkeeping
     int  dist_gn(int L, bool p2p);
     int  dist_gn_begin(bool p2p);
@@ -386,8 +392,18 @@ private:
     int  dist_gn_flat(int L);
     int  dist_gn_flat_loop_one_launch(int L), dist_gn_flat_loop_three_launch(int L);
     int  dist_flat_exchange_iter(float* Ap, int k, int nb);
-    int  dist_gn_range(int L);                          // Range, Partition: full-length pcg_update + applyJTJ over the owned units + ONE exchange per PCG iteration
-    int  dist_gn_shard(int L);                          // Shard: applyJTJ on the rank's residuals, all-reduce of the shared block of A p, one tiny all-gather
+    // Range, Partition: dist_gn_range = its begin (clears, PCGInit1, alphaN_0 and r everywhere), L x (dist_three_launch_iter on the full vector, ONE exchange), linear update of all unknowns
+    int  dist_gn_range(int L), dist_gn_range_begin(), dist_range_exchange_iter(int k, int nb);
+    // Shard: dist_gn_shard = its begin (through alphaN_0), L x (dist_three_launch_iter, all-reduce of the point block of A p + block sums + the camera sums), linear update
+    int  dist_gn_shard(int L), dist_gn_shard_begin(), dist_shard_exchange_iter(int k, int cam_slots);
+    struct TwoBlocks { int cam = 0, pt = 0; };          // partial counts of one element-wise launch on the camera block and on the point block
+    template <class Launch> TwoBlocks dist_on_blocks(float* cam_partials, float* pt_partials, const char* what, Launch launch);      // launch(offset, n, partials); "<what> launch failed (cam, pt)"
+    struct ShardSum { int j; float* pts; int nbp; float* out; };      // camera partials in slot j (rank-ordered over the ranks) + the point block's -> out (nullptr: scal(j), the slot's final word)
+    int  dist_shard_sums(std::initializer_list<ShardSum> sums, const char* what_cam, const char* what_sum);      // ONE all-gather of one float per sum
+    // Shard, LM: step_lm_shard = lm_shard_setup, lm_shard_loop (its residual-reset branch: lm_shard_residual_reset), lm_shard_finish
+    struct ShardLm;
+    bool lm_shard_setup(ShardLm& st), lm_shard_loop(ShardLm& st), lm_shard_residual_reset(ShardLm& st, int k, TwoBlocks& nb);
+    int  lm_shard_apply(float* x, float* Ax, int T0, const char* what), lm_shard_finish(ShardLm& st);
     float dist_cost();
     void dist_release();
 };

@@ -46,6 +46,13 @@ void Plan::dist_fail(const char* fmt, ...)
 // a rank-local launch / copy: skipped once the rank has failed, a negative (or non-hipSuccess) result is the failure
 #define DLOCAL(call, what) do { if (!D.failed) { int rc__ = (int)(call); if (D.inject > 0 && --D.inject == 0) rc__ = -999; if (rc__ < 0) dist_fail("%s failed (%d)", what, rc__); } } while (0)
 #define DCOPY(call, what)  do { if (!D.failed) { const hipError_t e__ = (call); if (e__ != hipSuccess) dist_fail("%s failed (%s)", what, hipGetErrorString(e__)); } } while (0)
+// a device-side exchange is launched by EVERY rank, failed or not (nobody may wait for a rank): its result counts, and ticks the injection counter, on a healthy rank only
+void Plan::dist_exchange_rc(int rc, const char* what)
+{
+    DistState& D = *dist_;
+    if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
+    if (rc < 0 && !D.failed) dist_fail("%s failed (%d)", what, rc);
+}
 
 int Plan::dist_allgather(const void* send, void* recv, long bytes)
 {
@@ -565,12 +572,11 @@ int Plan::dist_xrows(float* vec, bool rows, int mode, thallo_sum_t sm, const flo
     DistState& D = *dist_;
     const thallo_segs_t none = segs({});
     const int poison = D.failed ? 1 : 0;
-    int rc = zeta_state ? thallo_hip_dist_xrows_zeta(D.d, D.xr, vec, rows ? D.seg_rows_first : none, rows ? D.seg_rows_last : none, rows ? D.seg_rows_top : none, rows ? D.seg_rows_bot : none,
+    const int rc = zeta_state ? thallo_hip_dist_xrows_zeta(D.d, D.xr, vec, rows ? D.seg_rows_first : none, rows ? D.seg_rows_last : none, rows ? D.seg_rows_top : none, rows ? D.seg_rows_bot : none,
                                                      sm, aD_part, nb, poison, out0, out1, zeta_state, zeta_k, sp.q_tolerance, ctx.stream)
                         : thallo_hip_dist_xrows(D.d, D.xr, vec, rows ? D.seg_rows_first : none, rows ? D.seg_rows_last : none, rows ? D.seg_rows_top : none, rows ? D.seg_rows_bot : none,
                                                 mode, sm, aD_part, s3, nb, poison, out0, out1, ctx.stream);
-    if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-    if (rc < 0 && !D.failed) dist_fail("device-side row exchange failed (%d)", rc);
+    dist_exchange_rc(rc, "device-side row exchange");
     return 0;
 }
 
@@ -619,6 +625,14 @@ float Plan::dist_cost()
 
 // ---- Slab: one GN step = dist_gn_begin, ONE of four PCG loops, the shared finish (DESIGN.md "GN schedules").  Every rank issues every collective of the sequence
 // unconditionally; everything rank-local stays behind !D.failed (DLOCAL / DCOPY).
+int Plan::dist_pcg_init()
+{   // the head of every form's step: PCGInit1 into slot 2 -> its partial count (the caller says whether that is the slot's count: the shard forms finish the launch on two blocks first)
+    cur_ = 0;
+    int nb = 0;
+    if (!dist_->failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(2)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }
+    return nb;
+}
+
 int Plan::dist_gn_begin(bool p2p)
 {
     DistState& D = *dist_;
@@ -626,9 +640,7 @@ int Plan::dist_gn_begin(bool p2p)
     const int B = 2, W = D.W, world = D.cfg.world, rank = D.cfg.rank;
     float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
     unsigned char* flags = plugin->slab_flags();
-    cur_ = 0;
-    int nb = 0;
-    if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }
+    const int nb = dist_pcg_init();
     if (!D.failed) set_nb(B, nb);
     {   // alphaN_0 over all ranks; ghost rows of r and z; and the flags byte of the ghost rows (M^-1 of a ghost pixel depends on rows this rank
         // does not hold, so its owner supplies it)
@@ -896,12 +908,10 @@ int Plan::dist_sum_and_rows(int j, float* vec)
 int Plan::dist_xrows_lm(float* vec, int jN, int jD, int jB, int nb, float* lm_state, int k)
 {   // device-side transport only: the ranks' alphaD / {N, S1, S2} / {U, T1, T2} partials + the boundary rows of the new A p; alphaD_k, betaN_k, q_{k+1} and the zeta test
     DistState& D = *dist_;
-    const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };
-    int rc = thallo_hip_dist_xrows_lm(D.d, D.xr, vec, D.seg_rows_first, D.seg_rows_last, D.seg_rows_top, D.seg_rows_bot, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD),
-                                      v_.s12, v_.s12b, D.failed ? 1 : nb, D.failed ? 1 : 0, scal(jD), scal(jB), lm_state, k, sp.q_tolerance, ctx.stream);
-    if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-    if (rc < 0 && !D.failed) dist_fail("device-side LM exchange failed (%d)", rc);
-    if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+    const DistPayload w = dist_payload(sum(jN), slot(jD), nb);
+    dist_exchange_rc(thallo_hip_dist_xrows_lm(D.d, D.xr, vec, D.seg_rows_first, D.seg_rows_last, D.seg_rows_top, D.seg_rows_bot, w.sum, w.slot, v_.s12, v_.s12b, w.nb, w.poison,
+                                              scal(jD), scal(jB), lm_state, k, sp.q_tolerance, ctx.stream), "device-side LM exchange");
+    if (!D.failed) words_done(k);
     return 0;
 }
 
@@ -911,8 +921,8 @@ int Plan::dist_two_sums_and_rows(int j1, int j2, float* vec, float* zeta_state, 
     DistState& D = *dist_;
     if (zeta_done) *zeta_done = false;
     if (!D.xrows_now) return dist_sum_slot(j1) || dist_sum_and_rows(j2, vec) ? -1 : 0;
-    const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };
-    if (dist_xrows(vec, true, 0, D.failed ? dummy : partial_sum(j1), D.failed ? (const float*)D.send.ptr : slot(j2), nullptr, D.failed ? 1 : nb_[j2], scal(j1), scal(j2), zeta_state, zeta_k)) return -1;
+    const DistPayload w = dist_payload(partial_sum(j1), slot(j2), nb_[j2]);
+    if (dist_xrows(vec, true, 0, w.sum, w.slot, nullptr, w.nb, scal(j1), scal(j2), zeta_state, zeta_k)) return -1;
     if (zeta_done && zeta_state) *zeta_done = true;
     if (!D.failed) { fin_[j1] = 1; fin_[j2] = 1; }
     return 0;
@@ -923,9 +933,7 @@ int Plan::dist_gn_flat(int L)
     DistState& D = *dist_;
     const int B = 2;
     const bool pc = plugin->use_preconditioner();
-    cur_ = 0;
-    int nb = 0;
-    if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }
+    const int nb = dist_pcg_init();
     if (!D.failed) set_nb(B, nb);
     {   TimedLaunch t(ctx, "SlabExchangeInit");
         if (dist_sum_and_rows(B, v_.r)) return -1;                       // alphaN_0; ghost rows of r (p_0 = M^-1 r_0 there too)
@@ -957,26 +965,31 @@ int Plan::dist_gn_flat_loop_one_launch(int L)
     return 0;
 }
 
+int Plan::dist_three_launch_iter(int k, long o, long n)
+{   // Flat, Range, Partition, Shard: PCGUpdate over [o, o + n), then applyJTJ with its sums into alphaD_k's slot (no finish in the launch) -> its partial count; the form's exchange follows
+    DistState& D = *dist_;
+    const int jN = 2 + 2 * k, jD = jN + 1;
+    const bool pc = plugin->use_preconditioner();
+    int nb = 0;
+    if (!D.failed) {
+        {   TimedLaunch t(ctx, "PCGUpdate");
+            DLOCAL(thallo_hip_pcg_update(v_.r + o, v_.Ap + o, pc ? v_.pre + o : nullptr, v_.p[cur_] + o, v_.p[cur_ ^ 1] + o, v_.delta + o, n, k == 0,
+                                         prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), ctx.stream), "PCGUpdate launch");
+        }
+        const thallo_fin_t nofin = { { nullptr, 0 }, nullptr, nullptr, nullptr };
+        if (!D.failed) { nb = plugin->apply_jtj_sums(ctx, v_, v_.p[cur_ ^ 1], v_.Ap, slot(jD), nofin); if (nb < 0) dist_fail("PCGStep1 launch failed (%d)", nb); }
+        if (!D.failed) set_nb(jD, nb);
+    }
+    cur_ ^= 1;
+    return nb;
+}
+
 int Plan::dist_gn_flat_loop_three_launch(int L)
 {   // the iteration is pcg_update over owned + ghost rows, applyJTJ with sums over the owned rows, the exchange
     DistState& D = *dist_;
     const long oe = D.rowlen * (D.row0 - D.top), lene = D.rowlen * (D.row1 + D.bot - (D.row0 - D.top));
-    const bool pc = plugin->use_preconditioner();
-    int nb = 0;
-    for (int k = 0; k < L; ++k) {
-        const int jN = 2 + 2 * k, jD = jN + 1;
-        if (!D.failed) {
-            {   TimedLaunch t(ctx, "PCGUpdate");
-                DLOCAL(thallo_hip_pcg_update(v_.r + oe, v_.Ap + oe, pc ? v_.pre + oe : nullptr, v_.p[cur_] + oe, v_.p[cur_ ^ 1] + oe, v_.delta + oe, lene, k == 0,
-                                             prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), ctx.stream), "PCGUpdate launch");
-            }
-            const thallo_fin_t none = { { nullptr, 0 }, nullptr, nullptr, nullptr };
-            if (!D.failed) { nb = plugin->apply_jtj_sums(ctx, v_, v_.p[cur_ ^ 1], v_.Ap, slot(jD), none); if (nb < 0) dist_fail("PCGStep1 launch failed (%d)", nb); }
-            if (!D.failed) set_nb(jD, nb);
-        }
-        cur_ ^= 1;
-        if (dist_flat_exchange_iter(v_.Ap, k, nb)) return -1;
-    }
+    for (int k = 0; k < L; ++k)
+        if (dist_flat_exchange_iter(v_.Ap, k, dist_three_launch_iter(k, oe, lene))) return -1;
     return 0;
 }
 
@@ -986,8 +999,8 @@ int Plan::dist_flat_exchange_iter(float* Ap, int k, int nb)
     const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
     TimedLaunch t(ctx, "SlabExchange");
     if (D.xrows_now) {
-        const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };     // (a failed rank's arguments only have to be launchable: it sends NaN)
-        if (dist_xrows(Ap, true, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12, D.failed ? 1 : nb, scal(jD), scal(jB))) return -1;
+        const DistPayload w = dist_payload(sum(jN), slot(jD), nb);
+        if (dist_xrows(Ap, true, 1, w.sum, w.slot, v_.s12, w.nb, scal(jD), scal(jB))) return -1;
     } else if (dist_allgather_iter(Ap, k, nb)) return -1;
     if (!D.failed) words_done(k);
     return 0;
@@ -1019,9 +1032,8 @@ int Plan::dist_ghosts(float* vec, int sum_slot)
     const thallo_sum_t nothing = { nullptr, 0 };
     if (D.xrows_now) {       // one launch, no collective
         const thallo_sum_t sm = sum_slot < 0 ? nothing : D.failed ? thallo_sum_t{ (const float*)D.send.ptr, 1 } : partial_sum(sum_slot);
-        int rc = thallo_hip_dist_xunits(D.d, D.xr, vec, D.u_send, D.u_recvx, D.unit_slot, 0, sm, nullptr, nullptr, 0, D.failed ? 1 : 0, sum_slot >= 0 ? scal(sum_slot) : nullptr, nullptr, s);
-        if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-        if (rc < 0 && !D.failed) dist_fail("device-side boundary exchange failed (%d)", rc);
+        dist_exchange_rc(thallo_hip_dist_xunits(D.d, D.xr, vec, D.u_send, D.u_recvx, D.unit_slot, 0, sm, nullptr, nullptr, 0, D.failed ? 1 : 0, sum_slot >= 0 ? scal(sum_slot) : nullptr, nullptr, s),
+                         "device-side boundary exchange");
         if (sum_slot >= 0 && !D.failed) fin_[sum_slot] = 1;
         return 0;
     }
@@ -1032,64 +1044,59 @@ int Plan::dist_ghosts(float* vec, int sum_slot)
     return 0;
 }
 
+// Range, Partition: dist_gn_range = dist_gn_range_begin, L x (dist_three_launch_iter over the whole vector, dist_range_exchange_iter), the linear update of ALL unknowns.
+// Every rank keeps FULL-length vectors (a 100k-vertex graph is 2.4 MB per vector) and does the energy-independent vector update for ALL
+// unknowns -- redundantly, same inputs, same bits -- so the only thing that has to travel per PCG iteration is what a rank alone can
+// compute: its owned slice of A p and its partial sums.  ONE exchange of [alphaD | N, S1, S2 | owned slice of Ap] per iteration.
 int Plan::dist_gn_range(int L)
-{   // Every rank keeps FULL-length vectors (a 100k-vertex graph is 2.4 MB per vector) and does the energy-independent vector update for ALL
-    // unknowns -- redundantly, same inputs, same bits -- so the only thing that has to travel per PCG iteration is what a rank alone can
-    // compute: its owned slice of A p and its partial sums.  ONE all-gather of [alphaD | N, S1, S2 | owned slice of Ap] per iteration.
+{
+    DistState& D = *dist_;
+    if (dist_gn_range_begin()) return -1;
+    for (int k = 0; k < L; ++k)
+        if (dist_range_exchange_iter(k, dist_three_launch_iter(k, 0, v_.n))) return -1;
+    if (!D.failed) { last_l_iters = L; linear_update_tail(L, false); }   // all unknowns on every rank: they stay replicated, bit for bit
+    return 0;
+}
+
+int Plan::dist_gn_range_begin()
+{
     DistState& D = *dist_;
     hipStream_t s = ctx.stream;
-    const int B = 2, world = D.cfg.world;
-    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
-    const bool pc = plugin->use_preconditioner();
-    const thallo_segs_t none = segs({});
-    const bool part = D.form == DistForm::Partition;
-    cur_ = 0;
+    const int B = 2;
+    const bool pc = plugin->use_preconditioner(), part = D.form == DistForm::Partition;
     const size_t bytes = (size_t)v_.n_alloc * sizeof(float);
     DCOPY(hipMemsetAsync(v_.p[0], 0, bytes, s), "p clear");              // (pcg_init clears the owned units only)
     DCOPY(hipMemsetAsync(v_.delta, 0, bytes, s), "delta clear");
-    int nb = 0;
-    if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }
+    const int nb = dist_pcg_init();
     if (!D.failed) set_nb(B, nb);
-    {   TimedLaunch t(ctx, "RangeExchangeInit");
-        if (part ? dist_ghosts(v_.r, B) : dist_replicate(v_.r, B)) return -1;       // alphaN_0; r of every unit (partition form: of the ghost units)
-        if (pc && (part ? dist_ghosts(v_.pre, -1) : dist_replicate(v_.pre, -1))) return -1;
-    }
-    for (int k = 0; k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        if (!D.failed) {
-            {   TimedLaunch t(ctx, "PCGUpdate");
-                DLOCAL(thallo_hip_pcg_update(v_.r, v_.Ap, pc ? v_.pre : nullptr, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, v_.n, k == 0,
-                                             sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGUpdate launch");
-            }
-            const thallo_fin_t nofin = { { nullptr, 0 }, nullptr, nullptr, nullptr };
-            if (!D.failed) { nb = plugin->apply_jtj_sums(ctx, v_, v_.p[cur_ ^ 1], v_.Ap, slot(jD), nofin); if (nb < 0) dist_fail("PCGStep1 launch failed (%d)", nb); }
-            if (!D.failed) set_nb(jD, nb);
-        }
-        cur_ ^= 1;
-        TimedLaunch t(ctx, "RangeExchange");
-        if (part && D.xrows_now) {
-            const thallo_sum_t dummy = { (const float*)D.send.ptr, 1 };
-            int rc = thallo_hip_dist_xunits(D.d, D.xr, v_.Ap, D.u_send, D.u_recvx, D.unit_slot, 1, D.failed ? dummy : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12,
-                                            D.failed ? 1 : nb, D.failed ? 1 : 0, scal(jD), scal(jB), s);
-            if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-            if (rc < 0 && !D.failed) dist_fail("device-side boundary exchange failed (%d)", rc);
-            if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            continue;
-        }
-        if (part) {       // [alphaD | N, S1, S2 | A p at my boundary units] -> the ghosts' A p (r, p, delta of a ghost then follow from the same arithmetic as its owner's)
-            DLOCAL(thallo_hip_units_pack_iter(v_.Ap, D.u_send, slot(jD), v_.s12, nb, send, s), "boundary pack");
-            if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
-            DLOCAL(thallo_hip_units_unpack_iter(v_.Ap, D.u_recv7, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "ghost unpack");
-            if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            continue;
-        }
+    TimedLaunch t(ctx, "RangeExchangeInit");
+    if (part ? dist_ghosts(v_.r, B) : dist_replicate(v_.r, B)) return -1;       // alphaN_0; r of every unit (partition form: of the ghost units)
+    if (pc && (part ? dist_ghosts(v_.pre, -1) : dist_replicate(v_.pre, -1))) return -1;
+    return 0;
+}
+
+int Plan::dist_range_exchange_iter(int k, int nb)
+{   // "RangeExchange": the new A p where the other ranks need it, the rank-ordered sums into alphaD_k, betaN_k.  Partition on the device-side transport: ONE launch, no collective
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2, world = D.cfg.world;
+    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
+    TimedLaunch t(ctx, "RangeExchange");
+    if (D.form == DistForm::Partition && D.xrows_now) {
+        const DistPayload w = dist_payload(sum(jN), slot(jD), nb);
+        dist_exchange_rc(thallo_hip_dist_xunits(D.d, D.xr, v_.Ap, D.u_send, D.u_recvx, D.unit_slot, 1, w.sum, w.slot, v_.s12, w.nb, w.poison, scal(jD), scal(jB), s), "device-side boundary exchange");
+    } else if (D.form == DistForm::Partition) {       // [alphaD | N, S1, S2 | A p at my boundary units] -> the ghosts' A p (r, p, delta of a ghost then follow from the same arithmetic as its owner's)
+        DLOCAL(thallo_hip_units_pack_iter(v_.Ap, D.u_send, slot(jD), v_.s12, nb, send, s), "boundary pack");
+        if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
+        DLOCAL(thallo_hip_units_unpack_iter(v_.Ap, D.u_recv7, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "ghost unpack");
+    } else {                                          // [alphaD | N, S1, S2 | my owned slice of A p] -> every rank holds every slice
+        const thallo_segs_t none = segs({});
         DLOCAL(thallo_hip_slab_pack_iter(v_.Ap, D.pieces_mine, slot(jD), v_.s12, nb, send, s), "range pack");
         if (dist_allgather(send, gath, D.msg_iter * (long)sizeof(float))) return -1;
         DLOCAL(thallo_hip_slab_unpack_iter(v_.Ap, none, nullptr, none, nullptr, gath, D.msg_iter, world, sum(jN), scal(jD), scal(jB), s), "rank-ordered sums");
         DLOCAL(thallo_hip_range_unpack(v_.Ap, D.pieces_first, gath, D.msg_iter, 7, world, s), "range unpack");
-        if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
     }
-    if (!D.failed) { last_l_iters = L; linear_update_tail(L, false); }   // all unknowns on every rank: they stay replicated, bit for bit
+    if (!D.failed) words_done(k);
     return 0;
 }
 
@@ -1098,9 +1105,7 @@ int Plan::dist_allreduce(float* buf, long count)
 {
     DistState& D = *dist_;
     if (D.form == DistForm::Shard && D.p2p_on && count == D.sh_len && (D.cfg.world > 1 || !D.checked)) {      // peer stores only (world size 1: nothing to add; the set-up's self-check still runs it): reduce-scatter + all-gather in one launch, sums in rank order (the same bits on every rank and in every run)
-        int rc = thallo_hip_dist_allreduce(D.d, D.xa, buf, count, D.failed ? 1 : 0, ctx.stream);
-        if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-        if (rc < 0 && !D.failed) dist_fail("device-side all-reduce failed (%d)", rc);
+        dist_exchange_rc(thallo_hip_dist_allreduce(D.d, D.xa, buf, count, D.failed ? 1 : 0, ctx.stream), "device-side all-reduce");
         return 0;
     }
     if (D.cfg.world == 1) return 0;
@@ -1111,70 +1116,90 @@ int Plan::dist_allreduce(float* buf, long count)
     return rc;
 }
 
-int Plan::dist_gn_shard(int L)
-{   // A rank holds its cameras, ALL points and the observations of its cameras.  J p is local; the camera block of J^T(J p) is complete, the point block
-    // is a partial sum -> all-reduce (3P floats per PCG iteration); then every rank holds identical point blocks of Ap, r, p, delta and updates them
-    // redundantly.  The scalars: the camera parts of [alphaD | N, S1, S2] travel in one tiny all-gather and are added in rank order, the point parts
-    // are computed by every rank for itself after the all-reduce (thallo_hip_block_sums) -- identical inputs, identical bits.
+// One element-wise launch on the camera block [0, sh_off) and again on the point block [sh_off, sh_off + sh_len): launch(offset, n, partials) -> its partial count
+template <class Launch> Plan::TwoBlocks Plan::dist_on_blocks(float* cam_partials, float* pt_partials, const char* what, Launch launch)
+{
+    TwoBlocks nb;
+    if (dist_->failed) return nb;
+    nb.cam = launch(0L, dist_->sh_off, cam_partials);
+    nb.pt = launch(dist_->sh_off, dist_->sh_len, pt_partials);
+    if (nb.cam < 0 || nb.pt < 0) dist_fail("%s launch failed (%d, %d)", what, nb.cam, nb.pt);
+    return nb;
+}
+
+int Plan::dist_shard_sums(std::initializer_list<ShardSum> sums, const char* what_cam, const char* what_sum)
+{   // word i = (sum over the ranks, in rank order, of the camera block's partials in slot j) + the point block's partials pts: ONE all-gather of one float per sum
     DistState& D = *dist_;
     hipStream_t s = ctx.stream;
-    const int B = 2, world = D.cfg.world;
     float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
-    float* sh_aD = (float*)D.sh_aD.ptr; double* sh_s3 = (double*)D.sh_s3.ptr;
-    const long off = D.sh_off, len = D.sh_len;
-    const bool pc = plugin->use_preconditioner();
-    const thallo_segs_t none = segs({});
-    cur_ = 0;
-    int nb = 0;
-    if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }     // r = -J^T F and the RAW diagonal (v_.diag), both partial on the shared block
-    {   TimedLaunch t(ctx, "ShardExchangeInit");
-        if (dist_allreduce(v_.r + off, len) || dist_allreduce(v_.diag + off, len)) return -1;
-        // PCGInit1_Finish on the two blocks separately: pre = guardedInvert(diag), z = pre r, alphaN partials
-        int nbp = 0;
-        if (!D.failed) {
-            const int nbc = thallo_hip_pcg_init_finish(v_.r, v_.diag, v_.pre, v_.z, off, pc ? 1 : 0, slot(B), s);
-            nbp = thallo_hip_pcg_init_finish(v_.r + off, v_.diag + off, v_.pre + off, v_.z + off, len, pc ? 1 : 0, sh_aD, s);
-            if (nbc < 0 || nbp < 0) dist_fail("PCGInit1_Finish launch failed (%d, %d)", nbc, nbp);
-            else { set_nb(B, nbc); DLOCAL(thallo_hip_finish_sum(partial_sum(B), send, s), "alphaN sum"); }
-        }
-        if (dist_allgather(send, gath, sizeof(float))) return -1;
-        DLOCAL(thallo_hip_shard_scalars(gath, 1, world, sh_aD, nullptr, nbp, thallo_sum_t{ nullptr, 0 }, scal(B), nullptr, s), "alphaN_0");
-        if (!D.failed) fin_[B] = 1;
-    }
+    const int count = (int)sums.size();
+    const ShardSum* x = sums.begin();
+    for (int i = 0; i < count; ++i) DLOCAL(thallo_hip_finish_sum(partial_sum(x[i].j), send + i, s), what_cam);
+    if (dist_allgather(send, gath, count * (long)sizeof(float))) return -1;
+    for (int i = 0; i < count; ++i) DLOCAL(thallo_hip_shard_scalars(gath + i, count, D.cfg.world, x[i].pts, nullptr, x[i].nbp, thallo_sum_t{ nullptr, 0 }, x[i].out ? x[i].out : scal(x[i].j), nullptr, s), what_sum);
+    for (int i = 0; i < count; ++i) if (!x[i].out && !D.failed) fin_[x[i].j] = 1;
+    return 0;
+}
+
+// Shard: dist_gn_shard = dist_gn_shard_begin, L x (dist_three_launch_iter over the whole vector, dist_shard_exchange_iter), the linear update.
+// A rank holds its cameras, ALL points and the observations of its cameras.  J p is local; the camera block of J^T(J p) is complete, the point block
+// is a partial sum -> all-reduce (3P floats per PCG iteration); then every rank holds identical point blocks of Ap, r, p, delta and updates them
+// redundantly.  The scalars: the camera parts of [alphaD | N, S1, S2] travel in one tiny all-gather and are added in rank order, the point parts
+// are computed by every rank for itself after the all-reduce (thallo_hip_block_sums) -- identical inputs, identical bits.
+int Plan::dist_gn_shard(int L)
+{
+    DistState& D = *dist_;
+    if (dist_gn_shard_begin()) return -1;
     const int cam_slots = plugin->shared_split_slots();
     for (int k = 0; k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        if (!D.failed) {
-            {   TimedLaunch t(ctx, "PCGUpdate");
-                DLOCAL(thallo_hip_pcg_update(v_.r, v_.Ap, pc ? v_.pre : nullptr, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, v_.n, k == 0,
-                                             sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGUpdate launch");
-            }
-            const thallo_fin_t nofin = { { nullptr, 0 }, nullptr, nullptr, nullptr };
-            if (!D.failed) {
-                nb = plugin->apply_jtj_sums(ctx, v_, v_.p[cur_ ^ 1], v_.Ap, slot(jD), nofin);
-                if (nb < 0 || cam_slots < 1 || cam_slots >= nb) dist_fail("PCGStep1 launch failed (%d)", nb);
-            }
-            if (!D.failed) set_nb(jD, nb);
-        }
-        cur_ ^= 1;
-        TimedLaunch t(ctx, "ShardExchange");
-        if (dist_allreduce(v_.Ap + off, len)) return -1;
-        int nbp = 0;
-        if (!D.failed) { nbp = thallo_hip_block_sums(v_.p[cur_] + off, v_.Ap + off, v_.r + off, pc ? v_.pre + off : nullptr, len, sh_aD, sh_s3, s); if (nbp < 0) dist_fail("block sums launch failed (%d)", nbp); }
-        if (D.p2p_on) {       // no collective: the ranks' camera sums as granules, the point sums behind them (thallo_hip_dist_xscalars_shard)
-            int rc = thallo_hip_dist_xscalars_shard(D.d, D.xr, D.failed ? thallo_sum_t{ (const float*)D.send.ptr, 1 } : sum(jN), D.failed ? (const float*)D.send.ptr : slot(jD), v_.s12,
-                                                    D.failed ? 1 : cam_slots, sh_aD, sh_s3, D.failed ? 1 : nbp, D.failed ? 1 : 0, scal(jD), scal(jB), s);
-            if (D.inject > 0 && !D.failed && --D.inject == 0) rc = -999;
-            if (rc < 0 && !D.failed) dist_fail("device-side scalar exchange failed (%d)", rc);
-            if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
-            continue;
-        }
-        DLOCAL(thallo_hip_slab_pack_iter(v_.Ap, none, slot(jD), v_.s12, cam_slots, send, s), "shard pack");      // the camera launch's slots only
-        if (dist_allgather(send, gath, 7 * (long)sizeof(float))) return -1;
-        DLOCAL(thallo_hip_shard_scalars(gath, 7, world, sh_aD, sh_s3, nbp, sum(jN), scal(jD), scal(jB), s), "shard scalars");
-        if (!D.failed) { fin_[jD] = 1; set_nb(jB, 1); fin_[jB] = 1; }
+        const int nb = dist_three_launch_iter(k, 0, v_.n);
+        if (!D.failed && (cam_slots < 1 || cam_slots >= nb)) dist_fail("PCGStep1 launch failed (%d)", nb);
+        if (dist_shard_exchange_iter(k, cam_slots)) return -1;
     }
     if (!D.failed) { last_l_iters = L; linear_update_tail(L, false); }   // cameras of this rank + all points (replicated, bit for bit)
+    return 0;
+}
+
+int Plan::dist_gn_shard_begin()
+{
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int B = 2;
+    const long off = D.sh_off, len = D.sh_len;
+    const bool pc = plugin->use_preconditioner();
+    float* sh_aD = (float*)D.sh_aD.ptr;
+    dist_pcg_init();                                                     // r = -J^T F and the RAW diagonal (v_.diag), both partial on the shared block
+    TimedLaunch t(ctx, "ShardExchangeInit");
+    if (dist_allreduce(v_.r + off, len) || dist_allreduce(v_.diag + off, len)) return -1;
+    // PCGInit1_Finish on the two blocks separately: pre = guardedInvert(diag), z = pre r, alphaN partials
+    const TwoBlocks nb = dist_on_blocks(slot(B), sh_aD, "PCGInit1_Finish", [&](long o, long n, float* partials) {
+        return thallo_hip_pcg_init_finish(v_.r + o, v_.diag + o, v_.pre + o, v_.z + o, n, pc ? 1 : 0, partials, s); });
+    if (!D.failed) set_nb(B, nb.cam);
+    return dist_shard_sums({ { B, sh_aD, nb.pt, nullptr } }, "alphaN sum", "alphaN_0");
+}
+
+int Plan::dist_shard_exchange_iter(int k, int cam_slots)
+{   // "ShardExchange": the point block of A p added over the ranks; its sums, which every rank then takes for itself; the ranks' camera sums in front of them
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int jN = 2 + 2 * k, jD = jN + 1, jB = jN + 2;
+    const long off = D.sh_off, len = D.sh_len;
+    const bool pc = plugin->use_preconditioner();
+    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
+    float* sh_aD = (float*)D.sh_aD.ptr; double* sh_s3 = (double*)D.sh_s3.ptr;
+    TimedLaunch t(ctx, "ShardExchange");
+    if (dist_allreduce(v_.Ap + off, len)) return -1;
+    int nbp = 0;
+    if (!D.failed) { nbp = thallo_hip_block_sums(v_.p[cur_] + off, v_.Ap + off, v_.r + off, pc ? v_.pre + off : nullptr, len, sh_aD, sh_s3, s); if (nbp < 0) dist_fail("block sums launch failed (%d)", nbp); }
+    if (D.p2p_on) {       // no collective: the ranks' camera sums as granules, the point sums behind them (thallo_hip_dist_xscalars_shard)
+        const DistPayload w = dist_payload(sum(jN), slot(jD), cam_slots);
+        dist_exchange_rc(thallo_hip_dist_xscalars_shard(D.d, D.xr, w.sum, w.slot, v_.s12, w.nb, sh_aD, sh_s3, D.failed ? 1 : nbp, w.poison, scal(jD), scal(jB), s), "device-side scalar exchange");
+    } else {
+        DLOCAL(thallo_hip_slab_pack_iter(v_.Ap, segs({}), slot(jD), v_.s12, cam_slots, send, s), "shard pack");      // the camera launch's slots only
+        if (dist_allgather(send, gath, 7 * (long)sizeof(float))) return -1;
+        DLOCAL(thallo_hip_shard_scalars(gath, 7, D.cfg.world, sh_aD, sh_s3, nbp, sum(jN), scal(jD), scal(jB), s), "shard scalars");
+    }
+    if (!D.failed) words_done(k);
     return 0;
 }
 
@@ -1184,125 +1209,152 @@ int Plan::dist_gn_shard(int L)
 // every element-wise kernel (PCGFinalizeDiagonal, PCGStep1_Finish, PCGStep2 and its halves) runs on the two blocks separately -- the camera block's partial sums travel in one
 // tiny all-gather and are added in rank order, the point block's are added by every rank for itself behind them (identical inputs, identical bits) -- so alpha, beta, q, the
 // zeta test, the model cost and the trust region are the same words on every rank and the replicated point unknowns stay bit-identical, accepted and reverted steps alike.
+// step_lm_shard = lm_shard_setup, lm_shard_loop (the residual reset: lm_shard_residual_reset), lm_shard_finish; a part that returns false (a collective itself failed) ends the
+// step with 0 and leaves the coarse timers it has started running.
+struct Plan::ShardLm {      // what the parts of one step share.  Slots as in LmStep: QS q, B + 2k .. alphaN_k, alphaD_k, betaN_k; T0, T1 the model cost's two sums
+    const int L, T0, T1, period, ev_iter;
+    static constexpr int B = 2, QS = 1;
+    float *ptA, *ptB;       // the point block's partials of up to two sums per exchange
+    float* lmst;            // 8 words: Q0, gate, iterations done, | dJJd, db, -
+    int ev_lin;
+};
+static const char* const kCamSum = "camera block sum";
+static const char* const kShardSum = "shard sum";
+
 int Plan::step_lm_shard(int ev_iter)
+{
+    const int L = sp.lIterations;
+    ShardLm st = { L, 2 * L + 4, 2 * L + 5, sp.residual_reset_period > 0 ? sp.residual_reset_period : (1 << 30), ev_iter, nullptr, nullptr, (float*)scratch_.ptr + 16, -1 };
+    if (!lm_shard_setup(st)) return 0;
+    {   GateOff gate_off(ctx, reinterpret_cast<const unsigned*>(st.lmst) + 1);
+        if (!lm_shard_loop(st)) return 0;
+    }
+    return lm_shard_finish(st);
+}
+
+// Vectors, the trust region's start, PCGInit1, r and the raw diagonal all-reduced on the point block, PCGFinalizeDiagonal on the two blocks, alphaN_0, the LM state reset
+bool Plan::lm_shard_setup(ShardLm& st)
 {
     DistState& D = *dist_;
     hipStream_t s = ctx.stream;
-    const int L = sp.lIterations, B = 2, QS = 1, T0 = 2 * L + 4, T1 = 2 * L + 5, world = D.cfg.world;
-    const long off = D.sh_off, len = D.sh_len, n_all = off + len;
+    const int B = st.B;
+    const long off = D.sh_off, len = D.sh_len;
     const bool pc = plugin->use_preconditioner();
     if (ensure_lm_vectors()) { dist_fail("out of device memory for the LM vectors"); }
     if (!D.sh_lm.ptr && D.sh_lm.alloc(THALLO_HIP_MAX_PARTIALS * sizeof(float))) dist_fail("out of device memory for the LM partials");
-    float* send = (float*)D.send.ptr; float* gath = (float*)D.gath.ptr;
-    float* ptA = (float*)D.sh_aD.ptr; float* ptB = (float*)D.sh_lm.ptr;          // the point block's partials of up to two sums per exchange
-    float* lmst = (float*)scratch_.ptr + 16;                                      // 8 words: Q0, gate, iterations done, | dJJd, db, -
-    const unsigned* gate = reinterpret_cast<const unsigned*>(lmst) + 1;
+    st.ptA = (float*)D.sh_aD.ptr; st.ptB = (float*)D.sh_lm.ptr;
     const int ev_setup = timer_.start("Nonlinear Setup", s);
     lm_trust_region_at_start();
-    // words[i] = (sum over the ranks, in rank order, of the camera block's partials in slot js[i]) + the point block's partials pts[i]: ONE all-gather of `count` floats
-    auto gsum = [&](int count, const int* js, float* const* pts, const int* nbp, float* const* outs) -> int {
-        for (int i = 0; i < count; ++i) DLOCAL(thallo_hip_finish_sum(partial_sum(js[i]), send + i, s), "camera block sum");
-        if (dist_allgather(send, gath, count * (long)sizeof(float))) return -1;
-        for (int i = 0; i < count; ++i) DLOCAL(thallo_hip_shard_scalars(gath + i, count, world, pts[i], nullptr, nbp[i], thallo_sum_t{ nullptr, 0 }, outs[i], nullptr, s), "shard sum");
-        return 0;
-    };
-    auto gsum1 = [&](int j, float* pts, int nbp, float* out) { const int js[1] = { j }; float* const ps[1] = { pts }; const int ns[1] = { nbp }; float* const os[1] = { out }; return gsum(1, js, ps, ns, os); };
-    cur_ = 0;
-    int nb = 0, nbc = 0, nbp = 0, nbq = 0;
-    if (!D.failed) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); if (nb < 0) dist_fail("PCGInit1 launch failed (%d)", nb); }      // r = -J^T F and the RAW diagonal, both partial on the point block
+    dist_pcg_init();                                                  // r = -J^T F and the RAW diagonal, both partial on the point block
     {   TimedLaunch t(ctx, "ShardExchangeInit");
-        if (dist_allreduce(v_.r + off, len) || dist_allreduce(v_.diag + off, len)) return 0;
+        if (dist_allreduce(v_.r + off, len) || dist_allreduce(v_.diag + off, len)) return false;
     }
     {   TimedLaunch t(ctx, "PCGFinalizeDiagonal");                    // :1596-1604, on the two blocks; alphaN_0 restarts from their sums
-        if (!D.failed) {
-            nbc = thallo_hip_lm_finalize_diagonal(v_.diag, v_.SSq, v_.CtC, v_.pre, v_.r, v_.b, v_.z, off, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal, sp.nIter == 0 ? 1 : 0, pc ? 1 : 0, slot(B), s);
-            nbp = thallo_hip_lm_finalize_diagonal(v_.diag + off, v_.SSq + off, v_.CtC + off, v_.pre + off, v_.r + off, v_.b + off, v_.z + off, len, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal,
-                                                  sp.nIter == 0 ? 1 : 0, pc ? 1 : 0, ptA, s);
-            if (nbc < 0 || nbp < 0) dist_fail("PCGFinalizeDiagonal launch failed (%d, %d)", nbc, nbp); else set_nb(B, nbc);
-        }
-        if (gsum1(B, ptA, nbp, scal(B))) return 0;
-        if (!D.failed) fin_[B] = 1;
+        const TwoBlocks nb = dist_on_blocks(slot(B), st.ptA, "PCGFinalizeDiagonal", [&](long o, long n, float* partials) {
+            return thallo_hip_lm_finalize_diagonal(v_.diag + o, v_.SSq + o, v_.CtC + o, v_.pre + o, v_.r + o, v_.b + o, v_.z + o, n, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal,
+                                                   sp.nIter == 0 ? 1 : 0, pc ? 1 : 0, partials, s); });
+        if (!D.failed) set_nb(B, nb.cam);
+        if (dist_shard_sums({ { B, st.ptA, nb.pt, nullptr } }, kCamSum, kShardSum)) return false;
     }
-    DLOCAL(thallo_hip_lm_state_reset(lmst, s), "LM state reset");
+    DLOCAL(thallo_hip_lm_state_reset(st.lmst, s), "LM state reset");
     timer_.stop(ev_setup, s);
-    const int ev_lin = timer_.start("Linear Solve", s);
+    st.ev_lin = timer_.start("Linear Solve", s);
+    return true;
+}
+
+int Plan::lm_shard_apply(float* x, float* Ax, int T0, const char* what)
+{   // J^T J x on this rank's residuals -> the launch's partial count (its own sums go to the scratch slot T0); the point block of Ax is a partial sum
+    int nb = 0;
+    if (!dist_->failed) { ctx.lm_ctc = nullptr; nb = plugin->apply_jtj(ctx, x, Ax, slot(T0)); if (nb < 0) dist_fail("%s launch failed (%d)", what, nb); }
+    return nb;
+}
+
+bool Plan::lm_shard_loop(ShardLm& st)
+{
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int B = st.B, QS = st.QS;
+    const long off = D.sh_off, len = D.sh_len;
     float* p = v_.p[0];
-    GateOff gate_off(ctx, gate);
-    const int period = sp.residual_reset_period > 0 ? sp.residual_reset_period : (1 << 30);
-    for (int k = 0; k < L; ++k) {
+    for (int k = 0; k < st.L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         {   TimedLaunch t(ctx, "PCGStep3");                           // p = z + beta p  (k = 0: p = z), cameras and points
-            DLOCAL(thallo_hip_pcg_pupdate(v_.z, p, p, nullptr, n_all, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch");
+            DLOCAL(thallo_hip_pcg_pupdate(v_.z, p, p, nullptr, off + len, k == 0, prev_alpha(k).aN, prev_alpha(k).aD, sum(jN), s), "PCGStep3 launch");
         }
-        if (!D.failed) { ctx.lm_ctc = nullptr; nb = plugin->apply_jtj(ctx, p, v_.Ap, slot(T0)); if (nb < 0) dist_fail("PCGStep1 launch failed (%d)", nb); }      // J^T J p: the point block a partial sum
+        lm_shard_apply(p, v_.Ap, st.T0, "PCGStep1");                  // J^T J p
         {   TimedLaunch t(ctx, "ShardExchange");
-            if (dist_allreduce(v_.Ap + off, len)) return 0;
+            if (dist_allreduce(v_.Ap + off, len)) return false;
         }
         {   TimedLaunch t(ctx, "PCGStep1_Finish");                    // + CtC p ; alphaD  (:777-787), AFTER the all-reduce: CtC p must enter once
-            if (!D.failed) {
-                nbc = thallo_hip_lm_step1_finish(v_.Ap, v_.CtC, p, off, slot(jD), s);
-                nbp = thallo_hip_lm_step1_finish(v_.Ap + off, v_.CtC + off, p + off, len, ptA, s);
-                if (nbc < 0 || nbp < 0) dist_fail("PCGStep1_Finish launch failed (%d, %d)", nbc, nbp); else set_nb(jD, nbc);
-            }
-            if (gsum1(jD, ptA, nbp, scal(jD))) return 0;
-            if (!D.failed) fin_[jD] = 1;
+            const TwoBlocks nb = dist_on_blocks(slot(jD), st.ptA, "PCGStep1_Finish", [&](long o, long n, float* partials) {
+                return thallo_hip_lm_step1_finish(v_.Ap + o, v_.CtC + o, p + o, n, partials, s); });
+            if (!D.failed) set_nb(jD, nb.cam);
+            if (dist_shard_sums({ { jD, st.ptA, nb.pt, nullptr } }, kCamSum, kShardSum)) return false;
         }
-        const bool reset = ((k + 1) % period) == 0;                   // :1653-1657
-        if (reset) {
-            {   TimedLaunch t(ctx, "PCGStep2");
-                DLOCAL(thallo_hip_lm_step2_first_half(v_.delta, p, n_all, sum(jN), sum(jD), s), "PCGStep2 (first half) launch");
-            }
-            if (!D.failed) { ctx.lm_ctc = nullptr; nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); if (nb < 0) dist_fail("computeAdelta launch failed (%d)", nb); }
-            {   TimedLaunch t(ctx, "ShardExchange");
-                if (dist_allreduce(v_.Adelta + off, len)) return 0;
-            }
-            TimedLaunch t(ctx, "PCGStep2");
-            if (!D.failed) {
-                const int f0 = thallo_hip_lm_step1_finish(v_.Adelta, v_.CtC, v_.delta, off, slot(T1), s), f1 = thallo_hip_lm_step1_finish(v_.Adelta + off, v_.CtC + off, v_.delta + off, len, ptA, s);
-                nbc = thallo_hip_lm_step2_second_half(v_.r, v_.b, v_.Adelta, v_.pre, v_.z, v_.delta, off, slot(jB), slot(QS), s);
-                nbp = thallo_hip_lm_step2_second_half(v_.r + off, v_.b + off, v_.Adelta + off, v_.pre + off, v_.z + off, v_.delta + off, len, ptA, ptB, s);
-                if (f0 < 0 || f1 < 0 || nbc < 0 || nbp < 0) dist_fail("PCGStep2 (residual reset) launch failed (%d, %d, %d, %d)", f0, f1, nbc, nbp);
-            }
+        TwoBlocks nb;                                                 // PCGStep2's: the partials of betaN_k, and as many of q_{k+1}
+        if (((k + 1) % st.period) == 0) {                             // :1653-1657
+            if (!lm_shard_residual_reset(st, k, nb)) return false;
         } else {
             TimedLaunch t(ctx, "PCGStep2");
-            if (!D.failed) {
-                nbc = thallo_hip_pcg_step2_full(v_.delta, p, v_.r, v_.Ap, v_.pre, v_.z, v_.b, off, sum(jN), sum(jD), slot(jB), slot(QS), 1, s);
-                nbp = thallo_hip_pcg_step2_full(v_.delta + off, p + off, v_.r + off, v_.Ap + off, v_.pre + off, v_.z + off, v_.b + off, len, sum(jN), sum(jD), ptA, ptB, 1, s);
-                if (nbc < 0 || nbp < 0) dist_fail("PCGStep2 launch failed (%d, %d)", nbc, nbp);
-            }
+            nb = dist_on_blocks(slot(jB), st.ptA, "PCGStep2", [&](long o, long n, float* partials) {
+                return thallo_hip_pcg_step2_full(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), partials, partials == st.ptA ? st.ptB : slot(QS), 1, s); });
         }
-        nbq = nbp;
-        if (!D.failed) { set_nb(jB, nbc); set_nb(QS, nbc); }
-        {   const int js[2] = { jB, QS }; float* const ps[2] = { ptA, ptB }; const int ns[2] = { nbp, nbq }; float* const os[2] = { scal(jB), scal(QS) };
-            if (gsum(2, js, ps, ns, os)) return 0;                     // betaN_k and q_{k+1} over all ranks
-            if (!D.failed) { fin_[jB] = 1; fin_[QS] = 1; }
-        }
+        if (!D.failed) { set_nb(jB, nb.cam); set_nb(QS, nb.cam); }
+        if (dist_shard_sums({ { jB, st.ptA, nb.pt, nullptr }, { QS, st.ptB, nb.pt, nullptr } }, kCamSum, kShardSum)) return false;      // betaN_k and q_{k+1} over all ranks
         {   TimedLaunch t(ctx, "PCGZeta");
-            DLOCAL(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, lmst, s), "PCGZeta launch");
+            DLOCAL(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, st.lmst, s), "PCGZeta launch");
         }
     }
-    gate_off.off();
-    timer_.stop(ev_lin, s);
+    return true;
+}
+
+bool Plan::lm_shard_residual_reset(ShardLm& st, int k, TwoBlocks& nb)
+{   // PCGStep2 of an iteration that restarts the residual: delta += alpha p; r = b - (J^T J + CtC) delta, whose point block takes an all-reduce of its own; z, betaN, q
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int jN = st.B + 2 * k, jD = jN + 1, jB = jN + 2;
+    const long off = D.sh_off, len = D.sh_len;
+    {   TimedLaunch t(ctx, "PCGStep2");
+        DLOCAL(thallo_hip_lm_step2_first_half(v_.delta, v_.p[0], off + len, sum(jN), sum(jD), s), "PCGStep2 (first half) launch");
+    }
+    lm_shard_apply(v_.delta, v_.Adelta, st.T0, "computeAdelta");
+    {   TimedLaunch t(ctx, "ShardExchange");
+        if (dist_allreduce(v_.Adelta + off, len)) return false;
+    }
+    TimedLaunch t(ctx, "PCGStep2");
+    if (!D.failed) {      // (two kernels on the two blocks each, and ONE failure with the four codes: by hand)
+        const int f0 = thallo_hip_lm_step1_finish(v_.Adelta, v_.CtC, v_.delta, off, slot(st.T1), s), f1 = thallo_hip_lm_step1_finish(v_.Adelta + off, v_.CtC + off, v_.delta + off, len, st.ptA, s);
+        nb.cam = thallo_hip_lm_step2_second_half(v_.r, v_.b, v_.Adelta, v_.pre, v_.z, v_.delta, off, slot(jB), slot(st.QS), s);
+        nb.pt = thallo_hip_lm_step2_second_half(v_.r + off, v_.b + off, v_.Adelta + off, v_.pre + off, v_.z + off, v_.delta + off, len, st.ptA, st.ptB, s);
+        if (f0 < 0 || f1 < 0 || nb.cam < 0 || nb.pt < 0) dist_fail("PCGStep2 (residual reset) launch failed (%d, %d, %d, %d)", f0, f1, nb.cam, nb.pt);
+    }
+    return true;
+}
+
+// The model cost's two sums, the unknowns saved and updated, the cost over all ranks, the report read back, accept or revert
+int Plan::lm_shard_finish(ShardLm& st)
+{
+    DistState& D = *dist_;
+    hipStream_t s = ctx.stream;
+    const int T0 = st.T0, T1 = st.T1;
+    timer_.stop(st.ev_lin, s);
     const int ev_fin = timer_.start("Nonlinear Finish", s);
     // model cost change = delta.b - 0.5 delta.(J^T J delta): both sums are LINEAR in the ranks' contributions -- the applyJTJ launch's own partials of delta.(its part of
     // J^T J delta) add up over the ranks to the whole (no all-reduce of the vector), delta.b over the camera blocks + the point block once
-    if (!D.failed) { ctx.lm_ctc = nullptr; nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); if (nb < 0) dist_fail("model cost: applyJTJ launch failed (%d)", nb); else set_nb(T0, nb); }
-    if (!D.failed) {
-        nbc = thallo_hip_dot(v_.delta, v_.b, off, slot(T1), s); nbp = thallo_hip_dot(v_.delta + off, v_.b + off, len, ptB, s);
-        if (nbc < 0 || nbp < 0) dist_fail("model cost: dot launch failed (%d, %d)", nbc, nbp); else set_nb(T1, nbc);
-    }
-    {   const int js[2] = { T0, T1 }; float* const ps[2] = { ptA, ptB }; const int ns[2] = { 0, nbp }; float* const os[2] = { lmst + 3, lmst + 4 };
-        if (gsum(2, js, ps, ns, os)) return 0;
-    }
+    const int nb = lm_shard_apply(v_.delta, v_.Adelta, T0, "model cost: applyJTJ");
+    if (!D.failed) set_nb(T0, nb);
+    const TwoBlocks nbd = dist_on_blocks(slot(T1), st.ptB, "model cost: dot", [&](long o, long n, float* partials) { return thallo_hip_dot(v_.delta + o, v_.b + o, n, partials, s); });
+    if (!D.failed) set_nb(T1, nbd.cam);
+    if (dist_shard_sums({ { T0, st.ptA, 0, st.lmst + 3 }, { T1, st.ptB, nbd.pt, st.lmst + 4 } }, kCamSum, kShardSum)) return 0;
     if (!D.failed) {
         DCOPY(copy_unknowns(false), "savePreviousUnknowns");
         linear_update_tail(0, false);                                 // X += delta: this rank's cameras, all points (replicated)
     }
     const float newCost = dist_cost();                                // rank-ordered sum of the ranks' costs; a failed rank makes EVERY rank stop here
-    if (!ready_ || !std::isfinite(newCost)) { timer_.stop(ev_fin, s); timer_.stop(ev_iter, s); if (!finalized_) { finalized_ = true; } return 0; }
+    if (!ready_ || !std::isfinite(newCost)) { timer_.stop(ev_fin, s); timer_.stop(st.ev_iter, s); if (!finalized_) { finalized_ = true; } return 0; }
     float rep[8] = { 0 };
-    if (hipMemcpyAsync(rep, lmst, sizeof(rep), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { set_error("distributed: LM report read-back failed"); return 0; }
-    return lm_accept_or_revert(rep[3], rep[4], newCost, lm_iterations_done(rep, L), ev_fin, ev_iter);
+    if (hipMemcpyAsync(rep, st.lmst, sizeof(rep), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { set_error("distributed: LM report read-back failed"); return 0; }
+    return lm_accept_or_revert(rep[3], rep[4], newCost, lm_iterations_done(rep, st.L), ev_fin, st.ev_iter);
 }
 
 // ---- the device-side exchange's self-check.  It is used only if, ON THIS TOPOLOGY, it moves known patterns (Slab: reproduces the all-gather path's scalars) and no
