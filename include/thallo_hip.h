@@ -202,6 +202,10 @@ int thallo_hip_linear_update2(float* X, const float* delta, const float* p_older
 #define THALLO_HIP_MAX_UPDATE_TERMS 32
 typedef struct { const float* p[THALLO_HIP_MAX_UPDATE_TERMS]; thallo_sum_t alphaN[THALLO_HIP_MAX_UPDATE_TERMS], alphaD[THALLO_HIP_MAX_UPDATE_TERMS]; int count; } thallo_update_terms_t;
 int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups /* 0: as many as the flat kernels use */, thallo_stream_t stream);
+/* ... for the caller who knows that delta is zero (nothing has touched it since the GN step began): the running value starts at 0.0f and delta is NOT read -- the
+   bits of thallo_hip_linear_update_n on a delta of stored zeros, without the pass that stores them and the pass that reads them back.  X == NULL: delta is
+   written (whatever it held before); X != NULL: delta is neither read nor written. */
+int thallo_hip_linear_update_n_from_zero(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream);
 /* Known-answer test of the wave64 primitives of the generated kernels (ballot, peer grouping by key, grouped sums: thallo.t:3380-3399 / cuda_util.t:334-427 for 64-wide waves),
    the reference's tests/cuda_unit_tests/{ballot,get_peers,reduce_peers}.t restated for 64 lanes; one wave, compiled from the generated kernels' own prelude with hipRTC:
    out_ballot = max over lanes of ballot(lane != 0) = 0xFFFFFFFFFFFFFFFE; out_peers = sum over lanes of (peer mask of key lane % 4) & 0xFF = 255 * 64 / 4;

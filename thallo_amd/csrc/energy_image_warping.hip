@@ -345,7 +345,7 @@ __global__ __launch_bounds__(BLOCK) void k_step2_iw(float4* __restrict__ r, cons
 }
 
 // ------------------------------------------------------------------------------------------ PCGInit1 (+_Finish)
-// Once per GN iteration: evalJTF in gather form, guardedInvert, z = M^-1 r, p_prev = 0, delta = 0, the
+// Once per GN iteration: evalJTF in gather form, guardedInvert, z = M^-1 r, p_prev = 0, delta = 0 (unless delta == NULL), the
 // (cos,sin) and validity planes, alphaN partials.  Not pipelined (1 % of a GN iteration).
 __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict__ off, const float* __restrict__ ang,
                                                 const float2* __restrict__ ur, const float2* __restrict__ cons,
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict_
                 const float zx = mx * rx, zy = my * ry, zaa = ma * ra;
                 reinterpret_cast<float2*>(z)[pix] = make_float2(zx, zy);  z[2 * N + pix] = zaa;
                 reinterpret_cast<float2*>(p_prev)[pix] = make_float2(0.f, 0.f); p_prev[2 * N + pix] = 0.f;
-                reinterpret_cast<float2*>(delta)[pix] = make_float2(0.f, 0.f);  delta[2 * N + pix] = 0.f;
+                if (delta) { reinterpret_cast<float2*>(delta)[pix] = make_float2(0.f, 0.f);  delta[2 * N + pix] = 0.f; }      // (NULL: the caller's first update of delta starts from 0.0f itself)
                 cs[pix] = make_float2(T.c[i], T.s[i]);
                 flags[pix] = fl;
                 acc += rx * zx + ry * zy + ra * zaa;                // :701

@@ -524,51 +524,129 @@ __global__ __launch_bounds__(BLOCK) void k_linear_update2(float* __restrict__ X,
 // of `delta += alpha p` applied once per iteration in that order (round 5: the one-kernel schedule keeps a RING of p planes and touches delta once per ring
 // instead of once per iteration or two).  X != NULL: the end of a GN step, X += (the updated delta) and delta itself is not written back.
 // V4: every pointer 16-byte aligned and len a multiple of 4 (solver vectors always; caller buffers usually).
-template <bool V4>
+//
+// The head of the launch: al[j] = alpha_j = safe_div(sum_partials(alphaN_j), sum_partials(alphaD_j)) for every term, with all their memory traffic in flight
+// together instead of one term after the other (32 terms were 64 dependent round trips in every workgroup before the first plane load went out).  Lane j of
+// every wave reads term j's two descriptors; terms whose two sums are single words (the product path: the loop's launches leave words) are loaded and divided
+// by lane j of wave 0; a term with a list of partials goes to wave j mod 4, both lists loaded before the first addition, added in sum_partials' order.
+// No barrier inside: the caller's __syncthreads() publishes al.  Every lane of the workgroup must call it.
+__device__ __forceinline__ float2 sum_partials_pair(const float* __restrict__ pa, int na, const float* __restrict__ pb, int nb)
+{
+    const int lane = threadIdx.x & (THALLO_WAVE - 1);
+    constexpr int PER = THALLO_MAX_PARTIALS / THALLO_WAVE;
+    float va[PER], vb[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { const int i = lane + k * THALLO_WAVE; va[k] = i < na ? pa[i] : 0.0f; }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { const int i = lane + k * THALLO_WAVE; vb[k] = i < nb ? pb[i] : 0.0f; }
+    float sa = 0.0f, sb = 0.0f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) sa += va[k];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) sb += vb[k];
+    sa = wave_sum_all(sa); sb = wave_sum_all(sb);
+    // (one word: the word itself, as sum_partials returns it -- adding +0.0f to it would turn a -0.0f around)
+    const float wa = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, va[0])));
+    const float wb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, vb[0])));
+    return make_float2(na == 1 ? wa : sa, nb == 1 ? wb : sb);
+}
+__device__ __forceinline__ const float* wave_uniform_ptr(const float* p, int lane)
+{
+    const unsigned long long b = (unsigned long long)reinterpret_cast<uintptr_t>(p);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
+    return reinterpret_cast<const float*>((uintptr_t)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ void update_alphas(const thallo_update_terms_t& T, float* __restrict__ al)
+{
+    const int lane = threadIdx.x & (THALLO_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / THALLO_WAVE));
+    const bool mine = lane < T.count;
+    const int jl = mine ? lane : 0;
+    const float* pn = T.alphaN[jl].partials; const float* pd = T.alphaD[jl].partials;
+    const int cn = T.alphaN[jl].count, cd = T.alphaD[jl].count;
+    const bool words = cn == 1 && cd == 1;
+    if (wave == 0 && mine && words) al[lane] = safe_div<false>(pn[0], pd[0]);
+    unsigned lists = (unsigned)__ballot(mine && !words);      // (at most 32 terms)
+    lists &= 0x11111111u << wave;
+    while (lists) {
+        const int j = __builtin_ctz(lists);
+        lists &= lists - 1;
+        const float2 s = sum_partials_pair(wave_uniform_ptr(pn, j), __builtin_amdgcn_readlane(cn, j), wave_uniform_ptr(pd, j), __builtin_amdgcn_readlane(cd, j));
+        if (lane == 0) al[j] = safe_div<false>(s.x, s.y);
+    }
+}
+
+__device__ __forceinline__ void fma4(float4& d, float a, const float4& q)
+{
+    d.x = __builtin_fmaf(a, q.x, d.x); d.y = __builtin_fmaf(a, q.y, d.y); d.z = __builtin_fmaf(a, q.z, d.z); d.w = __builtin_fmaf(a, q.w, d.w);
+}
+// terms j0 .. count-1 onto the running value of float4 i: eight planes' loads in flight per lane (the terms are still applied one after the other): a background
+// launch on 256 workgroups is latency-bound -- 9 x 16 B x 65,536 threads in flight against 5 x with four
+__device__ __forceinline__ void apply_terms4(float4& d, int j, long i, const thallo_update_terms_t& T, const float* al)
+{
+    for (; j + 8 <= T.count; j += 8) {
+        float4 q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[j + u]) + i, true);      // read once, never again
+#pragma unroll
+        for (int u = 0; u < 8; ++u) fma4(d, al[j + u], q[u]);
+    }
+    for (; j + 4 <= T.count; j += 4) {
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[j + u]) + i, true);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fma4(d, al[j + u], q[u]);
+    }
+    for (; j < T.count; ++j) fma4(d, al[j], ldf4(reinterpret_cast<const float4*>(T.p[j]) + i, true));
+}
+__device__ __forceinline__ void store_update4(float* __restrict__ X, float* __restrict__ delta, long i, const float4& d)
+{
+    if (X) { float4 x = reinterpret_cast<const float4*>(X)[i]; x.x = x.x + d.x; x.y = x.y + d.y; x.z = x.z + d.z; x.w = x.w + d.w; reinterpret_cast<float4*>(X)[i] = x; }
+    else reinterpret_cast<float4*>(delta)[i] = d;
+}
+
+// ZERO: delta is known to hold zeros (the first touch of a GN step): the running value starts at 0.0f and delta is not read -- the bits of reading a stored zero.
+// What does not depend on the alphas -- the first trip's delta and its first eight planes -- is loaded before the head, so it travels while the alphas do.
+template <bool V4, bool ZERO>
 __global__ __launch_bounds__(BLOCK) void k_linear_update_n(float* __restrict__ X, float* __restrict__ delta, thallo_update_terms_t T, long len)
 {
     __shared__ float al[THALLO_HIP_MAX_UPDATE_TERMS];
-    for (int j = 0; j < T.count; ++j) {     // (wave-cooperative sums: every wave computes every alpha, in the order every other consumer uses)
-        const float a = safe_div<false>(sum_partials(T.alphaN[j].partials, T.alphaN[j].count), sum_partials(T.alphaD[j].partials, T.alphaD[j].count));
-        if (threadIdx.x == 0) al[j] = a;
-    }
-    __syncthreads();
+    const long i0 = (long)blockIdx.x * BLOCK + threadIdx.x, stride = (long)gridDim.x * BLOCK;
     if (V4) {
         const long n4 = len >> 2;
-        for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * BLOCK) {
-            float4 d = reinterpret_cast<const float4*>(delta)[i];
-            int j = 0;
-            for (; j + 8 <= T.count; j += 8) {      // eight planes' loads in flight per lane (the terms are still applied one after the other): a background launch on 256
-                float4 q[8];                        // workgroups is latency-bound -- 9 x 16 B x 65,536 threads in flight against 5 x with four
+        const bool have = i0 < n4, eight = T.count >= 8;
+        float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q[8];
+        if (have) {
+            if (!ZERO) d = reinterpret_cast<const float4*>(delta)[i0];
+            if (eight) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[j + u]) + i, true);      // read once, never again
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float a = al[j + u];
-                    d.x = __builtin_fmaf(a, q[u].x, d.x); d.y = __builtin_fmaf(a, q[u].y, d.y); d.z = __builtin_fmaf(a, q[u].z, d.z); d.w = __builtin_fmaf(a, q[u].w, d.w);
-                }
+                for (int u = 0; u < 8; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[u]) + i0, true);
             }
-            for (; j + 4 <= T.count; j += 4) {
-                float4 q[4];
+        }
+        update_alphas(T, al);
+        __syncthreads();
+        if (have) {
+            if (eight) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[j + u]) + i, true);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float a = al[j + u];
-                    d.x = __builtin_fmaf(a, q[u].x, d.x); d.y = __builtin_fmaf(a, q[u].y, d.y); d.z = __builtin_fmaf(a, q[u].z, d.z); d.w = __builtin_fmaf(a, q[u].w, d.w);
-                }
+                for (int u = 0; u < 8; ++u) fma4(d, al[u], q[u]);
             }
-            for (; j < T.count; ++j) {
-                const float4 q = ldf4(reinterpret_cast<const float4*>(T.p[j]) + i, true);
-                const float a = al[j];
-                d.x = __builtin_fmaf(a, q.x, d.x); d.y = __builtin_fmaf(a, q.y, d.y); d.z = __builtin_fmaf(a, q.z, d.z); d.w = __builtin_fmaf(a, q.w, d.w);
-            }
-            if (X) { float4 x = reinterpret_cast<const float4*>(X)[i]; x.x = x.x + d.x; x.y = x.y + d.y; x.z = x.z + d.z; x.w = x.w + d.w; reinterpret_cast<float4*>(X)[i] = x; }
-            else reinterpret_cast<float4*>(delta)[i] = d;
+            apply_terms4(d, eight ? 8 : 0, i0, T, al);
+            store_update4(X, delta, i0, d);
+        }
+        for (long i = i0 + stride; i < n4; i += stride) {
+            float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (!ZERO) e = reinterpret_cast<const float4*>(delta)[i];
+            apply_terms4(e, 0, i, T, al);
+            store_update4(X, delta, i, e);
         }
     } else {
-        for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < len; i += (long)gridDim.x * BLOCK) {
-            float d = delta[i];
+        float d = 0.0f;
+        if (!ZERO && i0 < len) d = delta[i0];
+        update_alphas(T, al);
+        __syncthreads();
+        for (long i = i0; i < len; i += stride) {
+            if (i != i0) d = ZERO ? 0.0f : delta[i];
             for (int j = 0; j < T.count; ++j) d = __builtin_fmaf(al[j], T.p[j][i], d);
             if (X) X[i] = X[i] + d; else delta[i] = d;
         }
@@ -1083,7 +1161,7 @@ int thallo_hip_linear_update2(float* X, const float* delta, const float* p_older
     return e ? e : grid;
 }
 
-int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream)
+static int linear_update_n(bool zero, float* X, float* delta, const thallo_update_terms_t& terms, long len, int max_workgroups, thallo_stream_t stream)
 {
     if (!delta || len < 0 || terms.count < 0 || terms.count > THALLO_HIP_MAX_UPDATE_TERMS) return -(int)hipErrorInvalidValue;
     bool v4 = !(len & 3) && !(((uintptr_t)X | (uintptr_t)delta) & 15);
@@ -1091,13 +1169,21 @@ int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t ter
         if (!terms.p[j] || !terms.alphaN[j].partials || !terms.alphaD[j].partials || terms.alphaN[j].count < 1 || terms.alphaD[j].count < 1) return -(int)hipErrorInvalidValue;
         if ((uintptr_t)terms.p[j] & 15) v4 = false;
     }
-    if (len == 0 || (terms.count == 0 && !X)) return 0;
+    if (len == 0 || (terms.count == 0 && !X && !zero)) return 0;      // (zero, no terms, no X: the zeros themselves are what delta is left with)
     int grid = flat_grid(v4 ? len >> 2 : len, 2 * cu_count());
     if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;      // (a background update next to the PCG loop's launches: a share of the bandwidth, not all of it)
-    if (v4) hipLaunchKernelGGL(k_linear_update_n<true>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, X, delta, terms, len);
-    else    hipLaunchKernelGGL(k_linear_update_n<false>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, X, delta, terms, len);
+    auto kernel = v4 ? (zero ? k_linear_update_n<true, true> : k_linear_update_n<true, false>) : (zero ? k_linear_update_n<false, true> : k_linear_update_n<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, X, delta, terms, len);
     int e = check_launch();
     return e ? e : grid;
+}
+int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream)
+{
+    return linear_update_n(false, X, delta, terms, len, max_workgroups, stream);
+}
+int thallo_hip_linear_update_n_from_zero(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream)
+{
+    return linear_update_n(true, X, delta, terms, len, max_workgroups, stream);
 }
 
 int thallo_hip_finish_sum(thallo_sum_t sum, float* out, thallo_stream_t stream)

@@ -151,6 +151,7 @@ public:
     // implement pcg_step1_mode; the driver then finishes the GN step with up to two pending alpha*p terms.
     virtual bool batches_delta() const { return false; }
     virtual bool takes_any_p_plane() const { return false; }
+    virtual bool init_takes_null_delta() const { return false; }      // pcg_init with v.delta == NULL stores no zeros there (the ring's first delta update starts from 0.0f instead)
     // iterations k0 .. k1-1 of the one-kernel GN loop in ONE launch (image_warping's persistent marching loop): planes[k % n] as in the ring schedule, the plan's
     // slot layout passed through (thallo_hip_iw_pcg_march_persist).  Returns the workgroup count or < 0
     virtual bool persist_ok() const { return false; }

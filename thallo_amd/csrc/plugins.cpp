@@ -296,6 +296,7 @@ public:
                                        v.z, v.p[cur], v.p[cur ^ 1], v.delta, v.Ap, first ? 1 : 0, aN, aD, bN, none, none, (const int*)irregular.ptr, v.r, out, c.stream);
     }
     bool batches_delta() const override { return true; }
+    bool init_takes_null_delta() const override { return true; }
     bool takes_any_p_plane() const override { return march_; }      // (whole images and -- round 6 -- row slabs: the marching kernels keep the ghost rows of whatever plane they write current)
     bool persist_ok() const override { return persist_; }
 #ifdef THALLO_RESEARCH

@@ -96,9 +96,34 @@ int CoarseTimer::start(const char* name, hipStream_t s)
     return (int)events.size() - 1;
 }
 void CoarseTimer::stop(int idx, hipStream_t s) { if (idx >= 0) hipEventRecord(events[idx].end, s); }
+int CoarseTimer::start_with(int outer, const char* name, hipStream_t s)
+{
+    if (outer < 0) return start(name, s);
+    Info i; i.name = name; i.start = events[outer].start; i.owns_start = false; i.end = nullptr;
+    HIP_OK(hipEventCreate(&i.end));
+    events.push_back(i);
+    return (int)events.size() - 1;
+}
+int CoarseTimer::stop_start(int idx, const char* name, hipStream_t s)
+{
+    if (idx < 0) return start(name, s);
+    stop(idx, s);
+    Info i; i.name = name; i.start = events[idx].end; i.owns_start = false; i.end = nullptr;
+    HIP_OK(hipEventCreate(&i.end));
+    events.push_back(i);
+    return (int)events.size() - 1;
+}
+void CoarseTimer::stop_both(int idx, int outer, hipStream_t s)
+{
+    stop(idx, s);
+    if (idx < 0 || outer < 0) { if (idx < 0) stop(outer, s); return; }
+    Info& o = events[outer];
+    if (o.owns_end && o.end) hipEventDestroy(o.end);
+    o.end = events[idx].end; o.owns_end = false;
+}
 void CoarseTimer::cleanup()
 {
-    for (auto& i : events) { if (i.start) hipEventDestroy(i.start); if (i.end) hipEventDestroy(i.end); }
+    for (auto& i : events) { if (i.start && i.owns_start) hipEventDestroy(i.start); if (i.end && i.owns_end) hipEventDestroy(i.end); }
     events.clear();
 }
 
@@ -241,6 +266,7 @@ const char* env_switch(const char* name)
         { "THALLO_FRONTEND_COMPUTED", "frontend_computed" },    // 0: computed arrays (expr:get) inlined at every access instead of materialized by a precompute kernel (rounds 1-5; A/B)
         { "THALLO_FRONTEND_PRELOAD", "frontend_preload" },      // 0: every residual instance of a generated merged gather kernel loads for itself (round 4's lowering)
         { "THALLO_INC_LANES", "inc_lanes" },                    // N (a power of two <= 64): lanes per owner in the generated index-map gather kernels (default: by list length and owner count)
+        { "THALLO_DELTA_FIRST_TOUCH", "delta_first_touch" },    // 0: PCGInit1 zeroes delta in every schedule, and the ring schedule's first delta update of a GN step reads those zeros back
         { "THALLO_PERSIST", "persist" },                        // 1: iterations 1 .. L-1 of a GN step of image_warping's marching kernel as persistent launches (bit-identical, measured slower)
     };
     for (const char* k : known) if (!strcmp(k, name)) return getenv(name);
@@ -274,6 +300,7 @@ void Plan::read_ab_switches()
     batch_delta_   = delta_planes_ != 0;
     lm_fold_p_     = !off("THALLO_LM_FOLD_P");
     lm_fold_step_  = !off("THALLO_LM_FOLD_STEP");
+    delta_first_touch_ = !off("THALLO_DELTA_FIRST_TOUCH");
 }
 
 void Plan::set_param(const char* name, const void* value)
@@ -415,6 +442,7 @@ int Plan::step(void** params)
         else { if (!finalized_) finalize(); return 0; }
     }
     const int ev_iter = timer_.start("Nonlinear Iteration", ctx.stream);
+    bufs_at_step_ = bufs_.size();
     if (dist_ && lm_ && !dist_->runs_lm()) { set_error("distributed: %s runs Gauss-Newton only across ranks", plugin->name()); if (!finalized_) finalize(); return 0; }
     const int rc = lm_ && dist_ && dist_->form == DistForm::Shard ? step_lm_shard(ev_iter) : lm_ ? step_lm(ev_iter) : dist_ ? step_gn_slab(ev_iter) : step_gn(ev_iter);
     if (rc == 1 && sp.max_solver_time_in_seconds > 0.0f && ev_total_ >= 0) {   // :1767-1779
@@ -458,30 +486,31 @@ Plan::Owned Plan::owned_range(size_t u) const
 
 // The head and the tail that every PCG-loop form of a GN step shares (the direct solve records other coarse events and keeps its own lines).
 // gn_begin: "Nonlinear Setup" around PCGInit1 (alphaN_0's partials into slot B = 2), "Linear Solve" started; false: the launch failed, the step ends.
-bool Plan::gn_begin(int& ev_lin)
+// delta_unset: PCGInit1 stores no zeros into delta -- the caller has proved that this step's first reader of delta is a launch that takes "delta is zero" instead.
+bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
 {
     hipStream_t s = ctx.stream;
-    const int ev_setup = timer_.start("Nonlinear Setup", s);
+    // (a step that had to allocate -- the first one, or the first after lIterations changed -- has enqueued clears behind "Nonlinear Iteration"'s start: a record of its own)
+    const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
     cur_ = 0;
-    const int nb = plugin->pcg_init(ctx, v_, cur_, slot(2));
+    SolverVectors v_init = v_;
+    if (delta_unset) v_init.delta = nullptr;
+    const int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
     set_nb(2, nb); finish(2);
-    timer_.stop(ev_setup, s);
-    ev_lin = timer_.start("Linear Solve", s);
+    ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
     return true;
 }
 // gn_finish: the loop is enqueued, "Nonlinear Finish" starts (the caller's update of the unknowns follows); gn_end: the step is counted, its events end
 int Plan::gn_finish(int L, int ev_lin)
 {
     last_l_iters = L;
-    timer_.stop(ev_lin, ctx.stream);
-    return timer_.start("Nonlinear Finish", ctx.stream);
+    return timer_.stop_start(ev_lin, "Nonlinear Finish", ctx.stream);
 }
 int Plan::gn_end(int ev_fin, int ev_iter)
 {
     sp.nIter++;
-    timer_.stop(ev_fin, ctx.stream);
-    timer_.stop(ev_iter, ctx.stream);
+    timer_.stop_both(ev_fin, ev_iter, ctx.stream);
     return 1;
 }
 
@@ -507,7 +536,7 @@ int Plan::step_gn(int ev_iter)
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
     const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     int ev_lin, nb;
-    if (!gn_begin(ev_lin)) return 0;
+    if (!gn_begin(ev_iter, ev_lin)) return 0;
     const bool batched = plugin->batches_delta() && batch_delta_;      // every other delta update deferred (thallo_hip.h THALLO_IW_STEP1_MODE)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
@@ -560,15 +589,20 @@ int Plan::step_gn_one_kernel(int ev_iter)
 {
     if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
     const int L = sp.lIterations;
-    int ev_lin;
-    if (!gn_begin(ev_lin)) return 0;
-    // Round 5: a RING of p planes instead of the ping-pong pair.  Launch k writes p_k into plane k mod n and carries no delta update at all; delta is touched once
-    // per n - 1 iterations by thallo_hip_linear_update_n (every pending alpha_j p_j, oldest first, one fma each: the bits of an update per iteration) and the step's
-    // last terms ride in PCGLinearUpdate.  Per iteration and unknown 4 (12 + 24 / (n - 1)) / 12 bytes of delta traffic instead of 24 (every iteration) or 18 (every other).
     const int n_ring = ring_planes(L);
     const GnSchedule sched = gn_schedule(L, n_ring);
     const bool async = n_ring >= 2 && aux_async_ && sched != GnSchedule::Persist && aux_stream();      // (where the delta updates run: ring_flush)
+    // delta's first touch: on the ring (n_ring >= 2, so L >= 3), with the updates on the loop's own stream, no launch of the loop touches delta; the step's first
+    // PCGDeltaUpdate -- or, when every term still fits it, PCGLinearUpdate -- is its first reader and is told that delta is zero, and PCGInit1 stores no zeros there
+    // (24 B per unknown pixel less per step).  Every other schedule, and every step that ends early, never reads what PCGInit1 left out: the next step decides anew.
+    const bool delta_unset = delta_first_touch_ && n_ring >= 2 && !async && sched != GnSchedule::Persist && plugin->init_takes_null_delta();
+    int ev_lin;
+    if (!gn_begin(ev_iter, ev_lin, delta_unset)) return 0;
+    // Round 5: a RING of p planes instead of the ping-pong pair.  Launch k writes p_k into plane k mod n and carries no delta update at all; delta is touched once
+    // per n - 1 iterations by thallo_hip_linear_update_n (every pending alpha_j p_j, oldest first, one fma each: the bits of an update per iteration) and the step's
+    // last terms ride in PCGLinearUpdate.  Per iteration and unknown 4 (12 + 24 / (n - 1)) / 12 bytes of delta traffic instead of 24 (every iteration) or 18 (every other).
     GnStep st{ L, n_ring < 2 && batch_delta_ && delta_planes_ != 0 && plugin->batches_delta(), PRing(*this, n_ring, async) };
+    st.ring.delta_zero = delta_unset;
     bool done = false;
     switch (sched) {
     case GnSchedule::Persist:        done = gn_loop_persist(st); break;
@@ -702,7 +736,8 @@ int Plan::ring_flush(PRing& R, int upto)
     while (R.next_batch(upto, T)) {
         if (!R.async) {
             TimedLaunch t(ctx, "PCGDeltaUpdate");
-            if (thallo_hip_linear_update_n(nullptr, v_.delta, T, v_.n_alloc, 0, s) < 0) return -1;
+            if ((R.delta_zero ? thallo_hip_linear_update_n_from_zero : thallo_hip_linear_update_n)(nullptr, v_.delta, T, v_.n_alloc, 0, s) < 0) return -1;
+            R.delta_zero = false;      // (all of delta is written now)
             R.synced = R.flushed;
             continue;
         }
@@ -781,7 +816,7 @@ int Plan::step_gn_resident(int ev_iter)
     if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
     const int L = sp.lIterations, B = 2;
     int ev_lin;
-    if (!gn_begin(ev_lin)) return 0;
+    if (!gn_begin(ev_iter, ev_lin)) return 0;
     const int nb = plugin->pcg_resident(ctx, v_, L, sum(B), scal(B + 1));
     if (nb < 0) { set_error("PCGLoopResident launch failed (%d)", nb); return 0; }
     for (int k = 0; k < L; ++k) { set_nb(B + 2 * k + 1, 1); words_done(k); }
@@ -800,7 +835,7 @@ int Plan::step_gn_expanded(int ev_iter)
     const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
     int ev_lin, nb;
-    if (!gn_begin(ev_lin)) return 0;
+    if (!gn_begin(ev_iter, ev_lin)) return 0;
     // THALLO_FIN_IN_KERNEL unset: the finish of iteration k-1 -- alphaD, betaN from the applyJTJ launch's partials -- is folded into the flat update of iteration k
     // (thallo_hip_pcg_update_fin: every workgroup adds the partials up for itself, the same bits), so the applyJTJ launch has no tail; one one-wave launch finishes the last iteration
     const bool defer = fin_in_kernel_ && fin_deferred_;

@@ -29,11 +29,15 @@ struct SolverParameters {   // gauss_newton.t:200-216, defaults :41-55
 // util.Timer (util.t:446-541) with hipEvents; names as in gauss_newton.t:1173,1563-1564,1611,1690
 class CoarseTimer {
 public:
-    struct Info { std::string name; hipEvent_t start, end; };
+    struct Info { std::string name; hipEvent_t start, end; bool owns_start = true, owns_end = true; };
     std::vector<Info> events;
     bool enabled = true;      // Thallo_InitializationParameters.timingLevel 0 = "No timing recorded" (Thallo.h): no events at all -- an event record is a barrier packet between two launches
     int  start(const char* name, hipStream_t s);
     void stop(int idx, hipStream_t s);
+    // One record per distinct stream position (an event record is a barrier packet between two launches):
+    int  start_with(int outer, const char* name, hipStream_t s);    // start(name) right behind start(outer), nothing enqueued between them: the new interval starts at outer's start event
+    int  stop_start(int idx, const char* name, hipStream_t s);      // stop(idx) and start(name) with nothing enqueued between them: the new interval starts at idx's end event
+    void stop_both(int idx, int outer, hipStream_t s);              // stop(idx) and stop(outer) at one position: outer ends at idx's end event
     void evaluate(Thallo_PerformanceSummary* out, bool print_table, KernelTimer* kt);
     void cleanup();
     ~CoarseTimer() { cleanup(); }
@@ -179,11 +183,12 @@ private:
     CoarseTimer timer_;
     float* host_words_ = nullptr;      // 16 pinned host words: the step's read-backs (a cost, the LM report) land here -- a copy into pageable memory is staged and synchronous
     int ev_total_ = -1;
+    size_t bufs_at_step_ = 0;       // bufs_.size() when the step's "Nonlinear Iteration" started: unchanged = no allocation (and no clear behind one) has been enqueued since
     int cur_ = 0;
 
     float* slot(int j) { return (float*)parts_.ptr + (size_t)j * THALLO_HIP_MAX_PARTIALS; }
     std::vector<char> fin_;         // slot already reduced to one word (scal(j)) by a 1-wave finish_sum launch
-    bool fin_in_kernel_ = true, one_kernel_ = true, batch_delta_ = true, lm_fold_p_ = true, lm_fold_step_ = true;   // A/B switches: read_ab_switches()
+    bool fin_in_kernel_ = true, one_kernel_ = true, batch_delta_ = true, lm_fold_p_ = true, lm_fold_step_ = true, delta_first_touch_ = true;   // A/B switches: read_ab_switches()
     int delta_planes_ = -1;         // THALLO_DELTA_PLANES (-1: unset)
     std::vector<float*> ring_;      // the ring of p planes of the one-kernel GN loop (ring_planes)
     bool ring_possible() const;     // the plugin's iteration takes any p plane, on one GPU or on a row slab of the one-kernel schedule
@@ -198,6 +203,7 @@ private:
         Plan& P;
         const int n;                                    // planes (< 2: no ring)
         const bool async;
+        bool delta_zero = false;                        // delta has not been touched since the step began and PCGInit1 left it unset: its first update starts from 0.0f (one GPU, updates on the loop's stream)
         int flushed = 0;                                // p_0 .. p_{flushed-1} are in delta, or on their way there (async)
         int synced = 0;                                 // ... and the loop's stream has waited for the updates of p_0 .. p_{synced-1}
         struct Sent { int upto; hipEvent_t done; };
@@ -266,7 +272,7 @@ private:
     bool gn_loop_deferred(GnStep& st, int k_end);       // iterations [0, k_end)
     bool gn_loop_finish_in_launch(GnStep& st);
     int  step_gn_resident(int ev_iter);
-    bool gn_begin(int& ev_lin);                         // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2, "Linear Solve" started
+    bool gn_begin(int ev_iter, int& ev_lin, bool delta_unset = false);      // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2 (delta_unset: it stores no zeros into delta), "Linear Solve" started
     int  gn_finish(int L, int ev_lin);                  // ... its tail: "Nonlinear Finish" started (the caller's update of the unknowns follows) ...
     int  gn_end(int ev_fin, int ev_iter);               // ... and the step counted, its events ended
     bool resident_used_ = false;    // a resident launch ran since the last cost evaluation (its error word is read there)
@@ -418,7 +424,8 @@ template <class Launched> bool Plan::ring_linear_update(PRing& R, int L, Launche
         const Owned o = owned_range(u);
         thallo_update_terms_t Tu = T;
         for (int j = 0; j < Tu.count; ++j) Tu.p[j] += off + o.lo;
-        if (!launched(thallo_hip_linear_update_n(plugin->unknown_ptr((int)u) + o.lo, v_.delta + off + o.lo, Tu, o.len, 0, ctx.stream))) return false;
+        // (R.delta_zero: no update has run in this step -- every image's part of delta is read for the first time here, as zeros; X is given, so delta stays unwritten)
+        if (!launched((R.delta_zero ? thallo_hip_linear_update_n_from_zero : thallo_hip_linear_update_n)(plugin->unknown_ptr((int)u) + o.lo, v_.delta + off + o.lo, Tu, o.len, 0, ctx.stream))) return false;
         off += plugin->unknown_images()[u].n_floats;
     }
     return true;
