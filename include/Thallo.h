@@ -130,6 +130,19 @@ const char* ThalloX_PlanEnergyName(Thallo_Plan* plan);
  * schedule lines), "dense [JtJ]p", "sparse [[Jt][J]]p", "dense direct solve". */
 const char* ThalloX_PlanScheduleName(Thallo_Plan* plan);
 
+/* The PCG preconditioner.  THALLOX_PRECOND_JACOBI: the reference's point Jacobi (guardedInvert(diag J^T J); in the LM branch 1 / (CtC + diag)) -- the default, and what a
+ * plan that never makes this call runs, launch for launch.  THALLOX_PRECOND_BLOCK_JACOBI: one dense block of J^T J (+ the LM diagonal) per group of unknowns that belongs
+ * together, factored once per step -- bundle_adjustment: 9 x 9 per camera, 3 x 3 per point; Gauss-Newton and ThalloX_EnableLM; one GPU; the plan then runs its unfused PCG
+ * loop (ThalloX_PlanScheduleName says so).  Between Thallo_ProblemPlan and Thallo_ProblemInit, or before a re-Init: it takes effect at the next Init.  Returns 0, or nonzero
+ * with ThalloX_LastError naming the energy and the reason: an energy without blocks (every other energy, generated ones included), a doublePrecision = 1 state, a distributed
+ * plan (ThalloX_PlanSetDistributed after this call is refused likewise), a direct-solve plan. */
+#define THALLOX_PRECOND_JACOBI       0   /* the reference's; default */
+#define THALLOX_PRECOND_BLOCK_JACOBI 1
+int ThalloX_PlanSetPreconditioner(Thallo_Plan* plan, int kind);
+/* Blocks of the last step's factorisation that were not positive definite in float32 and fell back to their point-Jacobi diagonal (they behave as under
+ * THALLOX_PRECOND_JACOBI); -1 when the block form does not run.  Synchronises the plan's stream. */
+int ThalloX_PlanPreconditionerFallbacks(Thallo_Plan* plan);
+
 /* 1 if the most recent Thallo_ProblemInit on this plan succeeded (parameters bound, plugin prepared), else 0: Init itself returns void. */
 int ThalloX_PlanReady(Thallo_Plan* plan);
 

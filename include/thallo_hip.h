@@ -746,6 +746,40 @@ int thallo_hip_ba_apply_jtj2(int C, int P, const int* cam_ptr, const int* q_pt, 
 int thallo_hip_sfs_apply_jtj_sums(int W, int H, int row0, int row1, int yoff, int Hg, const float* host_params, const float* G, const float* Wt, const unsigned char* fl,
                                   float* U, float* R, const float* p, float* Ap, float* alphaD_out, const float* r, double* s3_out, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- block-Jacobi preconditioner (block_precond.hip; opt-in, DESIGN.md "Block-Jacobi preconditioner")
+ * One dense block of J^T J per group of unknowns that belongs together instead of the reference's point Jacobi.  A REGION is `count` blocks of `size` (3 or 9)
+ * consecutive unknowns starting at `offset` of the flat vector (bundle adjustment: cameras {0, 9, C}, points {9 C, 3, P}).  H (the blocks) and G (their factors) hold the
+ * regions one after the other, each as size (size + 1) / 2 planes of `count` floats: entry (i, j), j <= i, of block b at
+ *     region_base + (i (i + 1) / 2 + j) * count + b            (thallo_hip_block_floats: floats of H or G for a region list, -1 for an invalid list)
+ * so that one lane per block reads consecutive words.  One fixed summation order per launch shape, no float atomics: bitwise reproducible. */
+#define THALLO_HIP_MAX_BLOCK_REGIONS 4
+typedef struct thallo_block_region_t {
+    long offset;
+    int  size, count;
+} thallo_block_region_t;
+typedef struct thallo_block_regions_t {
+    thallo_block_region_t r[THALLO_HIP_MAX_BLOCK_REGIONS];
+    int n;
+} thallo_block_regions_t;
+long thallo_hip_block_floats(thallo_block_regions_t regions);
+/* Bundle adjustment's blocks, once per GN / LM step behind thallo_hip_ba_compute_j + thallo_hip_ba_pack_point_blocks: H = the lower triangles of sum J_c^T J_c over both
+ * residual rows of a camera's observations (45 floats per camera, from Jb through cam_ptr) and of a point's (6 floats, from JP through pt_ptr).  The diagonal entries are the
+ * sums thallo_hip_ba_pcg_init leaves in diag_out, added in the same order.  A camera or point nothing observes gets a zero block. */
+int thallo_hip_ba_block_diag(int C, int P, const int* cam_ptr, const int* pt_ptr, const float* Jb, const float* JP, float* H, thallo_stream_t stream);
+/* B = H + diag(shift) (shift: a flat vector -- the LM CtC -- or NULL); s_i = 1 / sqrt(B_ii); L L^T = S B S (Cholesky); G = L^-1 S.  Then M^-1 r = G^T (G r), symmetric positive
+ * definite however G is rounded.  A block with a B_ii or a pivot that is not a positive finite number, or whose G is not finite, becomes G = diag(sqrt(pre_i)) -- the
+ * point-Jacobi M^-1 the caller already holds in `pre` -- and is counted: status[0] = number of such blocks of this launch. */
+int thallo_hip_block_factor(thallo_block_regions_t regions, const float* H, const float* shift, const float* pre, float* G, unsigned* status, thallo_stream_t stream);
+/* z = G^T (G r); partials of r . z (returns their number).  gate: non-NULL and non-zero on the device = the launch does nothing (the LM loop's gate, thallo_hip_lm_zeta). */
+int thallo_hip_block_apply(thallo_block_regions_t regions, const float* G, const float* r, float* z, float* rz_out, const unsigned* gate, thallo_stream_t stream);
+/* thallo_hip_pcg_step2 with the block preconditioner: alpha = alphaN / alphaD (0 if alphaD == 0); r -= alpha Ap; z = G^T (G r); betaN partials = sum z . r. */
+int thallo_hip_block_step2(thallo_block_regions_t regions, const float* G, float* r, const float* Ap, float* z, thallo_sum_t alphaN, thallo_sum_t alphaD, float* betaN_out,
+                           thallo_stream_t stream);
+/* thallo_hip_pcg_step2_full (lm = 1, b given) with the block preconditioner: delta += alpha p; r -= alpha Ap; z = G^T (G r); partials of betaN = z . r and of
+ * q = 0.5 delta . (r + b); the unguarded LM divide.  Gated like thallo_hip_block_apply; the zeta test is thallo_hip_lm_zeta behind it. */
+int thallo_hip_block_step2_lm(thallo_block_regions_t regions, const float* G, float* delta, const float* p, float* r, const float* Ap, float* z, const float* b,
+                              thallo_sum_t alphaN, thallo_sum_t alphaD, float* betaN_out, float* q_out, const unsigned* gate, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

@@ -98,6 +98,8 @@ def lib():
     L.ThalloX_LastError.restype = C.c_char_p
     L.ThalloX_PlanReady.argtypes = [vp]; L.ThalloX_PlanReady.restype = C.c_int
     L.ThalloX_PlanScheduleName.argtypes = [vp]; L.ThalloX_PlanScheduleName.restype = C.c_char_p
+    L.ThalloX_PlanSetPreconditioner.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetPreconditioner.restype = C.c_int
+    L.ThalloX_PlanPreconditionerFallbacks.argtypes = [vp]; L.ThalloX_PlanPreconditionerFallbacks.restype = C.c_int
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -370,6 +372,20 @@ class ThalloSolver:
     def enable_lm(self, on=True):
         """Run the LM branch of gauss_newton.t (dead as shipped in the reference, see include/Thallo.h)."""
         self._L.ThalloX_EnableLM(self.plan, 1 if on else 0)
+
+    PRECONDITIONERS = {"jacobi": 0, "block_jacobi": 1}      # THALLOX_PRECOND_* of include/Thallo.h
+
+    def set_preconditioner(self, kind):
+        """"jacobi" (the reference's, default) or "block_jacobi" (bundle_adjustment: 9 x 9 camera and 3 x 3 point blocks); before init().  Raises, with the library's
+        reason, where the plan has no block form (include/Thallo.h ThalloX_PlanSetPreconditioner)."""
+        if kind not in self.PRECONDITIONERS:
+            raise ValueError(f"preconditioner {kind!r}: expected one of {sorted(self.PRECONDITIONERS)}")
+        if self._L.ThalloX_PlanSetPreconditioner(self.plan, self.PRECONDITIONERS[kind]) != 0:
+            raise RuntimeError("ThalloX_PlanSetPreconditioner failed: " + last_error())
+
+    def preconditioner_fallbacks(self):
+        """Blocks of the last step that fell back to their diagonal (-1: the block form does not run)."""
+        return self._L.ThalloX_PlanPreconditionerFallbacks(self.plan)
 
     def set_kernel_sampling(self, period):
         self._L.ThalloX_SetKernelSampling(self.plan, period)

@@ -915,6 +915,20 @@ public:
                                                cameras, Pts(), (const float*)JP.ptr, (float*)JpP.ptr, p, c.lm_ctc, Ap, out, c.gate, c.stream);
         return apply2(c, nullptr, p, Ap, out);
     }
+    // block-Jacobi: 9 x 9 per camera, 3 x 3 per point.  Jb, JP, cam_ptr and pt_ptr are in the plan's internal ids already (a renumbered plan included)
+    bool block_precond_ok() const override { return true; }
+    thallo_block_regions_t block_regions() const override
+    {
+        thallo_block_regions_t r; r.n = 2;
+        r.r[0] = { 0L, 9, C }; r.r[1] = { 9L * C, 3, P };
+        for (int i = 2; i < THALLO_HIP_MAX_BLOCK_REGIONS; ++i) r.r[i] = { 0L, 3, 0 };
+        return r;
+    }
+    int block_diag(LaunchCtx& c, float* H) override
+    {
+        TimedLaunch t(c, "BlockDiag");
+        return thallo_hip_ba_block_diag(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, H, c.stream);
+    }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }
     int shared_split_slots() const override { return thallo_hip_ba_apply2_camera_slots(C, P); }

@@ -389,6 +389,8 @@ void Plan::init(void** params)
             return;
         }
     }
+    block_on_ = false;
+    if (block_want_) { if (block_prepare()) return; block_on_ = true; }
     ready_ = true;
     if (dist_ && dist_->want_p2p && !dist_->checked && dist_self_check()) { ready_ = false; return; }
     if (dist_ && dist_->checked && dist_->p2p_on && dist_->form == DistForm::Slab) {      // (also right behind a self-check that has just passed: ADVICE r5)
@@ -531,6 +533,7 @@ int Plan::step_gn(int ev_iter)
         timer_.stop(ev_iter, s);
         return 1;
     }
+    if (block_on_) return step_gn_block(ev_iter);
     if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok()) return step_gn_resident(ev_iter);
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
@@ -552,6 +555,85 @@ int Plan::step_gn(int ev_iter)
     }
     const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, batched);
+    return gn_end(ev_fin, ev_iter);
+}
+
+// ------------------------------------------------------------------ block-Jacobi preconditioner (opt-in; block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
+int Plan::set_preconditioner(int kind)
+{
+    if (kind != THALLOX_PRECOND_JACOBI && kind != THALLOX_PRECOND_BLOCK_JACOBI) { set_error("%s: unknown preconditioner kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_PRECOND_JACOBI) { block_want_ = false; return 0; }
+    if (!ok_) return -1;
+    if (!plugin->block_precond_ok()) { set_error("%s: no block-Jacobi preconditioner for this energy (its plugin states no blocks; bundle_adjustment does)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: the block-Jacobi preconditioner runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to precondition", plugin->name()); return -1; }
+    block_want_ = true;
+    return 0;
+}
+
+int Plan::block_prepare()
+{
+    if (dist_ || plugin->direct_solve() || !plugin->block_precond_ok()) { set_error("%s: the block-Jacobi preconditioner needs a one-GPU PCG plan", plugin->name()); return -1; }
+    block_regions_ = plugin->block_regions();
+    const long nf = thallo_hip_block_floats(block_regions_);
+    if (nf < 0) { set_error("%s: invalid block regions", plugin->name()); return -1; }
+    if (block_H_) return 0;
+    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
+    block_H_ = (float*)get(((size_t)nf + 64) * sizeof(float)); block_G_ = (float*)get(((size_t)nf + 64) * sizeof(float)); block_status_ = (unsigned*)get(64);
+    if (!block_H_ || !block_G_ || !block_status_) { block_H_ = block_G_ = nullptr; block_status_ = nullptr; set_error("%s: out of device memory for the block preconditioner", plugin->name()); return -1; }
+    return 0;
+}
+
+int Plan::block_setup(const float* shift, const unsigned* gate, float* rz_out)
+{
+    int rc = plugin->block_diag(ctx, block_H_);
+    if (rc < 0) return rc;
+    { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(block_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
+    TimedLaunch t(ctx, "BlockApply");
+    return thallo_hip_block_apply(block_regions_, block_G_, v_.r, v_.z, rz_out, gate, ctx.stream);
+}
+
+int Plan::preconditioner_fallbacks()
+{
+    if (!block_on_ || !block_status_) return -1;
+    unsigned n = 0;
+    if (hipMemcpyAsync(&n, block_status_, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
+    return (int)n;
+}
+
+const char* Plan::schedule_name()
+{
+    if (!block_on_ && !block_want_) return plugin->schedule_name();
+    schedule_text_ = std::string(plugin->schedule_name()) + "; block-Jacobi preconditioner (unfused PCG loop)";
+    return schedule_text_.c_str();
+}
+
+int Plan::step_gn_block(int ev_iter)
+{   // the generic GN loop (step_gn's last branch) with M^-1 = G^T G: behind PCGInit1 the blocks, their factors and z = M^-1 r with alphaN_0's partials (they replace
+    // PCGInit1's point-Jacobi z and sum); PCGStep2 is thallo_hip_block_step2.  PCGInit1 leaves p_prev = 0 and the first PCGStep1 forms p = z, as in every schedule.
+    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    hipStream_t s = ctx.stream;
+    const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
+    cur_ = 0;
+    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
+    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
+    nb = block_setup(nullptr, nullptr, slot(B));
+    if (nb < 0) { set_error("block preconditioner set-up failed (%d)", nb); return 0; }
+    set_nb(B, nb); finish(B);
+    const int ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        const PrevAlpha a = prev_alpha(k);
+        nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
+        if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
+        set_nb(jD, nb); finish(jD); cur_ ^= 1;
+        {   TimedLaunch t(ctx, "BlockStep2");
+            nb = thallo_hip_block_step2(block_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
+        if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
+        set_nb(jB, nb); finish(jB);
+    }
+    const int ev_fin = gn_finish(L, ev_lin);
+    linear_update_tail(L, false);
     return gn_end(ev_fin, ev_iter);
 }
 
@@ -970,6 +1052,10 @@ bool Plan::lm_setup(LmStep& st)
             st.check(nb, "PCGFinalizeDiagonal launch");
         }
     }
+    if (block_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; z and alphaN_0 become the block form's.  Every step: CtC follows the trust-region radius
+        nb = block_setup(v_.CtC, nullptr, slot(B));
+        st.check(nb, "block preconditioner set-up");
+    }
     if (st.failed) return false;
     if (!st.skip()) set_nb(B, nb);
     if (st.global_rows(B, v_.z)) return false;                        // alphaN_0 over all ranks; ghost rows of z
@@ -986,6 +1072,7 @@ bool Plan::lm_setup(LmStep& st)
 Plan::LmSchedule Plan::lm_schedule(const LmStep& st)
 {
     const int L = st.L, period = st.period;
+    if (block_on_) return LmSchedule::Reference;      // (the block form lives in the unfused loop only)
     // round 6: the loop, the zeta test, the owed update of delta, the model cost and the update of the unknowns in ONE resident launch (plugins whose state fits the chip's
     // registers: shape_from_shading at the size of the reference's data set).  THALLO_RESIDENT=0: one launch per iteration (A/B).
     if (!st.slab && st.fold_init && lm_fold_step_ && lm_fold_p_ && st.fold_ctc && one_kernel_ && plugin->resident_lm_ok() && L >= 1 && L <= period) return LmSchedule::Resident;
@@ -1167,16 +1254,20 @@ void Plan::lm_loop_reference(LmStep& st)
                 ctx.lm_ctc = nullptr;
                 st.check(nb, "computeAdelta launch");
                 if (!st.skip() && !fold_ctc) st.check(thallo_hip_lm_step1_finish(v_.Adelta + o, v_.CtC + o, v_.delta + o, n, slot(T1), s), "computeAdelta (CtC) launch");
-                if (!st.skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(jB), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
+                // (block form: the second half's point-Jacobi z and betaN partials go to waste -- the partials into the scratch slot T1 --, thallo_hip_block_apply behind it
+                //  forms both anew: two launches on every residual_reset_period-th iteration rather than one more fused kernel)
+                if (!st.skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(block_on_ ? T1 : jB), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
                 nbq = nb;
+                if (block_on_ && !st.skip()) { nb = thallo_hip_block_apply(block_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
             }
         } else if (!st.skip()) {
-            TimedLaunch t(ctx, "PCGStep2");
-            if (zeta_in_step2) nb = thallo_hip_pcg_step2_full_zeta(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS),
+            TimedLaunch t(ctx, block_on_ ? "BlockStep2LM" : "PCGStep2");
+            if (block_on_) nb = thallo_hip_block_step2_lm(block_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, v_.b, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);      // (the zeta test: the PCGZeta launch below)
+            else if (zeta_in_step2) nb = thallo_hip_pcg_step2_full_zeta(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS),
                                                                     v_.fin_tickets, k, sp.q_tolerance, lmst, s);
             else nb = thallo_hip_pcg_step2_full(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS), 1, s);
             st.check(nb, "PCGStep2 launch");
-            nbq = nb; zeta_done = zeta_in_step2;
+            nbq = nb; zeta_done = zeta_in_step2 && !block_on_;
         }
         if (st.failed) return;
         if (!st.skip()) { set_nb(jB, nb); set_nb(QS, nbq); }

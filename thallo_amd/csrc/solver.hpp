@@ -147,6 +147,10 @@ public:
     void unknowns_changed();       // the caller rewrote unknowns / inputs in place between two LM steps (ThalloX_UnknownsChanged)
     void enable_lm(bool on);       // extension: run the LM branch the reference text describes (dead as shipped, thallo.t:463)
     bool lm() const { return lm_; }
+    // ThalloX_PlanSetPreconditioner: THALLOX_PRECOND_JACOBI (the reference's, default) or THALLOX_PRECOND_BLOCK_JACOBI; takes effect at the next Init.  0 = ok
+    int  set_preconditioner(int kind);
+    int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
+    const char* schedule_name();          // the plugin's, and the block preconditioner when it runs
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
     int  set_ghost_exchange(int n_boundary, const int* boundary_units, int n_ghost, const int* ghost_units, const int* ghost_src_rank, const int* ghost_src_pos);
@@ -279,6 +283,16 @@ private:
     float compute_cost();
     float* host_words();
     int   step_gn(int ev_iter);
+    // ---- block-Jacobi preconditioner (opt-in; block_precond.hip).  want: what ThalloX_PlanSetPreconditioner asked for; on: what this solve runs (decided at Init, where
+    // H, G and the status word are allocated -- never inside a step)
+    bool block_want_ = false, block_on_ = false;
+    thallo_block_regions_t block_regions_;
+    float *block_H_ = nullptr, *block_G_ = nullptr;
+    unsigned* block_status_ = nullptr;
+    std::string schedule_text_;
+    int   block_prepare();                              // Init: the regions and the buffers
+    int   block_setup(const float* shift, const unsigned* gate, float* rz_out);      // block_diag, block_factor (shift: the LM CtC or NULL), block_apply: z and the partials of r . z -> their number
+    int   step_gn_block(int ev_iter);                   // the generic GN loop with thallo_hip_block_step2 as PCGStep2
     // ---- Levenberg-Marquardt: step_lm = lm_setup, one of four PCG loops (lm_schedule), lm_finish
     enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident };
     // Between the LM state reset and the end of the PCG loop the plugin's launches are gated on the state's gate word (the zeta test on the device); whichever way

@@ -57,6 +57,54 @@ def cat512():
             float(np.sqrt(np.float32(100.0))), float(np.sqrt(np.float32(0.01)))]
 
 
+def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
+    """One whole solve (Init + while Step) per pass, from the same start, with the reference's Jacobi or the opt-in block-Jacobi preconditioner.  Pass 1 (also the warm-up)
+    reads the PCG iterations and the cost after every step; then `reps` timed passes at timingLevel 0 with nothing else in the stream (wall clock, Init to the last Step);
+    then one pass at timingLevel 1 for the coarse "Linear Solve" events and one with every launch sampled for the kernel means."""
+    def plan(timing):
+        dev = [torch.from_numpy(x.copy()).cuda() for x in params]
+        s = thallo_amd.ThalloSolver(dims, thallo_amd.energy_file("bundle_adjustment"), timing_level=timing, **({"solverkind": "levenberg_marquardt"} if lm else {}))
+        if lm: s.enable_lm()
+        s.set_preconditioner(precond)
+        s.set_solver_parameters(nIterations=nit, lIterations=lit, **sp)
+        return s, s.make_params(dev), dev
+    s, prm, dev = plan(0)
+    s.init(prm)
+    costs, iters, fallbacks = [s.current_cost()], [], 0
+    while s.step(prm):
+        costs.append(s.current_cost()); iters.append(len(s.alpha_beta_trace())); fallbacks += max(0, s.preconditioner_fallbacks())
+    sched = s.schedule_name
+    s.close()
+    whole = []
+    for _ in range(reps):
+        s, prm, dev = plan(0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        s.init(prm)
+        while s.step(prm): pass
+        torch.cuda.synchronize()
+        whole.append((time.perf_counter() - t0) * 1e3)
+        s.close()
+    s, prm, dev = plan(1)
+    s.init(prm)
+    while s.step(prm): pass
+    s.current_cost()
+    ps = s.performance_summary()
+    s.close()
+    s, prm, dev = plan(0)
+    s.set_kernel_sampling(1)
+    s.init(prm)
+    while s.step(prm): pass
+    torch.cuda.synchronize()
+    ks = {k: round((v["own_mean_ms"] or v["mean_ms"]) * 1e3, 2) for k, v in s.kernel_stats().items() if v["mean_ms"]}
+    s.close()
+    lin = ps["linearSolve"]
+    return {"config": name, "preconditioner": precond, "schedule": sched, "pcg_iters_per_step": iters, "pcg_iters": sum(iters), "cost_after_each_step": costs,
+            "whole_solve_ms": [round(x, 3) for x in whole], "whole_solve_ms_min": round(min(whole), 3),
+            "linear_solve_ms_per_step": round(lin["meanMS"], 4), "linear_solve_steps": lin["count"],
+            "us_per_pcg_iter": round(lin["meanMS"] * lin["count"] / max(1, sum(iters)) * 1e3, 2), "fallbacks": fallbacks, "kernel_mean_us": ks}
+
+
 only = sys.argv[1] if len(sys.argv) > 1 else ""      # e.g. "sfs", "ba", "image_warping", "arap": the configurations whose name contains it
 want = lambda name: only in name
 out = []
@@ -75,4 +123,14 @@ if want("bundle_adjustment") or only == "ba":
     p = syn.bundle_adjustment()
     out.append(run("bundle_adjustment C=1723 P=156502 O=678718 LM x150 (BASELINE config 5's solver)", "bundle_adjustment", (p[0].shape[0], p[1].shape[0], p[2].shape[0]), p, 3, 150, lm=True))
     out.append(run("bundle_adjustment C=1723 P=156502 O=678718 GN x150", "bundle_adjustment", (p[0].shape[0], p[1].shape[0], p[2].shape[0]), p, 3, 150))
+if only == "ba":      # (on request only: the default set is what tools/profile_configs.sh profiles)
+    # the opt-in block-Jacobi preconditioner against the default Jacobi path of the same build, whole solves from the same start (profiles/block_jacobi/)
+    d = (p[0].shape[0], p[1].shape[0], p[2].shape[0])
+    rows = [("bundle_adjustment ladybug shape LM 5x150 q_tolerance 0.1", 5, 150, True, 3, dict(q_tolerance=0.1, function_tolerance=0.0)),
+            ("bundle_adjustment ladybug shape GN 5x10", 5, 10, False, 3, {}),
+            ("bundle_adjustment ladybug shape GN 5x25", 5, 25, False, 3, {}),
+            ("bundle_adjustment ladybug shape LM 2x150 q_tolerance 0 (every iteration runs: the loop's cost per iteration)", 2, 150, True, 1, dict(q_tolerance=0.0, function_tolerance=0.0))]
+    for name, nit, lit, lm, reps, sp in rows:      # the two preconditioners of a row one after the other
+        for pc in ("jacobi", "block_jacobi"):
+            out.append(solve_ab(name, d, p, nit, lit, lm, pc, reps=reps, **sp))
 print(json.dumps(out, indent=1))
