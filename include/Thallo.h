@@ -143,6 +143,20 @@ int ThalloX_PlanSetPreconditioner(Thallo_Plan* plan, int kind);
  * THALLOX_PRECOND_JACOBI); -1 when the block form does not run.  Synchronises the plan's stream. */
 int ThalloX_PlanPreconditionerFallbacks(Thallo_Plan* plan);
 
+/* The linear solver of a step.  THALLOX_SOLVER_PCG: PCG on the full system J^T J delta = -J^T F (+ the LM diagonal) -- the default, and what a plan that never makes this call
+ * runs, launch for launch.  THALLOX_SOLVER_SCHUR_PCG: bundle_adjustment's points are eliminated exactly through their 3 x 3 blocks and PCG runs on the Schur complement over
+ * the 9 C camera unknowns, preconditioned by the 9 x 9 camera blocks -- whatever ThalloX_PlanSetPreconditioner was given; the points follow by back-substitution
+ * (Gauss-Newton and ThalloX_EnableLM; one GPU; ThalloX_PlanScheduleName says "Schur complement on the cameras; block-Jacobi on S").  Between Thallo_ProblemPlan and
+ * Thallo_ProblemInit, or before a re-Init: it takes effect at the next Init.  Returns 0, or nonzero with ThalloX_LastError naming the energy and the reason: every energy but
+ * bundle_adjustment (generated ones included), a doublePrecision = 1 state, a distributed plan (ThalloX_PlanSetDistributed after this call is refused likewise), a
+ * direct-solve plan. */
+#define THALLOX_SOLVER_PCG       0   /* default */
+#define THALLOX_SOLVER_SCHUR_PCG 1
+int ThalloX_PlanSetLinearSolver(Thallo_Plan* plan, int kind);
+/* Points that the last step's elimination held fixed (delta = 0 for the step: their 3 x 3 block did not factor, or has a squared pivot of the Jacobi-scaled block below 2^-16);
+ * -1 when the Schur form does not run.  ThalloX_PlanPreconditionerFallbacks then reports the camera blocks' fallbacks.  Synchronises the plan's stream. */
+int ThalloX_PlanSchurHeldPoints(Thallo_Plan* plan);
+
 /* 1 if the most recent Thallo_ProblemInit on this plan succeeded (parameters bound, plugin prepared), else 0: Init itself returns void. */
 int ThalloX_PlanReady(Thallo_Plan* plan);
 

@@ -780,6 +780,27 @@ int thallo_hip_block_step2(thallo_block_regions_t regions, const float* G, float
 int thallo_hip_block_step2_lm(thallo_block_regions_t regions, const float* G, float* delta, const float* p, float* r, const float* Ap, float* z, const float* b,
                               thallo_sum_t alphaN, thallo_sum_t alphaD, float* betaN_out, float* q_out, const unsigned* gate, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- Schur complement on the cameras (ba_schur.hip; opt-in, DESIGN.md "Schur complement on the cameras")
+ * Bundle adjustment with the points eliminated exactly through their 3 x 3 blocks: with A = J^T J (+ diag(CtC) in LM) = [[B, E], [E^T, Cp]] and b = [b_c; b_p],
+ * S = B - E Cp^-1 E^T, g = b_c - E Cp^-1 b_p, PCG on S delta_c = g, delta_p = Cp^-1 (b_p - E^T delta_c).  Index lists, Jb and JP as thallo_hip_ba_block_diag takes them (the
+ * plan's internal ids); U: 2 O floats of scratch in camera order (thallo_hip_ba_apply_jtj2's JpC); vectors b, x, delta in the flat order [cameras | points].
+ * One fixed summation order per launch shape, no float atomics: bitwise reproducible. */
+/* The ELIMINATION factor of the point blocks: Hp = the point region of H (6 planes of P floats behind the 45 C camera floats), shift_p = the LM CtC of the points or NULL;
+ * G (6 planes of P floats) = L^-1 S as thallo_hip_block_factor forms it, Cp^-1 = G^T G.  A point whose block has a B_ii that is not a positive finite number, a squared pivot of
+ * the unit-diagonal scaled block below 2^-16 or a G that is not finite is HELD FIXED: G = 0 (delta_p = 0, no coupling term); held[0] = their number. */
+int thallo_hip_ba_schur_factor(int P, const float* Hp, const float* shift_p, float* G, unsigned* held, thallo_stream_t stream);
+/* y = Cp^-1 b_p (3 P floats) and g = b_c - E y (9 C floats; also into r_out where non-NULL, which may be b): a point launch and a camera launch. */
+int thallo_hip_ba_schur_rhs(int C, int P, const int* cam_ptr, const int* pt_ptr, const int* pt_pos, const float* Jb, const float* JP, const float* G, const float* b,
+                            float* y, float* U, float* g, float* r_out, thallo_stream_t stream);
+/* Sx = S x for a camera vector x (9 C floats) in residual space, J_c^T (I - J_p Cp^-1 J_p^T) J_c x (+ CtC_c x_c where ctc is non-NULL: LM), and the partials of x . S x
+ * (returns their number): camera, point and camera launch.  gate: non-NULL and non-zero on the device = the three launches do nothing (thallo_hip_lm_zeta). */
+int thallo_hip_ba_schur_apply(int C, int P, const int* cam_ptr, const int* pt_ptr, const int* pt_pos, const float* Jb, const float* JP, const float* G, const float* x,
+                              const float* ctc, float* U, float* Sx, float* xSx_out, const unsigned* gate, thallo_stream_t stream);
+/* delta_p = Cp^-1 (b_p - E^T delta_c) into the point part of delta: a camera and a point launch.  p non-NULL (the GN loop's last term): the camera launch first forms
+ * delta_c += alpha p, alpha = alphaN / alphaD (0 if alphaD == 0), and leaves it in delta. */
+int thallo_hip_ba_schur_back(int C, int P, const int* cam_ptr, const int* pt_ptr, const int* pt_pos, const float* Jb, const float* JP, const float* G, const float* b,
+                             float* delta, const float* p, thallo_sum_t alphaN, thallo_sum_t alphaD, float* U, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

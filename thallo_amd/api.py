@@ -100,6 +100,8 @@ def lib():
     L.ThalloX_PlanScheduleName.argtypes = [vp]; L.ThalloX_PlanScheduleName.restype = C.c_char_p
     L.ThalloX_PlanSetPreconditioner.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetPreconditioner.restype = C.c_int
     L.ThalloX_PlanPreconditionerFallbacks.argtypes = [vp]; L.ThalloX_PlanPreconditionerFallbacks.restype = C.c_int
+    L.ThalloX_PlanSetLinearSolver.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetLinearSolver.restype = C.c_int
+    L.ThalloX_PlanSchurHeldPoints.argtypes = [vp]; L.ThalloX_PlanSchurHeldPoints.restype = C.c_int
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -386,6 +388,21 @@ class ThalloSolver:
     def preconditioner_fallbacks(self):
         """Blocks of the last step that fell back to their diagonal (-1: the block form does not run)."""
         return self._L.ThalloX_PlanPreconditionerFallbacks(self.plan)
+
+    LINEAR_SOLVERS = {"pcg": 0, "schur_pcg": 1}      # THALLOX_SOLVER_* of include/Thallo.h
+
+    def set_linear_solver(self, kind):
+        """"pcg" (the full system, default) or "schur_pcg" (bundle_adjustment: the points eliminated through their 3 x 3 blocks, PCG on the cameras, preconditioned by the
+        camera blocks whatever set_preconditioner was given); before init().  Raises, with the library's reason, where the plan has no Schur form
+        (include/Thallo.h ThalloX_PlanSetLinearSolver)."""
+        if kind not in self.LINEAR_SOLVERS:
+            raise ValueError(f"linear solver {kind!r}: expected one of {sorted(self.LINEAR_SOLVERS)}")
+        if self._L.ThalloX_PlanSetLinearSolver(self.plan, self.LINEAR_SOLVERS[kind]) != 0:
+            raise RuntimeError("ThalloX_PlanSetLinearSolver failed: " + last_error())
+
+    def schur_held_points(self):
+        """Points the last step's elimination held fixed (-1: the Schur form does not run)."""
+        return self._L.ThalloX_PlanSchurHeldPoints(self.plan)
 
     def set_kernel_sampling(self, period):
         self._L.ThalloX_SetKernelSampling(self.plan, period)

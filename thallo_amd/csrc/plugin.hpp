@@ -219,6 +219,14 @@ public:
     virtual bool block_precond_ok() const { return false; }
     virtual thallo_block_regions_t block_regions() const { thallo_block_regions_t r; r.n = 0; return r; }
     virtual int block_diag(LaunchCtx&, float* /*H*/) { return -1; }
+    // ---- Schur complement (opt-in: ThalloX_PlanSetLinearSolver; ba_schur.hip): plugins whose second block region can be eliminated exactly through its diagonal blocks, leaving
+    // PCG on the first region.  The defaults refuse.  reduce: the elimination factor Ge of the second region's blocks Hp (+ shift_p) with the held count, y and g = b_c - E y
+    // (also into r_out); apply: Sx = S x (+ ctc x) for a first-region vector and the partials of x . S x -> their number; back: the second region of delta from its first
+    // (p non-NULL: delta_c += (aN / aD) p first)
+    virtual bool schur_ok() const { return false; }
+    virtual int schur_reduce(LaunchCtx&, const float* /*Hp*/, const float* /*shift_p*/, float* /*Ge*/, unsigned* /*held*/, const float* /*b*/, float* /*y*/, float* /*g*/, float* /*r_out*/) { return -1; }
+    virtual int schur_apply(LaunchCtx&, const float* /*Ge*/, const float* /*x*/, const float* /*ctc*/, float* /*Sx*/, float* /*xSx_out*/, const unsigned* /*gate*/) { return -1; }
+    virtual int schur_back(LaunchCtx&, const float* /*Ge*/, const float* /*b*/, float* /*delta*/, const float* /*p*/, thallo_sum_t /*aN*/, thallo_sum_t /*aD*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale

@@ -929,6 +929,27 @@ public:
         TimedLaunch t(c, "BlockDiag");
         return thallo_hip_ba_block_diag(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, H, c.stream);
     }
+    // Schur complement on the cameras: the launches load the camera half of Jb (what block_diag summed), the packed point blocks JP, and use JpP as their u / v / t scratch
+    bool schur_ok() const override { return true; }
+    int schur_reduce(LaunchCtx& c, const float* Hp, const float* shift_p, float* Ge, unsigned* held, const float* b, float* y, float* g, float* r_out) override
+    {
+        { TimedLaunch t(c, "SchurFactor"); const int rc = thallo_hip_ba_schur_factor(P, Hp, shift_p, Ge, held, c.stream); if (rc < 0) return rc; }
+        TimedLaunch t(c, "SchurReduce");
+        return thallo_hip_ba_schur_rhs(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, y, (float*)JpP.ptr, g, r_out,
+                                       c.stream);
+    }
+    int schur_apply(LaunchCtx& c, const float* Ge, const float* x, const float* ctc, float* Sx, float* out, const unsigned* gate) override
+    {
+        TimedLaunch t(c, "SchurApply");
+        return thallo_hip_ba_schur_apply(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, x, ctc, (float*)JpP.ptr, Sx, out,
+                                         gate, c.stream);
+    }
+    int schur_back(LaunchCtx& c, const float* Ge, const float* b, float* delta, const float* p, thallo_sum_t aN, thallo_sum_t aD) override
+    {
+        TimedLaunch t(c, "SchurBack");
+        return thallo_hip_ba_schur_back(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, delta, p, aN, aD,
+                                        (float*)JpP.ptr, c.stream);
+    }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }
     int shared_split_slots() const override { return thallo_hip_ba_apply2_camera_slots(C, P); }

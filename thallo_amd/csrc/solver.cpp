@@ -390,7 +390,9 @@ void Plan::init(void** params)
         }
     }
     block_on_ = false;
-    if (block_want_) { if (block_prepare()) return; block_on_ = true; }
+    schur_on_ = false;
+    if (schur_want_) { if (schur_prepare()) return; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
+    else if (block_want_) { if (block_prepare()) return; block_on_ = true; }
     ready_ = true;
     if (dist_ && dist_->want_p2p && !dist_->checked && dist_self_check()) { ready_ = false; return; }
     if (dist_ && dist_->checked && dist_->p2p_on && dist_->form == DistForm::Slab) {      // (also right behind a self-check that has just passed: ADVICE r5)
@@ -533,6 +535,7 @@ int Plan::step_gn(int ev_iter)
         timer_.stop(ev_iter, s);
         return 1;
     }
+    if (schur_on_) return step_gn_schur(ev_iter);
     if (block_on_) return step_gn_block(ev_iter);
     if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok()) return step_gn_resident(ev_iter);
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
@@ -595,7 +598,7 @@ int Plan::block_setup(const float* shift, const unsigned* gate, float* rz_out)
 
 int Plan::preconditioner_fallbacks()
 {
-    if (!block_on_ || !block_status_) return -1;
+    if (!(block_on_ || schur_on_) || !block_status_) return -1;
     unsigned n = 0;
     if (hipMemcpyAsync(&n, block_status_, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
     return (int)n;
@@ -603,6 +606,10 @@ int Plan::preconditioner_fallbacks()
 
 const char* Plan::schedule_name()
 {
+    if (schur_on_ || schur_want_) {
+        schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras; block-Jacobi on S";
+        return schedule_text_.c_str();
+    }
     if (!block_on_ && !block_want_) return plugin->schedule_name();
     schedule_text_ = std::string(plugin->schedule_name()) + "; block-Jacobi preconditioner (unfused PCG loop)";
     return schedule_text_.c_str();
@@ -635,6 +642,141 @@ int Plan::step_gn_block(int ev_iter)
     const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, false);
     return gn_end(ev_fin, ev_iter);
+}
+
+// ------------------------------------------------------------------ Schur complement on the cameras (opt-in; ba_schur.hip, DESIGN.md "Schur complement on the cameras")
+int Plan::set_linear_solver(int kind)
+{
+    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; return 0; }
+    if (!ok_) return -1;
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on a Schur complement", plugin->name()); return -1; }
+    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no Schur-complement solve for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: the Schur-complement solve runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    schur_want_ = true;
+    return 0;
+}
+
+int Plan::schur_prepare()
+{
+    if (dist_ || plugin->direct_solve() || !plugin->schur_ok()) { set_error("%s: the Schur-complement solve needs a one-GPU PCG plan", plugin->name()); return -1; }
+    if (block_prepare()) return -1;                      // H, G, the status word (G's camera region: the preconditioner of S)
+    if (block_regions_.n != 2 || block_regions_.r[0].offset != 0) { set_error("%s: the Schur-complement solve needs two block regions, the kept one first", plugin->name()); return -1; }
+    schur_regions_ = block_regions_; schur_regions_.n = 1;
+    schur_n_ = (long)block_regions_.r[0].size * block_regions_.r[0].count;
+    schur_hp_off_ = thallo_hip_block_floats(schur_regions_);
+    schur_pt_off_ = block_regions_.r[1].offset;
+    if (schur_Ge_) return 0;
+    const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
+    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
+    schur_Ge_ = (float*)get((ns * (ns + 1) / 2 * np + 64) * sizeof(float)); schur_y_ = (float*)get((ns * np + 64) * sizeof(float));
+    schur_g_ = (float*)get(((size_t)v_.n_alloc + 64) * sizeof(float)); schur_held_ = (unsigned*)get(64);
+    if (!schur_Ge_ || !schur_y_ || !schur_g_ || !schur_held_) {
+        schur_Ge_ = schur_y_ = schur_g_ = nullptr; schur_held_ = nullptr;
+        set_error("%s: out of device memory for the Schur-complement solve", plugin->name()); return -1;
+    }
+    return 0;
+}
+
+int Plan::schur_setup(const float* shift, const float* b, float* rz_out)
+{   // behind PCGInit1 (+ PCGFinalizeDiagonal in LM): r = b = -J^T F over all unknowns, pre = the point-Jacobi M^-1 (the camera blocks' fallback)
+    int rc = plugin->block_diag(ctx, block_H_);
+    if (rc < 0) return rc;
+    { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(schur_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
+    if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r)) < 0) return rc;
+    TimedLaunch t(ctx, "BlockApply");
+    return thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, ctx.stream);
+}
+
+int Plan::schur_held_points()
+{
+    if (!schur_on_ || !schur_held_) return -1;
+    unsigned n = 0;
+    if (hipMemcpyAsync(&n, schur_held_, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
+    return (int)n;
+}
+
+int Plan::step_gn_schur(int ev_iter)
+{   // step_gn_block's loop on the reduced system (S, g): every vector of the loop is its camera part ([0, 9 C) of the plan's vectors); the point part of r stays b_p, which
+    // the back-substitution reads.  The loop's last delta_c += alpha p rides in the back-substitution's camera launch; PCGLinearUpdate then adds the complete delta.
+    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    hipStream_t s = ctx.stream;
+    const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
+    cur_ = 0;
+    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
+    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
+    nb = schur_setup(nullptr, v_.r, slot(B));
+    if (nb < 0) { set_error("Schur-complement set-up failed (%d)", nb); return 0; }
+    set_nb(B, nb); finish(B);
+    const int ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        const PrevAlpha a = prev_alpha(k);
+        {   TimedLaunch t(ctx, "PCGStep3");
+            nb = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, schur_n_, k == 0 ? 1 : 0, a.aN, a.aD, sum(jN), s); }
+        if (nb < 0) { set_error("PCGStep3 launch failed (%d)", nb); return 0; }
+        nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], nullptr, v_.Ap, slot(jD), nullptr);
+        if (nb < 0) { set_error("Schur apply launch failed (%d)", nb); return 0; }
+        set_nb(jD, nb); finish(jD); cur_ ^= 1;
+        {   TimedLaunch t(ctx, "BlockStep2");
+            nb = thallo_hip_block_step2(schur_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
+        if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
+        set_nb(jB, nb); finish(jB);
+    }
+    const int jL = B + 2 * (L - 1);
+    nb = plugin->schur_back(ctx, schur_Ge_, v_.r, v_.delta, L > 0 ? v_.p[cur_] : nullptr, sum(L > 0 ? jL : B), sum(L > 0 ? jL + 1 : B));
+    if (nb < 0) { set_error("Schur back-substitution launch failed (%d)", nb); return 0; }
+    const int ev_fin = gn_finish(L, ev_lin);
+    linear_update_tail(0, false);
+    return gn_end(ev_fin, ev_iter);
+}
+
+// The reference-shaped LM loop (lm_loop_reference on one GPU) on the reduced system: b := g, Q_k = 0.5 delta_c . (r_c + g) -- the full model's value minus the constant
+// 0.5 b_p . Cp^-1 b_p, which the zeta test (Ceres' criterion on the reduced model) does not use.  Every launch of the loop takes the gate word; the back-substitution behind
+// it does not.
+void Plan::lm_loop_schur(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const int L = st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const long n = schur_n_;
+    float* p = v_.p[0];
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
+            st.check(thallo_hip_pcg_pupdate(v_.z, p, p, nullptr, n, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch"); }
+        if (st.failed) return;
+        nb = plugin->schur_apply(ctx, schur_Ge_, p, v_.CtC, v_.Ap, slot(jD), ctx.gate);      // (S + CtC_c) p ; alphaD
+        st.check(nb, "Schur apply launch");
+        if (st.failed) return;
+        set_nb(jD, nb);
+        int nbq = 0;
+        if (((k + 1) % sp.residual_reset_period) == 0) {      // :1653-1657 on the reduced system: r_c = g - (S + CtC_c) delta_c, one more apply
+            { TimedLaunch t(ctx, "PCGStep2"); st.check(thallo_hip_lm_step2_first_half(v_.delta, p, n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
+            if (st.failed) return;
+            nb = plugin->schur_apply(ctx, schur_Ge_, v_.delta, v_.CtC, v_.Adelta, slot(T0), ctx.gate);
+            st.check(nb, "Schur apply (reset) launch");
+            if (st.failed) return;
+            // (as in the block form: the second half's point-Jacobi z and betaN partials go to waste -- the partials into the scratch slot T1 --, the block apply forms both anew)
+            { TimedLaunch t(ctx, "PCGStep2"); nb = thallo_hip_lm_step2_second_half(v_.r, schur_g_, v_.Adelta, v_.pre, v_.z, v_.delta, n, slot(T1), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
+            if (st.failed) return;
+            nbq = nb;
+            { TimedLaunch t(ctx, "BlockApply"); nb = thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
+        } else {
+            TimedLaunch t(ctx, "BlockStep2LM");
+            nb = thallo_hip_block_step2_lm(schur_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, schur_g_, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);
+            st.check(nb, "PCGStep2 launch");
+            nbq = nb;
+        }
+        if (st.failed) return;
+        set_nb(jB, nb); set_nb(QS, nbq);
+        st.k_done = k + 1;
+        {   TimedLaunch t(ctx, "PCGZeta");
+            st.check(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, st.lmst, s), "PCGZeta launch"); }
+        if (st.failed) return;
+    }
+    const thallo_sum_t none = { nullptr, 0 };
+    st.check(plugin->schur_back(ctx, schur_Ge_, v_.b, v_.delta, nullptr, none, none), "Schur back-substitution launch");
 }
 
 // ------------------------------------------------------------------ Levenberg-Marquardt branch
@@ -1020,6 +1162,7 @@ int Plan::step_lm(int ev_iter)
         case LmSchedule::OneKernel:     lm_loop_one_kernel(st); break;
         case LmSchedule::OneKernelSlab: lm_loop_one_kernel_slab(st); break;
         case LmSchedule::Reference:     lm_loop_reference(st); break;
+        case LmSchedule::Schur:         lm_loop_schur(st); break;
         }
     }
     if (st.failed || st.coll_failed) return 0;
@@ -1052,6 +1195,10 @@ bool Plan::lm_setup(LmStep& st)
             st.check(nb, "PCGFinalizeDiagonal launch");
         }
     }
+    if (schur_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; r_c becomes g, z_c and alphaN_0 the reduced system's.  Every step: CtC follows the trust-region radius
+        nb = schur_setup(v_.CtC, v_.b, slot(B));
+        st.check(nb, "Schur-complement set-up");
+    }
     if (block_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; z and alphaN_0 become the block form's.  Every step: CtC follows the trust-region radius
         nb = block_setup(v_.CtC, nullptr, slot(B));
         st.check(nb, "block preconditioner set-up");
@@ -1072,6 +1219,7 @@ bool Plan::lm_setup(LmStep& st)
 Plan::LmSchedule Plan::lm_schedule(const LmStep& st)
 {
     const int L = st.L, period = st.period;
+    if (schur_on_) return LmSchedule::Schur;
     if (block_on_) return LmSchedule::Reference;      // (the block form lives in the unfused loop only)
     // round 6: the loop, the zeta test, the owed update of delta, the model cost and the update of the unknowns in ONE resident launch (plugins whose state fits the chip's
     // registers: shape_from_shading at the size of the reference's data set).  THALLO_RESIDENT=0: one launch per iteration (A/B).

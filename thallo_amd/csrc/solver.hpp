@@ -150,7 +150,10 @@ public:
     // ThalloX_PlanSetPreconditioner: THALLOX_PRECOND_JACOBI (the reference's, default) or THALLOX_PRECOND_BLOCK_JACOBI; takes effect at the next Init.  0 = ok
     int  set_preconditioner(int kind);
     int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
-    const char* schedule_name();          // the plugin's, and the block preconditioner when it runs
+    const char* schedule_name();          // the plugin's, and the block preconditioner / the Schur form when it runs
+    // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default) or THALLOX_SOLVER_SCHUR_PCG; takes effect at the next Init.  0 = ok
+    int  set_linear_solver(int kind);
+    int  schur_held_points();             // points the last step's elimination held fixed (-1: the Schur form does not run)
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
     int  set_ghost_exchange(int n_boundary, const int* boundary_units, int n_ghost, const int* ghost_units, const int* ghost_src_rank, const int* ghost_src_pos);
@@ -293,8 +296,18 @@ private:
     int   block_prepare();                              // Init: the regions and the buffers
     int   block_setup(const float* shift, const unsigned* gate, float* rz_out);      // block_diag, block_factor (shift: the LM CtC or NULL), block_apply: z and the partials of r . z -> their number
     int   step_gn_block(int ev_iter);                   // the generic GN loop with thallo_hip_block_step2 as PCGStep2
+    // ---- Schur complement on the cameras (opt-in; ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
+    // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are allocated at Init too
+    bool schur_want_ = false, schur_on_ = false;
+    thallo_block_regions_t schur_regions_;              // the camera region alone
+    long schur_n_ = 0, schur_hp_off_ = 0, schur_pt_off_ = 0;      // camera unknowns; the point blocks' place in H; the points' place in the flat vector
+    float *schur_Ge_ = nullptr, *schur_y_ = nullptr, *schur_g_ = nullptr;
+    unsigned* schur_held_ = nullptr;
+    int   schur_prepare();                              // Init: the buffers
+    int   schur_setup(const float* shift, const float* b, float* rz_out);      // blocks, both factors, g (r_c = g), z_c = M_c^-1 r_c and the partials of r_c . z_c -> their number
+    int   step_gn_schur(int ev_iter);                   // step_gn_block's loop on (S, g), then the back-substitution
     // ---- Levenberg-Marquardt: step_lm = lm_setup, one of four PCG loops (lm_schedule), lm_finish
-    enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident };
+    enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident, Schur };
     // Between the LM state reset and the end of the PCG loop the plugin's launches are gated on the state's gate word (the zeta test on the device); whichever way
     // the loop is left, the gate is off again before the next launch that has to run
     struct GateOff {
@@ -330,6 +343,7 @@ private:
     bool  lm_setup(LmStep& st);
     LmSchedule lm_schedule(const LmStep& st);
     void  lm_loop_reference(LmStep& st);
+    void  lm_loop_schur(LmStep& st);                    // the reference-shaped loop on the reduced system (S + CtC_c, g), then the back-substitution
     void  lm_loop_one_kernel(LmStep& st);
     void  lm_loop_one_kernel_slab(LmStep& st);
     void  lm_loop_resident(LmStep& st);

@@ -58,21 +58,23 @@ def cat512():
 
 
 def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
-    """One whole solve (Init + while Step) per pass, from the same start, with the reference's Jacobi or the opt-in block-Jacobi preconditioner.  Pass 1 (also the warm-up)
+    """One whole solve (Init + while Step) per pass, from the same start, in one of three forms: "jacobi" (the default plan), "block_jacobi" (the opt-in block
+    preconditioner) or "schur_pcg" (the opt-in Schur-complement solve; its preconditioner is the camera blocks).  Pass 1 (also the warm-up)
     reads the PCG iterations and the cost after every step; then `reps` timed passes at timingLevel 0 with nothing else in the stream (wall clock, Init to the last Step);
     then one pass at timingLevel 1 for the coarse "Linear Solve" events and one with every launch sampled for the kernel means."""
     def plan(timing):
         dev = [torch.from_numpy(x.copy()).cuda() for x in params]
         s = thallo_amd.ThalloSolver(dims, thallo_amd.energy_file("bundle_adjustment"), timing_level=timing, **({"solverkind": "levenberg_marquardt"} if lm else {}))
         if lm: s.enable_lm()
-        s.set_preconditioner(precond)
+        if precond == "schur_pcg": s.set_linear_solver(precond)
+        else: s.set_preconditioner(precond)
         s.set_solver_parameters(nIterations=nit, lIterations=lit, **sp)
         return s, s.make_params(dev), dev
     s, prm, dev = plan(0)
     s.init(prm)
-    costs, iters, fallbacks = [s.current_cost()], [], 0
+    costs, iters, fallbacks, held = [s.current_cost()], [], 0, 0
     while s.step(prm):
-        costs.append(s.current_cost()); iters.append(len(s.alpha_beta_trace())); fallbacks += max(0, s.preconditioner_fallbacks())
+        costs.append(s.current_cost()); iters.append(len(s.alpha_beta_trace())); fallbacks += max(0, s.preconditioner_fallbacks()); held += max(0, s.schur_held_points())
     sched = s.schedule_name
     s.close()
     whole = []
@@ -102,7 +104,26 @@ def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
     return {"config": name, "preconditioner": precond, "schedule": sched, "pcg_iters_per_step": iters, "pcg_iters": sum(iters), "cost_after_each_step": costs,
             "whole_solve_ms": [round(x, 3) for x in whole], "whole_solve_ms_min": round(min(whole), 3),
             "linear_solve_ms_per_step": round(lin["meanMS"], 4), "linear_solve_steps": lin["count"],
-            "us_per_pcg_iter": round(lin["meanMS"] * lin["count"] / max(1, sum(iters)) * 1e3, 2), "fallbacks": fallbacks, "kernel_mean_us": ks}
+            "us_per_pcg_iter": round(lin["meanMS"] * lin["count"] / max(1, sum(iters)) * 1e3, 2), "fallbacks": fallbacks, "held_points": held, "kernel_mean_us": ks}
+
+
+def gn_budget(dims, params, form, target, nit=7, budgets=(5, 10, 15, 20, 25, 35, 50, 75, 100, 150)):
+    """The smallest lIterations of `budgets` at which nit GN steps of the form end at or below `target` (the default plan's cost after nit x 150) -> (lIterations, final cost);
+    lIterations None: not within the largest budget"""
+    last = None
+    for lit in budgets:
+        dev = [torch.from_numpy(x.copy()).cuda() for x in params]
+        s = thallo_amd.ThalloSolver(dims, thallo_amd.energy_file("bundle_adjustment"), timing_level=0)
+        if form == "schur_pcg": s.set_linear_solver(form)
+        else: s.set_preconditioner(form)
+        s.set_solver_parameters(nIterations=nit, lIterations=lit)
+        prm = s.make_params(dev)
+        s.init(prm)
+        while s.step(prm): pass
+        last = s.current_cost()
+        s.close()
+        if last <= target: return lit, last
+    return None, last
 
 
 only = sys.argv[1] if len(sys.argv) > 1 else ""      # e.g. "sfs", "ba", "image_warping", "arap": the configurations whose name contains it
@@ -124,13 +145,20 @@ if want("bundle_adjustment") or only == "ba":
     out.append(run("bundle_adjustment C=1723 P=156502 O=678718 LM x150 (BASELINE config 5's solver)", "bundle_adjustment", (p[0].shape[0], p[1].shape[0], p[2].shape[0]), p, 3, 150, lm=True))
     out.append(run("bundle_adjustment C=1723 P=156502 O=678718 GN x150", "bundle_adjustment", (p[0].shape[0], p[1].shape[0], p[2].shape[0]), p, 3, 150))
 if only == "ba":      # (on request only: the default set is what tools/profile_configs.sh profiles)
-    # the opt-in block-Jacobi preconditioner against the default Jacobi path of the same build, whole solves from the same start (profiles/block_jacobi/)
+    # the opt-in block-Jacobi preconditioner and the opt-in Schur-complement solve against the default Jacobi path of the same build, whole solves from the same start, all in
+    # this one process (profiles/block_jacobi/, profiles/ba_schur/)
     d = (p[0].shape[0], p[1].shape[0], p[2].shape[0])
     rows = [("bundle_adjustment ladybug shape LM 5x150 q_tolerance 0.1", 5, 150, True, 3, dict(q_tolerance=0.1, function_tolerance=0.0)),
             ("bundle_adjustment ladybug shape GN 5x10", 5, 10, False, 3, {}),
             ("bundle_adjustment ladybug shape GN 5x25", 5, 25, False, 3, {}),
+            ("bundle_adjustment ladybug shape GN 5x150", 5, 150, False, 3, {}),
             ("bundle_adjustment ladybug shape LM 2x150 q_tolerance 0 (every iteration runs: the loop's cost per iteration)", 2, 150, True, 1, dict(q_tolerance=0.0, function_tolerance=0.0))]
-    for name, nit, lit, lm, reps, sp in rows:      # the two preconditioners of a row one after the other
-        for pc in ("jacobi", "block_jacobi"):
+    forms = ("jacobi", "block_jacobi", "schur_pcg")
+    for name, nit, lit, lm, reps, sp in rows:      # the three forms of a row one after the other
+        for pc in forms:
             out.append(solve_ab(name, d, p, nit, lit, lm, pc, reps=reps, **sp))
+    # the GN iteration budget at which each form reaches the default plan's 7 x 150 cost
+    _, target = gn_budget(d, p, "jacobi", float("-inf"), budgets=(150,))
+    out.append({"config": "bundle_adjustment ladybug shape: lIterations at which 7 GN steps reach the default plan's 7x150 cost", "target_cost": target,
+                "budget": {pc: dict(zip(("lIterations", "cost"), gn_budget(d, p, pc, target))) for pc in forms}})
 print(json.dumps(out, indent=1))
