@@ -149,10 +149,18 @@ int ThalloX_PlanPreconditionerFallbacks(Thallo_Plan* plan);
  * (Gauss-Newton and ThalloX_EnableLM; one GPU; ThalloX_PlanScheduleName says "Schur complement on the cameras; block-Jacobi on S").  Between Thallo_ProblemPlan and
  * Thallo_ProblemInit, or before a re-Init: it takes effect at the next Init.  Returns 0, or nonzero with ThalloX_LastError naming the energy and the reason: every energy but
  * bundle_adjustment (generated ones included), a doublePrecision = 1 state, a distributed plan (ThalloX_PlanSetDistributed after this call is refused likewise), a
- * direct-solve plan. */
-#define THALLOX_SOLVER_PCG       0   /* default */
-#define THALLOX_SOLVER_SCHUR_PCG 1
+ * direct-solve plan.  THALLOX_SOLVER_SCHUR_EXPLICIT_PCG: the same solve -- elimination, right-hand side, preconditioner, PCG chain, back-substitution -- with the reduced
+ * camera matrix S ASSEMBLED once per step as a block-sparse matrix over the co-visible camera pairs (9 x 9 blocks, both triangles), so that every S x of the loop is one
+ * block-sparse mat-vec instead of three passes over the observations (ThalloX_PlanScheduleName: "Schur complement on the cameras, assembled (N blocks); block-Jacobi on
+ * S").  Its structure (blocks, term lists, one 9 x 3 block per observation) is built at Init and must fit a quarter of the free device memory and int32 indices: otherwise Init
+ * fails with ThalloX_LastError naming the bytes wanted and allowed -- the term count grows with the square of a point's track length; there is no silent fall-back to
+ * THALLOX_SOLVER_SCHUR_PCG.  Refused where THALLOX_SOLVER_SCHUR_PCG is. */
+#define THALLOX_SOLVER_PCG                0   /* default */
+#define THALLOX_SOLVER_SCHUR_PCG          1
+#define THALLOX_SOLVER_SCHUR_EXPLICIT_PCG 2
 int ThalloX_PlanSetLinearSolver(Thallo_Plan* plan, int kind);
+/* The stored 9 x 9 blocks of the assembled S (both triangles) after Thallo_ProblemInit; -1 when the assembled form does not run. */
+int ThalloX_PlanSchurBlocks(Thallo_Plan* plan);
 /* Points that the last step's elimination held fixed (delta = 0 for the step: their 3 x 3 block did not factor, or has a squared pivot of the Jacobi-scaled block below 2^-16);
  * -1 when the Schur form does not run.  ThalloX_PlanPreconditionerFallbacks then reports the camera blocks' fallbacks.  Synchronises the plan's stream. */
 int ThalloX_PlanSchurHeldPoints(Thallo_Plan* plan);

@@ -801,6 +801,26 @@ int thallo_hip_ba_schur_apply(int C, int P, const int* cam_ptr, const int* pt_pt
 int thallo_hip_ba_schur_back(int C, int P, const int* cam_ptr, const int* pt_ptr, const int* pt_pos, const float* Jb, const float* JP, const float* G, const float* b,
                              float* delta, const float* p, thallo_sum_t alphaN, thallo_sum_t alphaD, float* U, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- the assembled reduced camera matrix (ba_schur_explicit.hip; opt-in, DESIGN.md "Assembled reduced camera matrix")
+ * S = B (+ diag CtC_c) - E Cp^-1 E^T stored block-sparse over the co-visible camera pairs: nblk blocks of 9 x 9, both triangles, a row's blocks consecutive with ascending
+ * columns (row_ptr: C + 1 places, col: nblk cameras), entry-major planes S[e * nblk + blk], e = 9 a + b.  The lower triangle (the diagonal blocks included, every camera's
+ * always present) is what is summed: nlower blocks in the order (row, column); lower[3 l ..] = the place of block l, the place of its transpose (the same place for a
+ * diagonal block), and the camera of a diagonal block or -1; terms[2 t ..] = (q, q'), two observations of one point in camera order with camera(q) = the block's row and
+ * camera(q') = its column, the terms of block l at [term_ptr[l], term_ptr[l + 1]) in ascending (q, q').  A (camera, point) pair observed twice simply has more terms: its
+ * diagonal block lists (q, q), (q, q'), (q', q) and (q', q').  One fixed summation order per launch shape, no float atomics: bitwise reproducible. */
+#define THALLO_HIP_SCHUR_W_STRIDE 32      /* floats from one observation's W to the next: 27 used (W[3 a + m]), one 128-byte line each */
+/* W_q = (J_c,q^T J_p,q) G_p^T per observation in camera order (q_pt: its point), from the 24 floats of Jb and the elimination factor G of thallo_hip_ba_schur_factor
+ * (6 planes of P floats).  A held point (G = 0) gives W = 0.  Writes floats 0 .. 27 of every stride (27 = 0). */
+int thallo_hip_ba_schur_w(int O, int P, const int* q_pt, const float* Jb, const float* G, float* W, thallo_stream_t stream);
+/* S_ij = [i = j] (B_ii + diag CtC_c,i) - sum over the block's terms of W_q W_q'^T for every lower block, written with its transpose by the wave that summed it.  H: the 45 C
+ * camera floats of thallo_hip_ba_block_diag; ctc: the LM CtC of the cameras (9 C floats) or NULL.  The stored S is symmetric bit for bit. */
+int thallo_hip_ba_schur_assemble(int C, int nlower, long nblk, const int* lower, const int* term_ptr, const int* terms, const float* W, const float* H, const float* ctc, float* S,
+                                 thallo_stream_t stream);
+/* Sx = S x for a camera vector x (9 C floats) and the partials of x . S x (returns their number, thallo_hip_ba_schur_apply's): one launch.  gate: non-NULL and non-zero on
+ * the device = the launch does nothing (thallo_hip_lm_zeta). */
+int thallo_hip_ba_schur_apply_s(int C, long nblk, const int* row_ptr, const int* col, const float* S, const float* x, float* Sx, float* xSx_out, const unsigned* gate,
+                                thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

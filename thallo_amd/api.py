@@ -102,6 +102,7 @@ def lib():
     L.ThalloX_PlanPreconditionerFallbacks.argtypes = [vp]; L.ThalloX_PlanPreconditionerFallbacks.restype = C.c_int
     L.ThalloX_PlanSetLinearSolver.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetLinearSolver.restype = C.c_int
     L.ThalloX_PlanSchurHeldPoints.argtypes = [vp]; L.ThalloX_PlanSchurHeldPoints.restype = C.c_int
+    L.ThalloX_PlanSchurBlocks.argtypes = [vp]; L.ThalloX_PlanSchurBlocks.restype = C.c_int
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -389,12 +390,13 @@ class ThalloSolver:
         """Blocks of the last step that fell back to their diagonal (-1: the block form does not run)."""
         return self._L.ThalloX_PlanPreconditionerFallbacks(self.plan)
 
-    LINEAR_SOLVERS = {"pcg": 0, "schur_pcg": 1}      # THALLOX_SOLVER_* of include/Thallo.h
+    LINEAR_SOLVERS = {"pcg": 0, "schur_pcg": 1, "schur_explicit_pcg": 2}      # THALLOX_SOLVER_* of include/Thallo.h
 
     def set_linear_solver(self, kind):
-        """"pcg" (the full system, default) or "schur_pcg" (bundle_adjustment: the points eliminated through their 3 x 3 blocks, PCG on the cameras, preconditioned by the
-        camera blocks whatever set_preconditioner was given); before init().  Raises, with the library's reason, where the plan has no Schur form
-        (include/Thallo.h ThalloX_PlanSetLinearSolver)."""
+        """"pcg" (the full system, default), "schur_pcg" (bundle_adjustment: the points eliminated through their 3 x 3 blocks, PCG on the cameras, preconditioned by the
+        camera blocks whatever set_preconditioner was given; S x applied matrix-free) or "schur_explicit_pcg" (the same solve with the reduced camera matrix S assembled
+        once per step as a block-sparse matrix: one mat-vec per iteration; init() fails, naming the bytes, where its structure does not fit a quarter of the free device
+        memory); before init().  Raises, with the library's reason, where the plan has no Schur form (include/Thallo.h ThalloX_PlanSetLinearSolver)."""
         if kind not in self.LINEAR_SOLVERS:
             raise ValueError(f"linear solver {kind!r}: expected one of {sorted(self.LINEAR_SOLVERS)}")
         if self._L.ThalloX_PlanSetLinearSolver(self.plan, self.LINEAR_SOLVERS[kind]) != 0:
@@ -403,6 +405,10 @@ class ThalloSolver:
     def schur_held_points(self):
         """Points the last step's elimination held fixed (-1: the Schur form does not run)."""
         return self._L.ThalloX_PlanSchurHeldPoints(self.plan)
+
+    def schur_blocks(self):
+        """Stored 9 x 9 blocks of the assembled reduced camera matrix after init() (-1: the assembled form does not run)."""
+        return self._L.ThalloX_PlanSchurBlocks(self.plan)
 
     def set_kernel_sampling(self, period):
         self._L.ThalloX_SetKernelSampling(self.plan, period)

@@ -226,6 +226,12 @@ public:
     virtual bool schur_ok() const { return false; }
     virtual int schur_reduce(LaunchCtx&, const float* /*Hp*/, const float* /*shift_p*/, float* /*Ge*/, unsigned* /*held*/, const float* /*b*/, float* /*y*/, float* /*g*/, float* /*r_out*/) { return -1; }
     virtual int schur_apply(LaunchCtx&, const float* /*Ge*/, const float* /*x*/, const float* /*ctc*/, float* /*Sx*/, float* /*xSx_out*/, const unsigned* /*gate*/) { return -1; }
+    // the assembled form (ThalloX_PlanSetLinearSolver kind 2; ba_schur_explicit.hip).  schur_explicit(true), at Init behind prepare(): build the symbolic structure of S in the
+    // plan's internal ids and allocate it -> the stored blocks, or -1 with the reason set (budget, int32 indices, memory); from then on schur_apply multiplies by the
+    // assembled S (and ignores ctc: the assembly added it).  schur_explicit(false): back to the matrix-free apply.  schur_assemble, every step behind schur_reduce: W and S
+    // from the step's blocks H, the elimination factor Ge and the LM CtC of the first region (or NULL)
+    virtual long schur_explicit(bool /*on*/) { return -1; }
+    virtual int schur_assemble(LaunchCtx&, const float* /*H*/, const float* /*Ge*/, const float* /*ctc*/) { return -1; }
     virtual int schur_back(LaunchCtx&, const float* /*Ge*/, const float* /*b*/, float* /*delta*/, const float* /*p*/, thallo_sum_t /*aN*/, thallo_sum_t /*aD*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;

@@ -938,8 +938,110 @@ public:
         return thallo_hip_ba_schur_rhs(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, y, (float*)JpP.ptr, g, r_out,
                                        c.stream);
     }
+    // ---- the assembled reduced camera matrix (ThalloX_PlanSetLinearSolver kind 2; ba_schur_explicit.hip, DESIGN.md "Assembled reduced camera matrix").  The symbolic
+    // structure is built here on the host at Init from the point incidence lists as the device holds them (the plan's internal ids, a renumbered plan included): the
+    // co-visible camera pairs (every diagonal block present), and per lower-triangle block its terms (q, q'), two observations of one point, ascending.  A (camera, point)
+    // pair observed more than once simply yields more terms (both orders of the pair in the diagonal block: the lower triangle of the full sum needs both).
+    bool sx_on_ = false;
+    long sx_nblk_ = 0; int sx_nlower_ = 0;
+    DeviceBuffer sx_row_ptr_, sx_col_, sx_lower_, sx_term_ptr_, sx_terms_, sx_W_, sx_S_;
+    long schur_explicit(bool on) override
+    {
+        sx_on_ = false;
+        if (!on) { for (DeviceBuffer* b : { &sx_row_ptr_, &sx_col_, &sx_lower_, &sx_term_ptr_, &sx_terms_, &sx_W_, &sx_S_ }) b->release(); return 0; }
+        if (C < 1) { set_error("bundle_adjustment: the assembled Schur-complement solve needs at least one camera"); return -1; }
+        std::vector<int> pp((size_t)P + 1), ppos((size_t)O), qc((size_t)O), qp((size_t)O), cp((size_t)C + 1);
+        auto down = [](std::vector<int>& h, const DeviceBuffer& b) { return h.empty() || hipMemcpy(h.data(), b.ptr, sizeof(int) * h.size(), hipMemcpyDeviceToHost) == hipSuccess; };
+        if (!down(pp, pt_ptr) || !down(ppos, pt_pos) || !down(qc, q_cam) || !down(qp, q_pt) || !down(cp, cam_ptr)) { set_error("bundle_adjustment: cannot read the incidence lists"); return -1; }
+        // a point's observations ascending in camera order: ascending cameras too, so the partners q' of q with camera(q') <= camera(q) are a prefix of the list
+        for (int j = 0; j < P; ++j) std::sort(ppos.begin() + pp[j], ppos.begin() + pp[j + 1]);
+        // the allowance: a quarter of the free device memory (the rule of the ring of p planes), or less (THALLO_AB=schur_s_max_mb=N)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { set_error("bundle_adjustment: cannot read the free device memory"); return -1; }
+        unsigned long long allowed = free_b / 4;
+        const char* why = "a quarter of the free device memory";
+        if (const char* e = env_switch("THALLO_SCHUR_S_MAX_MB")) {
+            const unsigned long long cap = strtoull(e, nullptr, 10) << 20;
+            if (cap < allowed) { allowed = cap; why = "THALLO_AB schur_s_max_mb"; }
+        }
+        // the terms, counted before anything is built: an observation pairs with every observation of its point whose camera is not above its own
+        unsigned long long nterms = 0;
+        for (int j = 0; j < P; ++j)
+            for (int k = pp[j], e = pp[j]; k < pp[j + 1]; ++k) {
+                while (e < pp[j + 1] && qc[ppos[e]] <= qc[ppos[k]]) ++e;
+                nterms += (unsigned long long)(e - pp[j]);
+            }
+        const unsigned long long w_bytes = sizeof(float) * THALLO_HIP_SCHUR_W_STRIDE * (unsigned long long)O + 64;
+        auto over = [&](unsigned long long bytes, unsigned long long blocks, const char* least) {
+            set_error("bundle_adjustment: the assembled reduced camera matrix wants %s%llu bytes of device memory (%s%llu blocks of 9 x 9, %llu terms, %d observations), the budget allows %llu (%s): "
+                      "points seen by many cameras make the term count grow with the square of the track length; THALLOX_SOLVER_SCHUR_PCG applies S without assembling it",
+                      least, bytes, least, blocks, nterms, O, allowed, why);
+            return -1L;
+        };
+        if (nterms > 0x7fffffffULL) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu terms, more than its int32 indices hold", nterms); return -1; }
+        if (w_bytes + 8ULL * nterms > allowed) return over(w_bytes + 8ULL * nterms + 81ULL * 4 * (unsigned long long)C, (unsigned long long)C, "at least ");      // (the blocks are not counted yet)
+        // row by row, without a comparison sort of the terms: a row's observations ascend, a counting pass sizes its blocks, a second pass places the terms -- (q, q')
+        // ascending within every block.  Every diagonal block is present, with or without terms
+        std::vector<int> lower, term_ptr, tq(2 * (size_t)nterms + 2), cnt((size_t)C, 0), touched;
+        std::vector<long> keys;
+        size_t at = 0;
+        for (int i = 0; i < C; ++i) {
+            touched.assign(1, i);
+            for (int q = cp[i]; q < cp[i + 1]; ++q)
+                for (int k = pp[qp[q]]; k < pp[qp[q] + 1] && qc[ppos[k]] <= i; ++k) { const int c2 = qc[ppos[k]]; if (cnt[c2]++ == 0 && c2 != i) touched.push_back(c2); }
+            std::sort(touched.begin(), touched.end());
+            for (int c2 : touched) { keys.push_back((long)i * C + c2); term_ptr.push_back((int)at); const int n = cnt[c2]; cnt[c2] = (int)at; at += (size_t)n; }      // (cnt: now the block's next free place)
+            for (int q = cp[i]; q < cp[i + 1]; ++q)
+                for (int k = pp[qp[q]]; k < pp[qp[q] + 1] && qc[ppos[k]] <= i; ++k) { const size_t t = (size_t)cnt[qc[ppos[k]]]++; tq[2 * t] = q; tq[2 * t + 1] = ppos[k]; }
+            for (int c2 : touched) cnt[c2] = 0;
+        }
+        term_ptr.push_back((int)at);
+        if (at != nterms) { set_error("bundle_adjustment: internal: %zu terms listed, %llu counted", at, nterms); return -1; }
+        tq.resize(2 * (size_t)nterms);
+        const unsigned long long nlower = keys.size(), nblk = 2 * nlower - (unsigned long long)C;
+        if (nblk > 0x7fffffffULL / 3) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu blocks, more than its int32 indices hold", nblk); return -1; }
+        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5);
+        if (bytes > allowed) return over(bytes, nblk, "");
+        std::vector<int> row_ptr((size_t)C + 1, 0);
+        for (long key : keys) { const int i = (int)(key / C), j = (int)(key % C); row_ptr[i + 1]++; if (i != j) row_ptr[j + 1]++; }
+        for (int c = 0; c < C; ++c) row_ptr[c + 1] += row_ptr[c];
+        // places: the keys ascend by (row, column), so a row's lower part and diagonal are placed before the first (k, row), k > row, and those arrive with ascending k
+        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1), col((size_t)nblk);
+        lower.resize(3 * (size_t)nlower);
+        for (size_t l = 0; l < keys.size(); ++l) {
+            const int i = (int)(keys[l] / C), j = (int)(keys[l] % C);
+            const int bij = fill[i]++; col[bij] = j;
+            int bji = bij;
+            if (i != j) { bji = fill[j]++; col[bji] = i; }
+            lower[3 * l] = bij; lower[3 * l + 1] = bji; lower[3 * l + 2] = i == j ? i : -1;
+        }
+        auto up = [&](DeviceBuffer& b, const std::vector<int>& h) {
+            if (b.alloc(sizeof(int) * (h.size() + 4))) return -1;
+            return h.empty() || hipMemcpy(b.ptr, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+        };
+        if (up(sx_row_ptr_, row_ptr) || up(sx_col_, col) || up(sx_lower_, lower) || up(sx_term_ptr_, term_ptr) || up(sx_terms_, tq) ||
+            sx_W_.alloc((size_t)w_bytes) || sx_S_.alloc(sizeof(float) * 81 * (size_t)nblk + 64)) {
+            const std::string whyn = last_error();
+            set_error("bundle_adjustment: out of device memory for the assembled reduced camera matrix (%llu bytes): %s", bytes, whyn.c_str());
+            return -1;
+        }
+        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true;
+        return sx_nblk_;
+    }
+    int schur_assemble(LaunchCtx& c, const float* H, const float* Ge, const float* ctc) override
+    {
+        if (!sx_on_) return -1;
+        { TimedLaunch t(c, "SchurW"); const int rc = thallo_hip_ba_schur_w(O, P, (const int*)q_pt.ptr, (const float*)Jb.ptr, Ge, (float*)sx_W_.ptr, c.stream); if (rc < 0) return rc; }
+        TimedLaunch t(c, "SchurAssemble");
+        return thallo_hip_ba_schur_assemble(C, sx_nlower_, sx_nblk_, (const int*)sx_lower_.ptr, (const int*)sx_term_ptr_.ptr, (const int*)sx_terms_.ptr, (const float*)sx_W_.ptr, H, ctc,
+                                            (float*)sx_S_.ptr, c.stream);
+    }
     int schur_apply(LaunchCtx& c, const float* Ge, const float* x, const float* ctc, float* Sx, float* out, const unsigned* gate) override
     {
+        if (sx_on_) {      // (ctc is in the assembled diagonal blocks already)
+            TimedLaunch t(c, "SchurApplyS");
+            return thallo_hip_ba_schur_apply_s(C, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, x, Sx, out, gate, c.stream);
+        }
         TimedLaunch t(c, "SchurApply");
         return thallo_hip_ba_schur_apply(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, x, ctc, (float*)JpP.ptr, Sx, out,
                                          gate, c.stream);

@@ -267,6 +267,7 @@ const char* env_switch(const char* name)
         { "THALLO_FRONTEND_PRELOAD", "frontend_preload" },      // 0: every residual instance of a generated merged gather kernel loads for itself (round 4's lowering)
         { "THALLO_INC_LANES", "inc_lanes" },                    // N (a power of two <= 64): lanes per owner in the generated index-map gather kernels (default: by list length and owner count)
         { "THALLO_DELTA_FIRST_TOUCH", "delta_first_touch" },    // 0: PCGInit1 zeroes delta in every schedule, and the ring schedule's first delta update of a GN step reads those zeros back
+        { "THALLO_SCHUR_S_MAX_MB", "schur_s_max_mb" },          // N: the assembled reduced camera matrix (ThalloX_PlanSetLinearSolver kind 2) may take at most N MiB of device memory (default: a quarter of what is free)
         { "THALLO_PERSIST", "persist" },                        // 1: iterations 1 .. L-1 of a GN step of image_warping's marching kernel as persistent launches (bit-identical, measured slower)
     };
     for (const char* k : known) if (!strcmp(k, name)) return getenv(name);
@@ -392,7 +393,8 @@ void Plan::init(void** params)
     block_on_ = false;
     schur_on_ = false;
     if (schur_want_) { if (schur_prepare()) return; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
-    else if (block_want_) { if (block_prepare()) return; block_on_ = true; }
+    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes)
+    if (!schur_want_ && block_want_) { if (block_prepare()) return; block_on_ = true; }
     ready_ = true;
     if (dist_ && dist_->want_p2p && !dist_->checked && dist_self_check()) { ready_ = false; return; }
     if (dist_ && dist_->checked && dist_->p2p_on && dist_->form == DistForm::Slab) {      // (also right behind a self-check that has just passed: ADVICE r5)
@@ -606,6 +608,12 @@ int Plan::preconditioner_fallbacks()
 
 const char* Plan::schedule_name()
 {
+    if ((schur_on_ || schur_want_) && (schur_on_ ? schur_explicit_ : schur_explicit_want_)) {
+        schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras, assembled";
+        if (schur_on_ && schur_blocks_ >= 0) schedule_text_ += " (" + std::to_string(schur_blocks_) + " blocks)";
+        schedule_text_ += "; block-Jacobi on S";
+        return schedule_text_.c_str();
+    }
     if (schur_on_ || schur_want_) {
         schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras; block-Jacobi on S";
         return schedule_text_.c_str();
@@ -647,13 +655,15 @@ int Plan::step_gn_block(int ev_iter)
 // ------------------------------------------------------------------ Schur complement on the cameras (opt-in; ba_schur.hip, DESIGN.md "Schur complement on the cameras")
 int Plan::set_linear_solver(int kind)
 {
-    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; return 0; }
+    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG && kind != THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; schur_explicit_want_ = false; return 0; }
     if (!ok_) return -1;
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on a Schur complement", plugin->name()); return -1; }
-    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no Schur-complement solve for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name()); return -1; }
-    if (dist_) { set_error("%s: the Schur-complement solve runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
-    schur_want_ = true;
+    const bool ex = kind == THALLOX_SOLVER_SCHUR_EXPLICIT_PCG;
+    const char* what = ex ? "assembled Schur-complement solve" : "Schur-complement solve";
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a"); return -1; }
+    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
+    if (dist_) { set_error("%s: the %s runs on one GPU (this plan is distributed)", plugin->name(), what); return -1; }
+    schur_want_ = true; schur_explicit_want_ = ex;
     return 0;
 }
 
@@ -666,6 +676,11 @@ int Plan::schur_prepare()
     schur_n_ = (long)block_regions_.r[0].size * block_regions_.r[0].count;
     schur_hp_off_ = thallo_hip_block_floats(schur_regions_);
     schur_pt_off_ = block_regions_.r[1].offset;
+    // the assembled form: the structure of S, sized and checked against its budget before it is allocated; here, never inside a step
+    schur_explicit_ = false;
+    schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
+    if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
+    schur_explicit_ = schur_explicit_want_;
     if (schur_Ge_) return 0;
     const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
     auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
@@ -684,6 +699,7 @@ int Plan::schur_setup(const float* shift, const float* b, float* rz_out)
     if (rc < 0) return rc;
     { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(schur_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
     if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r)) < 0) return rc;
+    if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;      // (every step: B, the factor and in LM CtC are the step's)
     TimedLaunch t(ctx, "BlockApply");
     return thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, ctx.stream);
 }

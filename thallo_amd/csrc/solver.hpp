@@ -151,8 +151,9 @@ public:
     int  set_preconditioner(int kind);
     int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
     const char* schedule_name();          // the plugin's, and the block preconditioner / the Schur form when it runs
-    // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default) or THALLOX_SOLVER_SCHUR_PCG; takes effect at the next Init.  0 = ok
+    // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG or THALLOX_SOLVER_SCHUR_EXPLICIT_PCG; takes effect at the next Init.  0 = ok
     int  set_linear_solver(int kind);
+    int  schur_blocks() const { return schur_on_ && schur_explicit_ ? (int)schur_blocks_ : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
     int  schur_held_points();             // points the last step's elimination held fixed (-1: the Schur form does not run)
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
@@ -299,6 +300,8 @@ private:
     // ---- Schur complement on the cameras (opt-in; ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
     // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are allocated at Init too
     bool schur_want_ = false, schur_on_ = false;
+    bool schur_explicit_want_ = false, schur_explicit_ = false;      // kind 2 (asked for / running since the last Init): S assembled once per step by the plugin (ba_schur_explicit.hip), the loop's applies multiply by it
+    long schur_blocks_ = -1;                            // ... its stored blocks, known at Init
     thallo_block_regions_t schur_regions_;              // the camera region alone
     long schur_n_ = 0, schur_hp_off_ = 0, schur_pt_off_ = 0;      // camera unknowns; the point blocks' place in H; the points' place in the flat vector
     float *schur_Ge_ = nullptr, *schur_y_ = nullptr, *schur_g_ = nullptr;

@@ -57,16 +57,21 @@ def cat512():
             float(np.sqrt(np.float32(100.0))), float(np.sqrt(np.float32(0.01)))]
 
 
+SCHUR_FORMS = ("schur_pcg", "schur_explicit_pcg")      # linear solvers (set_linear_solver); the other forms are preconditioners of the full system
+
+
 def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
-    """One whole solve (Init + while Step) per pass, from the same start, in one of three forms: "jacobi" (the default plan), "block_jacobi" (the opt-in block
-    preconditioner) or "schur_pcg" (the opt-in Schur-complement solve; its preconditioner is the camera blocks).  Pass 1 (also the warm-up)
-    reads the PCG iterations and the cost after every step; then `reps` timed passes at timingLevel 0 with nothing else in the stream (wall clock, Init to the last Step);
+    """One whole solve (Init + while Step) per pass, from the same start, in one of four forms: "jacobi" (the default plan), "block_jacobi" (the opt-in block
+    preconditioner), "schur_pcg" (the opt-in Schur-complement solve; its preconditioner is the camera blocks) or "schur_explicit_pcg" (that solve with the reduced camera
+    matrix assembled once per step).  Pass 1 (also the warm-up)
+    reads the PCG iterations and the cost after every step; then `reps` timed passes at timingLevel 0 with nothing else in the stream (wall clock, Init to the last Step;
+    Init, which ends with a cost read back and in the assembled form builds the structure of S on the host, also on its own);
     then one pass at timingLevel 1 for the coarse "Linear Solve" events and one with every launch sampled for the kernel means."""
     def plan(timing):
         dev = [torch.from_numpy(x.copy()).cuda() for x in params]
         s = thallo_amd.ThalloSolver(dims, thallo_amd.energy_file("bundle_adjustment"), timing_level=timing, **({"solverkind": "levenberg_marquardt"} if lm else {}))
         if lm: s.enable_lm()
-        if precond == "schur_pcg": s.set_linear_solver(precond)
+        if precond in SCHUR_FORMS: s.set_linear_solver(precond)
         else: s.set_preconditioner(precond)
         s.set_solver_parameters(nIterations=nit, lIterations=lit, **sp)
         return s, s.make_params(dev), dev
@@ -75,17 +80,18 @@ def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
     costs, iters, fallbacks, held = [s.current_cost()], [], 0, 0
     while s.step(prm):
         costs.append(s.current_cost()); iters.append(len(s.alpha_beta_trace())); fallbacks += max(0, s.preconditioner_fallbacks()); held += max(0, s.schur_held_points())
-    sched = s.schedule_name
+    sched, blocks = s.schedule_name, s.schur_blocks()
     s.close()
-    whole = []
+    whole, inits = [], []
     for _ in range(reps):
         s, prm, dev = plan(0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         s.init(prm)
+        t1 = time.perf_counter()
         while s.step(prm): pass
         torch.cuda.synchronize()
-        whole.append((time.perf_counter() - t0) * 1e3)
+        whole.append((time.perf_counter() - t0) * 1e3); inits.append((t1 - t0) * 1e3)
         s.close()
     s, prm, dev = plan(1)
     s.init(prm)
@@ -103,6 +109,7 @@ def solve_ab(name, dims, params, nit, lit, lm, precond, reps=3, **sp):
     lin = ps["linearSolve"]
     return {"config": name, "preconditioner": precond, "schedule": sched, "pcg_iters_per_step": iters, "pcg_iters": sum(iters), "cost_after_each_step": costs,
             "whole_solve_ms": [round(x, 3) for x in whole], "whole_solve_ms_min": round(min(whole), 3),
+            "init_ms": [round(x, 3) for x in inits], "steps_ms": [round(w - i, 3) for w, i in zip(whole, inits)], "schur_blocks": blocks,
             "linear_solve_ms_per_step": round(lin["meanMS"], 4), "linear_solve_steps": lin["count"],
             "us_per_pcg_iter": round(lin["meanMS"] * lin["count"] / max(1, sum(iters)) * 1e3, 2), "fallbacks": fallbacks, "held_points": held, "kernel_mean_us": ks}
 
@@ -114,7 +121,7 @@ def gn_budget(dims, params, form, target, nit=7, budgets=(5, 10, 15, 20, 25, 35,
     for lit in budgets:
         dev = [torch.from_numpy(x.copy()).cuda() for x in params]
         s = thallo_amd.ThalloSolver(dims, thallo_amd.energy_file("bundle_adjustment"), timing_level=0)
-        if form == "schur_pcg": s.set_linear_solver(form)
+        if form in SCHUR_FORMS: s.set_linear_solver(form)
         else: s.set_preconditioner(form)
         s.set_solver_parameters(nIterations=nit, lIterations=lit)
         prm = s.make_params(dev)
@@ -146,15 +153,15 @@ if want("bundle_adjustment") or only == "ba":
     out.append(run("bundle_adjustment C=1723 P=156502 O=678718 GN x150", "bundle_adjustment", (p[0].shape[0], p[1].shape[0], p[2].shape[0]), p, 3, 150))
 if only == "ba":      # (on request only: the default set is what tools/profile_configs.sh profiles)
     # the opt-in block-Jacobi preconditioner and the opt-in Schur-complement solve against the default Jacobi path of the same build, whole solves from the same start, all in
-    # this one process (profiles/block_jacobi/, profiles/ba_schur/)
+    # this one process (profiles/block_jacobi/, profiles/ba_schur/, profiles/ba_schur_explicit/)
     d = (p[0].shape[0], p[1].shape[0], p[2].shape[0])
     rows = [("bundle_adjustment ladybug shape LM 5x150 q_tolerance 0.1", 5, 150, True, 3, dict(q_tolerance=0.1, function_tolerance=0.0)),
             ("bundle_adjustment ladybug shape GN 5x10", 5, 10, False, 3, {}),
             ("bundle_adjustment ladybug shape GN 5x25", 5, 25, False, 3, {}),
             ("bundle_adjustment ladybug shape GN 5x150", 5, 150, False, 3, {}),
             ("bundle_adjustment ladybug shape LM 2x150 q_tolerance 0 (every iteration runs: the loop's cost per iteration)", 2, 150, True, 1, dict(q_tolerance=0.0, function_tolerance=0.0))]
-    forms = ("jacobi", "block_jacobi", "schur_pcg")
-    for name, nit, lit, lm, reps, sp in rows:      # the three forms of a row one after the other
+    forms = ("jacobi", "block_jacobi", "schur_pcg", "schur_explicit_pcg")
+    for name, nit, lit, lm, reps, sp in rows:      # the four forms of a row one after the other
         for pc in forms:
             out.append(solve_ab(name, d, p, nit, lit, lm, pc, reps=reps, **sp))
     # the GN iteration budget at which each form reaches the default plan's 7 x 150 cost
