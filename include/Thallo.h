@@ -165,6 +165,21 @@ int ThalloX_PlanSchurBlocks(Thallo_Plan* plan);
  * -1 when the Schur form does not run.  ThalloX_PlanPreconditionerFallbacks then reports the camera blocks' fallbacks.  Synchronises the plan's stream. */
 int ThalloX_PlanSchurHeldPoints(Thallo_Plan* plan);
 
+/* Unknowns that are not to move: gauge fixing (one or two cameras), fixed intrinsics (components 6..8 of every camera), motion-only or structure-only bundle adjustment,
+ * known control points.  `input` is the Inputs{} index of an Unknown (bundle_adjustment: 0 cameras, 1 points); held is a HOST array of n = elements x components bytes in
+ * the caller's ids, held[element * components + k] != 0 meaning that this scalar is a constant of the solve; held == NULL clears that input's mask.  Every step is then the
+ * GN / LM step of the problem in the free unknowns, delta at a held scalar is exactly 0.0f and the unknown keeps its bits through Thallo_ProblemStep / Solve (an LM revert
+ * included); cost, model cost, the zeta test, accept / revert and the trust region run unchanged.  Works with every preconditioner and linear solver above; no launch is
+ * added to a PCG iteration.  A plan that never makes the call, clears its masks or holds nothing launches what it launches otherwise, bit for bit.  Between
+ * Thallo_ProblemPlan and Thallo_ProblemInit, or before a re-Init: it takes effect at the next Init, which fails (ThalloX_PlanReady 0) when the masks hold every unknown.
+ * Returns 0, or nonzero with ThalloX_LastError naming the energy and the reason: every energy but bundle_adjustment (generated ones included), a doublePrecision = 1 state,
+ * a distributed plan (ThalloX_PlanSetDistributed after this call is refused likewise), a direct-solve plan, an input that is not an Unknown, an n that is not
+ * elements x components. */
+int ThalloX_PlanSetHeldUnknowns(Thallo_Plan* plan, int input, const unsigned char* held, long n);
+/* Scalars held since the last Thallo_ProblemInit (ThalloX_PlanScheduleName then ends in "; N unknowns held"); -1 when no mask is in force.  ThalloX_PlanSchurHeldPoints keeps
+ * its meaning: the points the elimination's factor rule held. */
+long ThalloX_PlanHeldUnknowns(Thallo_Plan* plan);
+
 /* 1 if the most recent Thallo_ProblemInit on this plan succeeded (parameters bound, plugin prepared), else 0: Init itself returns void. */
 int ThalloX_PlanReady(Thallo_Plan* plan);
 

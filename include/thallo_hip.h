@@ -780,6 +780,18 @@ int thallo_hip_block_step2(thallo_block_regions_t regions, const float* G, float
 int thallo_hip_block_step2_lm(thallo_block_regions_t regions, const float* G, float* delta, const float* p, float* r, const float* Ap, float* z, const float* b,
                               thallo_sum_t alphaN, thallo_sum_t alphaD, float* betaN_out, float* q_out, const unsigned* gate, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- held unknowns (held.hip; opt-in, DESIGN.md "Held unknowns")
+ * mask: one byte per scalar of the flat vector, nonzero = the caller holds that unknown fixed.  Every product with M^-1 or Cp^-1 gets a zero row and column at a held
+ * scalar, so z, p and delta stay zero there and PCG runs on the free principal submatrix.  A few launches per step, none per PCG iteration. */
+/* Point Jacobi, behind PCGInit1 (GN) or PCGFinalizeDiagonal (LM): pre[i] = z[i] = 0 where mask[i]; the partials of r . z over all n scalars anew (returns their number). */
+int thallo_hip_hold_pcg(const unsigned char* mask, const float* r, float* pre, float* z, long n, float* rz_out, thallo_stream_t stream);
+/* H (regions and layout of thallo_hip_block_factor), in front of a factor launch: a held scalar's row and column of its block become those of the identity.  The scaled
+ * Cholesky then leaves exactly one nonzero of G in that row and column, the diagonal one. */
+int thallo_hip_block_hold(thallo_block_regions_t regions, const unsigned char* mask, float* H, thallo_stream_t stream);
+/* G, behind the factor launch: that row and column become zero.  G^T G is then the inverse of the block's free principal sub-block bordered by zeros; a fully held block
+ * has G = 0 (thallo_hip_ba_schur_factor's held-point rule). */
+int thallo_hip_block_hold_factor(thallo_block_regions_t regions, const unsigned char* mask, float* G, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- Schur complement on the cameras (ba_schur.hip; opt-in, DESIGN.md "Schur complement on the cameras")
  * Bundle adjustment with the points eliminated exactly through their 3 x 3 blocks: with A = J^T J (+ diag(CtC) in LM) = [[B, E], [E^T, Cp]] and b = [b_c; b_p],
  * S = B - E Cp^-1 E^T, g = b_c - E Cp^-1 b_p, PCG on S delta_c = g, delta_p = Cp^-1 (b_p - E^T delta_c).  Index lists, Jb and JP as thallo_hip_ba_block_diag takes them (the

@@ -103,6 +103,8 @@ def lib():
     L.ThalloX_PlanSetLinearSolver.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetLinearSolver.restype = C.c_int
     L.ThalloX_PlanSchurHeldPoints.argtypes = [vp]; L.ThalloX_PlanSchurHeldPoints.restype = C.c_int
     L.ThalloX_PlanSchurBlocks.argtypes = [vp]; L.ThalloX_PlanSchurBlocks.restype = C.c_int
+    L.ThalloX_PlanSetHeldUnknowns.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetHeldUnknowns.restype = C.c_int
+    L.ThalloX_PlanHeldUnknowns.argtypes = [vp]; L.ThalloX_PlanHeldUnknowns.restype = C.c_long
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -409,6 +411,23 @@ class ThalloSolver:
     def schur_blocks(self):
         """Stored 9 x 9 blocks of the assembled reduced camera matrix after init() (-1: the assembled form does not run)."""
         return self._L.ThalloX_PlanSchurBlocks(self.plan)
+
+    def hold(self, input, mask):
+        """Unknowns that are not to move (include/Thallo.h ThalloX_PlanSetHeldUnknowns): `input` is the Inputs{} index of an Unknown (bundle_adjustment: 0 cameras,
+        1 points), `mask` an array of elements x components flags in the caller's ids (nonzero = held), or None to clear that input's mask; before init().  Raises, with
+        the library's reason, where the plan cannot hold unknowns."""
+        if mask is None:
+            rc = self._L.ThalloX_PlanSetHeldUnknowns(self.plan, int(input), None, 0)
+        else:
+            import numpy as np
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+            rc = self._L.ThalloX_PlanSetHeldUnknowns(self.plan, int(input), m.ctypes.data_as(C.c_void_p), int(m.size))
+        if rc != 0:
+            raise RuntimeError("ThalloX_PlanSetHeldUnknowns failed: " + last_error())
+
+    def held_unknowns(self):
+        """Scalars held since the last init() (-1: no mask in force)."""
+        return self._L.ThalloX_PlanHeldUnknowns(self.plan)
 
     def set_kernel_sampling(self, period):
         self._L.ThalloX_SetKernelSampling(self.plan, period)

@@ -224,7 +224,9 @@ public:
     // (also into r_out); apply: Sx = S x (+ ctc x) for a first-region vector and the partials of x . S x -> their number; back: the second region of delta from its first
     // (p non-NULL: delta_c += (aN / aD) p first)
     virtual bool schur_ok() const { return false; }
-    virtual int schur_reduce(LaunchCtx&, const float* /*Hp*/, const float* /*shift_p*/, float* /*Ge*/, unsigned* /*held*/, const float* /*b*/, float* /*y*/, float* /*g*/, float* /*r_out*/) { return -1; }
+    // (hold: the plan's mask of held unknowns over the flat vector or NULL -- the elimination factor then gets zero rows and columns there: thallo_hip_block_hold_factor)
+    virtual int schur_reduce(LaunchCtx&, const float* /*Hp*/, const float* /*shift_p*/, float* /*Ge*/, unsigned* /*held*/, const float* /*b*/, float* /*y*/, float* /*g*/, float* /*r_out*/,
+                             const unsigned char* /*hold*/) { return -1; }
     virtual int schur_apply(LaunchCtx&, const float* /*Ge*/, const float* /*x*/, const float* /*ctc*/, float* /*Sx*/, float* /*xSx_out*/, const unsigned* /*gate*/) { return -1; }
     // the assembled form (ThalloX_PlanSetLinearSolver kind 2; ba_schur_explicit.hip).  schur_explicit(true), at Init behind prepare(): build the symbolic structure of S in the
     // plan's internal ids and allocate it -> the stored blocks, or -1 with the reason set (budget, int32 indices, memory); from then on schur_apply multiplies by the
@@ -233,6 +235,10 @@ public:
     virtual long schur_explicit(bool /*on*/) { return -1; }
     virtual int schur_assemble(LaunchCtx&, const float* /*H*/, const float* /*Ge*/, const float* /*ctc*/) { return -1; }
     virtual int schur_back(LaunchCtx&, const float* /*Ge*/, const float* /*b*/, float* /*delta*/, const float* /*p*/, thallo_sum_t /*aN*/, thallo_sum_t /*aD*/) { return -1; }
+    // ---- held unknowns (opt-in: ThalloX_PlanSetHeldUnknowns; held.hip): plugins all of whose PCG routes form M^-1 from the stored SolverVectors::pre.  hold_to_internal,
+    // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
+    virtual bool hold_ok() const { return false; }
+    virtual void hold_to_internal(int /*k*/, const unsigned char* /*caller*/, unsigned char* /*flat*/) const {}
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale

@@ -783,6 +783,7 @@ class BundleAdjustmentPlugin : public EnergyPlugin {
     // between ranks, each of which would choose another order.  THALLO_AB=ba_renumber=0 / 1: never / always.
     bool perm_ = false, import_pending_ = true, no_renumber_ = false;
     DeviceBuffer ptsP, d_new2old, oToP_int;
+    std::vector<int> h_new2old_;          // (the host's copy: a mask of held points arrives in the caller's ids)
     hipStream_t stream_ = nullptr;
     float* Pts() { return perm_ ? (float*)ptsP.ptr : points; }
     const int* OToP() const { return perm_ ? (const int*)oToP_int.ptr : oToP; }
@@ -832,6 +833,7 @@ public:
                 for (int j = 0; j < P; ++j) new2old[j] = j;
                 std::stable_sort(new2old.begin(), new2old.end(), [&](int x, int y) { return first[x] < first[y]; });
                 for (int j = 0; j < P; ++j) old2new[new2old[j]] = j;
+                h_new2old_ = new2old;
                 for (int o = 0; o < O; ++o) op[o] = old2new[op[o]];
                 if (ptsP.alloc(sizeof(float) * 3 * (size_t)P + 64) || d_new2old.alloc(sizeof(int) * ((size_t)P + 4)) || oToP_int.alloc(sizeof(int) * ((size_t)O + 4)) ||
                     hipMemcpy(d_new2old.ptr, new2old.data(), sizeof(int) * P, hipMemcpyHostToDevice) != hipSuccess ||
@@ -931,9 +933,14 @@ public:
     }
     // Schur complement on the cameras: the launches load the camera half of Jb (what block_diag summed), the packed point blocks JP, and use JpP as their u / v / t scratch
     bool schur_ok() const override { return true; }
-    int schur_reduce(LaunchCtx& c, const float* Hp, const float* shift_p, float* Ge, unsigned* held, const float* b, float* y, float* g, float* r_out) override
+    int schur_reduce(LaunchCtx& c, const float* Hp, const float* shift_p, float* Ge, unsigned* held, const float* b, float* y, float* g, float* r_out, const unsigned char* hold) override
     {
         { TimedLaunch t(c, "SchurFactor"); const int rc = thallo_hip_ba_schur_factor(P, Hp, shift_p, Ge, held, c.stream); if (rc < 0) return rc; }
+        if (hold) {
+            TimedLaunch t(c, "BlockHoldFactor");
+            thallo_block_regions_t pts = block_regions(); pts.r[0] = pts.r[1]; pts.n = 1;
+            const int rc = thallo_hip_block_hold_factor(pts, hold, Ge, c.stream); if (rc < 0) return rc;
+        }
         TimedLaunch t(c, "SchurReduce");
         return thallo_hip_ba_schur_rhs(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, y, (float*)JpP.ptr, g, r_out,
                                        c.stream);
@@ -1051,6 +1058,13 @@ public:
         TimedLaunch t(c, "SchurBack");
         return thallo_hip_ba_schur_back(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, delta, p, aN, aD,
                                         (float*)JpP.ptr, c.stream);
+    }
+    // held unknowns: every PCG route of this plugin takes M^-1 from v.pre (the flat updates, k_cam2 / k_pt2's sums, the residual reset) or from G
+    bool hold_ok() const override { return true; }
+    void hold_to_internal(int k, const unsigned char* caller, unsigned char* flat) const override
+    {
+        if (k == 0) { memcpy(flat, caller, 9 * (size_t)C); return; }
+        for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3);
     }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }

@@ -390,6 +390,7 @@ void Plan::init(void** params)
             return;
         }
     }
+    if (held_prepare()) return;
     block_on_ = false;
     schur_on_ = false;
     if (schur_want_) { if (schur_prepare()) return; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
@@ -501,8 +502,9 @@ bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
     cur_ = 0;
     SolverVectors v_init = v_;
     if (delta_unset) v_init.delta = nullptr;
-    const int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
+    int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
+    if (held_on() && (nb = hold_pcg(slot(2))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return false; }      // (p_0 = M^-1 r_0 is formed behind it, from pre)
     set_nb(2, nb); finish(2);
     ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
     return true;
@@ -539,7 +541,7 @@ int Plan::step_gn(int ev_iter)
     }
     if (schur_on_) return step_gn_schur(ev_iter);
     if (block_on_) return step_gn_block(ev_iter);
-    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok()) return step_gn_resident(ev_iter);
+    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan)
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
     const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
@@ -561,6 +563,51 @@ int Plan::step_gn(int ev_iter)
     const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, batched);
     return gn_end(ev_fin, ev_iter);
+}
+
+// ------------------------------------------------------------------ held unknowns (opt-in; held.hip, DESIGN.md "Held unknowns")
+int Plan::set_held_unknowns(int input, const unsigned char* held, long n)
+{
+    if (!ok_) return -1;
+    const auto& imgs = plugin->unknown_images();
+    int k = -1;
+    for (size_t i = 0; i < imgs.size(); ++i) if (imgs[i].param_index == input) k = (int)i;
+    if (!held) { if (k >= 0) held_masks_.erase(k); return 0; }
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to hold unknowns in", plugin->name()); return -1; }
+    if (!plugin->hold_ok()) { set_error("%s: no held unknowns for this energy (not every PCG route of its plugin takes M^-1 from the stored vector; bundle_adjustment's do)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: held unknowns run on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (k < 0) { set_error("%s: input %d is not an Unknown of this energy", plugin->name(), input); return -1; }
+    if (n != imgs[(size_t)k].n_floats) { set_error("%s: the mask of input %d has %ld bytes, the unknown has %ld scalars (elements x components)", plugin->name(), input, n, imgs[(size_t)k].n_floats); return -1; }
+    held_masks_[k].assign(held, held + n);
+    return 0;
+}
+
+int Plan::held_prepare()
+{   // Init, behind prepare() (the plugin's numbering is decided): the masks in the plan's internal ids, counted, uploaded -- never inside a step
+    held_count_ = -1; held_first_ = 0;
+    if (held_masks_.empty()) return 0;
+    if (dist_ || plugin->direct_solve() || !plugin->hold_ok()) { set_error("%s: held unknowns need a one-GPU PCG plan", plugin->name()); return -1; }
+    std::vector<unsigned char> flat((size_t)v_.n, 0);
+    for (const auto& m : held_masks_) plugin->hold_to_internal(m.first, m.second.data(), flat.data());
+    long count = 0;
+    for (unsigned char f : flat) count += f != 0;
+    if (count == v_.n) { set_error("%s: the mask holds every unknown (%ld scalars): nothing is left to solve for", plugin->name(), count); return -1; }
+    { const long n0 = plugin->unknown_images()[0].n_floats; for (long i = 0; i < n0; ++i) held_first_ += flat[(size_t)i] != 0; }
+    held_count_ = count;
+    if (count == 0) return 0;      // (nothing held: the plan launches what it launches without a mask)
+    if (!held_mask_) {
+        DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b);
+        if (b->alloc((size_t)v_.n_alloc + 64)) { held_count_ = -1; set_error("%s: out of device memory for the mask of held unknowns", plugin->name()); return -1; }
+        held_mask_ = (unsigned char*)b->ptr;
+    }
+    if (hipMemcpy(held_mask_, flat.data(), flat.size(), hipMemcpyHostToDevice) != hipSuccess) { held_count_ = -1; set_error("%s: cannot upload the mask of held unknowns", plugin->name()); return -1; }
+    return 0;
+}
+
+int Plan::hold_pcg(float* rz_out)
+{
+    TimedLaunch t(ctx, "HoldPCG");
+    return thallo_hip_hold_pcg(held_mask_, v_.r, v_.pre, v_.z, v_.n, rz_out, ctx.stream);
 }
 
 // ------------------------------------------------------------------ block-Jacobi preconditioner (opt-in; block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
@@ -593,7 +640,9 @@ int Plan::block_setup(const float* shift, const unsigned* gate, float* rz_out)
 {
     int rc = plugin->block_diag(ctx, block_H_);
     if (rc < 0) return rc;
+    if (held_on()) { TimedLaunch t(ctx, "BlockHold"); if ((rc = thallo_hip_block_hold(block_regions_, held_mask_, block_H_, ctx.stream)) < 0) return rc; }
     { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(block_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
+    if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(block_regions_, held_mask_, block_G_, ctx.stream)) < 0) return rc; }
     TimedLaunch t(ctx, "BlockApply");
     return thallo_hip_block_apply(block_regions_, block_G_, v_.r, v_.z, rz_out, gate, ctx.stream);
 }
@@ -607,6 +656,14 @@ int Plan::preconditioner_fallbacks()
 }
 
 const char* Plan::schedule_name()
+{
+    const char* base = schedule_base();
+    if (!held_on()) return base;
+    held_text_ = std::string(base) + "; " + std::to_string(held_count_) + " unknowns held";
+    return held_text_.c_str();
+}
+
+const char* Plan::schedule_base()
 {
     if ((schur_on_ || schur_want_) && (schur_on_ ? schur_explicit_ : schur_explicit_want_)) {
         schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras, assembled";
@@ -632,6 +689,7 @@ int Plan::step_gn_block(int ev_iter)
     cur_ = 0;
     int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
+    if (held_on() && (nb = hold_pcg(slot(B))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return 0; }      // (pre: the blocks' fallback)
     nb = block_setup(nullptr, nullptr, slot(B));
     if (nb < 0) { set_error("block preconditioner set-up failed (%d)", nb); return 0; }
     set_nb(B, nb); finish(B);
@@ -697,8 +755,12 @@ int Plan::schur_setup(const float* shift, const float* b, float* rz_out)
 {   // behind PCGInit1 (+ PCGFinalizeDiagonal in LM): r = b = -J^T F over all unknowns, pre = the point-Jacobi M^-1 (the camera blocks' fallback)
     int rc = plugin->block_diag(ctx, block_H_);
     if (rc < 0) return rc;
+    // held unknowns: H of both regions in one launch (the camera blocks and the point blocks lie one behind the other), G of the camera region here, the elimination
+    // factor inside schur_reduce; g, W, the assembly, both applies and the back-substitution inherit the rule through the two factors
+    if (held_on()) { TimedLaunch t(ctx, "BlockHold"); if ((rc = thallo_hip_block_hold(block_regions_, held_mask_, block_H_, ctx.stream)) < 0) return rc; }
     { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(schur_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
-    if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r)) < 0) return rc;
+    if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(schur_regions_, held_mask_, block_G_, ctx.stream)) < 0) return rc; }
+    if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
     if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;      // (every step: B, the factor and in LM CtC are the step's)
     TimedLaunch t(ctx, "BlockApply");
     return thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, ctx.stream);
@@ -715,12 +777,13 @@ int Plan::schur_held_points()
 int Plan::step_gn_schur(int ev_iter)
 {   // step_gn_block's loop on the reduced system (S, g): every vector of the loop is its camera part ([0, 9 C) of the plan's vectors); the point part of r stays b_p, which
     // the back-substitution reads.  The loop's last delta_c += alpha p rides in the back-substitution's camera launch; PCGLinearUpdate then adds the complete delta.
-    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    const int L = schur_empty() ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
     const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
     cur_ = 0;
     int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
+    if (held_on() && (nb = hold_pcg(slot(B))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return 0; }      // (pre: the camera blocks' fallback)
     nb = schur_setup(nullptr, v_.r, slot(B));
     if (nb < 0) { set_error("Schur-complement set-up failed (%d)", nb); return 0; }
     set_nb(B, nb); finish(B);
@@ -753,7 +816,7 @@ int Plan::step_gn_schur(int ev_iter)
 void Plan::lm_loop_schur(LmStep& st)
 {
     hipStream_t s = st.s;
-    const int L = st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const int L = schur_empty() ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
     const long n = schur_n_;
     float* p = v_.p[0];
     int nb = 0;
@@ -1210,6 +1273,10 @@ bool Plan::lm_setup(LmStep& st)
                                                  sp.nIter == 0 ? 1 : 0, st.pc ? 1 : 0, slot(B), s);
             st.check(nb, "PCGFinalizeDiagonal launch");
         }
+    }
+    if (held_on() && !st.skip()) {      // pre = z = 0 at the held scalars, alphaN_0 over the free ones; behind it every launch forms M^-1 r from pre (or from the blocks below)
+        nb = hold_pcg(slot(B));
+        st.check(nb, "held unknowns: the mask launch");
     }
     if (schur_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; r_c becomes g, z_c and alphaN_0 the reduced system's.  Every step: CtC follows the trust-region radius
         nb = schur_setup(v_.CtC, v_.b, slot(B));

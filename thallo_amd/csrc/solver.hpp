@@ -155,6 +155,10 @@ public:
     int  set_linear_solver(int kind);
     int  schur_blocks() const { return schur_on_ && schur_explicit_ ? (int)schur_blocks_ : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
     int  schur_held_points();             // points the last step's elimination held fixed (-1: the Schur form does not run)
+    // ThalloX_PlanSetHeldUnknowns: the mask of one Unknown (host bytes in the caller's ids, nonzero = that scalar is a constant of the solve; NULL clears it); takes effect
+    // at the next Init.  0 = ok
+    int  set_held_unknowns(int input, const unsigned char* held, long n);
+    long held_unknowns() const { return ready_ ? held_count_ : -1; }      // held scalars since the last Init (-1: no mask in force)
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
     int  set_ghost_exchange(int n_boundary, const int* boundary_units, int n_ghost, const int* ghost_units, const int* ghost_src_rank, const int* ghost_src_pos);
@@ -287,6 +291,20 @@ private:
     float compute_cost();
     float* host_words();
     int   step_gn(int ev_iter);
+    // ---- held unknowns (opt-in; held.hip): the caller's masks by unknown image; since the last Init their count and the mask over the flat vector in the plan's internal
+    // ids on the device (built and uploaded at Init, never inside a step).  The launches run only when something is held
+    std::map<int, std::vector<unsigned char>> held_masks_;
+    long held_count_ = -1;
+    unsigned char* held_mask_ = nullptr;
+    std::string held_text_;
+    long held_first_ = 0;                               // ... of them in the first unknown image (the Schur form's kept region)
+    bool  held_on() const { return held_count_ > 0; }
+    // every unknown of the reduced system is held (structure-only bundle adjustment on a Schur plan): the reduced system is empty, its PCG loop takes no iteration (p_0 = 0
+    // would make LM's unguarded alpha_0 = 0 / 0) and the back-substitution from delta_c = 0 is the whole solve
+    bool  schur_empty() const { return schur_on_ && held_on() && held_first_ == schur_n_; }
+    int   held_prepare();
+    int   hold_pcg(float* rz_out);                      // pre = z = 0 at the held scalars, the partials of r . z anew -> their number
+    const char* schedule_base();                        // schedule_name() without the held count
     // ---- block-Jacobi preconditioner (opt-in; block_precond.hip).  want: what ThalloX_PlanSetPreconditioner asked for; on: what this solve runs (decided at Init, where
     // H, G and the status word are allocated -- never inside a step)
     bool block_want_ = false, block_on_ = false;
