@@ -180,6 +180,26 @@ int ThalloX_PlanSetHeldUnknowns(Thallo_Plan* plan, int input, const unsigned cha
  * its meaning: the points the elimination's factor rule held. */
 long ThalloX_PlanHeldUnknowns(Thallo_Plan* plan);
 
+/* A robust loss for observations that are mismatches: one loss over the whole residual vector of an observation (bundle_adjustment: its 2 reprojection components).  With
+ * s = |r|^2 of an observation and scale a > 0 in residual units (pixels) the cost becomes sum_o 1/2 rho(s_o):
+ *   THALLOX_LOSS_TRIVIAL  rho = s                                        (the default: the squared loss)
+ *   THALLOX_LOSS_HUBER    rho = s for s <= a^2, 2 a sqrt(s) - a^2 beyond;   rho' = 1, a / sqrt(s)
+ *   THALLOX_LOSS_CAUCHY   rho = a^2 log(1 + s / a^2);                       rho' = 1 / (1 + s / a^2)
+ * Linearisation is first order (iteratively reweighted least squares; Triggs' correction without the rho'' term): with w = sqrt(rho'(s)) in float32 every step is the GN / LM
+ * step of J_s = w J, F_s = w F, so -J_s^T F_s is the exact gradient of the robust cost; Thallo_ProblemCurrentCost, the accept / revert test and function_tolerance see the
+ * robust cost.  Works with every preconditioner, linear solver and mask above; no launch is added to a step.  A plan that never makes the call, or sets
+ * THALLOX_LOSS_TRIVIAL, launches what it launches otherwise, bit for bit.  Between Thallo_ProblemPlan and Thallo_ProblemInit, or before a re-Init: it takes effect at the
+ * next Init; ThalloX_PlanScheduleName then carries "; huber loss, scale 2" / "; cauchy loss, scale 2" (in front of the held count).  Returns 0, or nonzero with
+ * ThalloX_LastError naming the energy and the reason: every energy but bundle_adjustment (generated ones included), a doublePrecision = 1 state, a distributed plan
+ * (ThalloX_PlanSetDistributed after this call is refused likewise), a direct-solve plan, an unknown kind, a scale that is not finite and positive (Huber, Cauchy). */
+#define THALLOX_LOSS_TRIVIAL 0
+#define THALLOX_LOSS_HUBER   1
+#define THALLOX_LOSS_CAUCHY  2
+int ThalloX_PlanSetRobustLoss(Thallo_Plan* plan, int kind, float scale);
+/* rho'(s) of every observation at the last linearisation (1 before the first), in (0, 1], into the HOST array host_out[n], the caller's observation ids: what a caller reads
+ * the inliers off.  Returns the number of observations, or -1 when no loss is in force since the last Init or n is not that number.  Synchronises the plan's stream. */
+long ThalloX_PlanRobustWeights(Thallo_Plan* plan, float* host_out, long n);
+
 /* 1 if the most recent Thallo_ProblemInit on this plan succeeded (parameters bound, plugin prepared), else 0: Init itself returns void. */
 int ThalloX_PlanReady(Thallo_Plan* plan);
 

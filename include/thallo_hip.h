@@ -523,6 +523,19 @@ int thallo_hip_ba_compute_j_ad(int O, const float* cameras, const float* points,
 int thallo_hip_ba_pcg_init(int C, int P, const int* cam_ptr, const int* q_pt, const int* pt_ptr, const int* pt_pos, const int* q_cam,
                            const float* Jb, const float* F, float* r, float* pre, float* z, float* p_prev, float* delta,
                            float* diag_out, float* alphaN_out, thallo_stream_t stream);
+/* Robust losses (opt-in, DESIGN.md "Robust losses"): one loss over the 2-vector residual of an observation, cost = sum_o 1/2 rho(s_o), s = r0^2 + r1^2, scale a > 0 in
+ * residual units.  Huber: rho = s (s <= a^2), 2 a sqrt(s) - a^2 beyond; Cauchy: rho = a^2 log(1 + s / a^2).  First order (IRLS): with w = sqrt(rho'(s)) in float32 the
+ * block of an observation and its residual are multiplied by w wherever they are formed.  cost_robust: the partials of sum 1/2 rho(s) (returns their number);
+ * compute_j_robust: Jb = w x block, F = w x residual, and w[q] (O floats, camera order q).  Behind it thallo_hip_ba_pack_point_blocks, thallo_hip_ba_pcg_init,
+ * thallo_hip_ba_block_diag and the Schur launches read the scaled arrays as they are; the four launches that REBUILD the block (below: thallo_hip_ba_apply_jtj2_fin, _lm,
+ * thallo_hip_ba_pcg_apply_lm, thallo_hip_ba_lm_reset_residual) have a _robust form that takes w and applies, bit for bit, the stored matrix.  An unknown kind, a scale that
+ * is not finite and positive or w == NULL is an error: these entry points never run the squared loss. */
+#define THALLO_HIP_LOSS_HUBER  1
+#define THALLO_HIP_LOSS_CAUCHY 2
+int thallo_hip_ba_cost_robust(int C, int P, int O, const float* cameras, const float* points, const float* observations,
+                              const int* oToC, const int* oToP, int kind, float scale, float* cost_out, thallo_stream_t stream);
+int thallo_hip_ba_compute_j_robust(int O, const float* cameras, const float* points, const float* observations,
+                                   const int* cam_obs, const int* q_cam, const int* q_pt, int kind, float scale, float* Jb, float* F, float* w, thallo_stream_t stream);
 
 /* ---------------------------------------------------------------- E3: examples/shape_from_shading/shape_from_shading.t
  * params 0-15 host scalars (w_p, w_s, w_g = SQUARED weights, f_x, f_y, u_x, u_y, L_1..L_9), X float unknown (16), D_i (17),
@@ -722,6 +735,21 @@ int thallo_hip_ba_pcg_apply_lm(int C_, int P_, const int* cam_ptr, const int* q_
                                const float* cameras, const float* points, const float* JP, float* JpC, const float* p, const float* CtC, float* Ap, float* alphaD_out,
                                const float* r, const float* pre, const float* delta, const float* b, double* s3_out, double* q3_out, thallo_fin_t fin,
                                float* lm_state, int k, float q_tolerance, int q_in, int q_out, thallo_stream_t stream);
+/* The launches above and thallo_hip_ba_apply_jtj2_fin / _lm of a plan with a robust loss (thallo_hip_ba_compute_j_robust): the camera launch loads w[q] next to q_pt[q] and
+ * multiplies the 24 rebuilt entries by it; everything else -- arguments, sums, return values -- as the plain form. */
+int thallo_hip_ba_lm_reset_residual_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                           const float* cameras, const float* points, const float* JP, float* JpC, const float* delta, const float* CtC, const float* b, const float* pre,
+                                           float* r, float* betaN_out, const unsigned* gate, const float* w, thallo_stream_t stream);
+int thallo_hip_ba_pcg_apply_lm_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                      const float* cameras, const float* points, const float* JP, float* JpC, const float* p, const float* CtC, float* Ap, float* alphaD_out,
+                                      const float* r, const float* pre, const float* delta, const float* b, double* s3_out, double* q3_out, thallo_fin_t fin,
+                                      float* lm_state, int k, float q_tolerance, int q_in, int q_out, const float* w, thallo_stream_t stream);
+int thallo_hip_ba_apply_jtj2_fin_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                        const float* cameras, const float* points, const float* JP, float* JpC, const float* p, float* Ap, float* alphaD_out,
+                                        const float* r, const float* pre, double* s3_out, const unsigned* gate, thallo_fin_t fin, const float* w, thallo_stream_t stream);
+int thallo_hip_ba_apply_jtj2_lm_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                       const float* cameras, const float* points, const float* JP, float* JpC, const float* p, const float* CtC, float* Ap, float* alphaD_out,
+                                       const unsigned* gate, const float* w, thallo_stream_t stream);
 /* ... and with the finish deferred (round 4): thallo_hip_ba_pcg_apply_lm with fin.tickets = NULL leaves partials only, and the flat update of the NEXT iteration
  * (thallo_hip_pcg_update_lm_fin) finishes alphaD, betaN, q and the zeta test in every workgroup before it updates -- the same arithmetic and order.  q_in / q_out: the words of
  * lm_state Q0 is read from / Q1 is left in (0 and 6 by the iteration's parity in that loop, so that no launch reads a word one of its workgroups writes; 0, 0 in the loop that

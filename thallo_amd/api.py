@@ -105,6 +105,9 @@ def lib():
     L.ThalloX_PlanSchurBlocks.argtypes = [vp]; L.ThalloX_PlanSchurBlocks.restype = C.c_int
     L.ThalloX_PlanSetHeldUnknowns.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetHeldUnknowns.restype = C.c_int
     L.ThalloX_PlanHeldUnknowns.argtypes = [vp]; L.ThalloX_PlanHeldUnknowns.restype = C.c_long
+    if hasattr(L, "ThalloX_PlanSetRobustLoss"):      # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_robust_bench.py --ab)
+        L.ThalloX_PlanSetRobustLoss.argtypes = [vp, C.c_int, C.c_float]; L.ThalloX_PlanSetRobustLoss.restype = C.c_int
+        L.ThalloX_PlanRobustWeights.argtypes = [vp, vp, C.c_long]; L.ThalloX_PlanRobustWeights.restype = C.c_long
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -428,6 +431,26 @@ class ThalloSolver:
     def held_unknowns(self):
         """Scalars held since the last init() (-1: no mask in force)."""
         return self._L.ThalloX_PlanHeldUnknowns(self.plan)
+
+    ROBUST_LOSSES = {"trivial": 0, "huber": 1, "cauchy": 2}
+
+    def set_robust_loss(self, kind, scale=1.0):
+        """A robust loss over each observation's residual (include/Thallo.h ThalloX_PlanSetRobustLoss): kind "trivial" (the squared loss, the default), "huber" or
+        "cauchy", scale in residual units (pixels); before init().  Raises, with the library's reason, where the plan cannot run one."""
+        k = self.ROBUST_LOSSES.get(kind, kind)
+        if not isinstance(k, int):
+            raise ValueError("robust loss %r: one of %s" % (kind, sorted(self.ROBUST_LOSSES)))
+        if self._L.ThalloX_PlanSetRobustLoss(self.plan, k, float(scale)) != 0:
+            raise RuntimeError("ThalloX_PlanSetRobustLoss failed: " + last_error())
+
+    def robust_weights(self):
+        """rho'(s) per observation at the last linearisation, numpy float32 [O] in the caller's observation ids, values in (0, 1] (1 = the loss treats the observation as
+        the squared loss does); raises when no loss is in force since the last init()."""
+        import numpy as np
+        out = np.empty(int(self._dims[2]), np.float32)      # (bundle_adjustment: dims = (cameras, points, observations); any other plan answers -1 below)
+        if self._L.ThalloX_PlanRobustWeights(self.plan, out.ctypes.data_as(C.c_void_p), int(out.size)) != out.size:
+            raise RuntimeError("ThalloX_PlanRobustWeights: no robust loss in force on this plan (or it has another number of observations)")
+        return out
 
     def set_kernel_sampling(self, period):
         self._L.ThalloX_SetKernelSampling(self.plan, period)

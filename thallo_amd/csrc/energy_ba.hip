@@ -168,28 +168,54 @@ __device__ __forceinline__ Blk ba_block(const CamPre& c, float X0, float X1, flo
     return b;
 }
 
+// ------------------------------------------------------------------------------------------ robust losses (opt-in; DESIGN.md "Robust losses")
+// One loss over the 2-vector residual of an observation: cost = sum_o 1/2 rho(s_o), s = r0^2 + r1^2, scale a in residual units.  LOSS 0: rho = s (the instantiations
+// every plan without a loss launches; their argument struct is empty).  1 Huber: rho = s (s <= a^2), 2 a sqrt(s) - a^2 beyond; rho' = 1, a / sqrt(s).  2 Cauchy:
+// rho = a^2 log(1 + s / a^2); rho' = 1 / (1 + s / a^2).  First order (IRLS, Triggs without rho''): the block of an observation and its residual are multiplied by
+// w = sqrt(rho'(s)) wherever they are formed -- precomputeJ (which also writes w[q], camera order) and k_cam2 (which loads it).
+template <int LOSS> struct LossArgs { float a, a2, ia2; };      // a, a * a, 1 / (a * a)
+template <> struct LossArgs<0> {};
+template <int LOSS> struct LossOut { float* w; };
+template <> struct LossOut<0> {};
+template <int LOSS> __device__ __forceinline__ float loss_w(const LossArgs<LOSS>& l, float s)
+{
+    if (LOSS == 1) return s <= l.a2 ? 1.0f : sqrtf(l.a / sqrtf(s));      // (an inlier -- s = 0 included -- never divides by sqrt(s))
+    return sqrtf(1.0f / (1.0f + s * l.ia2));
+}
+template <> __device__ __forceinline__ float loss_w<0>(const LossArgs<0>&, float) { return 1.0f; }
+template <int LOSS> __device__ __forceinline__ float loss_rho(const LossArgs<LOSS>& l, float s)
+{
+    if (LOSS == 1) return s <= l.a2 ? s : 2.0f * l.a * sqrtf(s) - l.a2;
+    return l.a2 * log1pf(s * l.ia2);
+}
+template <> __device__ __forceinline__ float loss_rho<0>(const LossArgs<0>&, float s) { return s; }
+
 // computeCost: per observation (any order)
+template <int LOSS>
 __global__ __launch_bounds__(BLOCK) void k_cost(int O_, const float* __restrict__ cams, const float* __restrict__ pts,
                                                 const float2* __restrict__ obs, const int* __restrict__ oToC, const int* __restrict__ oToP,
-                                                float* __restrict__ out)
+                                                float* __restrict__ out, LossArgs<LOSS> loss)
 {
     __shared__ float red[16];
     float acc = 0.0f;
     for (int o = blockIdx.x * BLOCK + threadIdx.x; o < O_; o += gridDim.x * BLOCK) {
         float r0, r1; const float2 ob = obs[o];
         ba_residual<float>(cams + 9L * oToC[o], pts + 3L * oToP[o], ob.x, ob.y, r0, r1);
-        acc += 0.5f * (r0 * r0 + r1 * r1);
+        if (LOSS == 0) acc += 0.5f * (r0 * r0 + r1 * r1);
+        else { const float s = r0 * r0 + r1 * r1, rho = loss_rho<LOSS>(loss, s); acc += 0.5f * rho; }      // (s: today's expression, so an all-inlier Huber adds today's bits)
     }
     block_store_partial(acc, out, red);
 }
 
 // precomputeJ: J blocks + residuals in camera-sorted order q.  AD = the forward-mode duals (what rounds 1-3 stored; kept as the closed form's test reference)
-template <bool AD>
+// LOSS != 0 (closed form only): w = sqrt(rho'(s)) from the residual at hand; w x block, w x F and w[q] are stored
+template <bool AD, int LOSS = 0>
 __global__ __launch_bounds__(BLOCK) void k_compute_j(int O_, const float* __restrict__ cams, const float* __restrict__ pts,
                                                      const float2* __restrict__ obs, const int* __restrict__ cam_obs,
                                                      const int* __restrict__ q_cam, const int* __restrict__ q_pt,
-                                                     float4* __restrict__ Jb, float2* __restrict__ F)
+                                                     float4* __restrict__ Jb, float2* __restrict__ F, LossArgs<LOSS> loss, LossOut<LOSS> lw)
 {
+    static_assert(!AD || LOSS == 0, "the dual-number form is the closed form's test reference: no loss");
     for (int q = blockIdx.x * BLOCK + threadIdx.x; q < O_; q += gridDim.x * BLOCK) {
         const float2 ob = obs[cam_obs[q]];
         float4* b = Jb + 6L * q;
@@ -206,7 +232,14 @@ __global__ __launch_bounds__(BLOCK) void k_compute_j(int O_, const float* __rest
             float r0, r1;
             ba_residual<float>(cams + 9L * q_cam[q], X, ob.x, ob.y, r0, r1);
             const CamPre cp = ba_cam_pre(cams + 9L * q_cam[q]);
-            const Blk k = ba_block(cp, X[0], X[1], X[2]);
+            Blk k = ba_block(cp, X[0], X[1], X[2]);
+            if constexpr (LOSS != 0) {
+                const float s = r0 * r0 + r1 * r1, w = loss_w<LOSS>(loss, s);
+#pragma unroll
+                for (int i = 0; i < 24; ++i) k.a[i] = k.a[i] * w;
+                r0 = r0 * w; r1 = r1 * w;
+                lw.w[q] = w;
+            }
 #pragma unroll
             for (int i = 0; i < 6; ++i) b[i] = make_float4(k.a[4 * i], k.a[4 * i + 1], k.a[4 * i + 2], k.a[4 * i + 3]);
             F[q] = make_float2(r0, r1);
@@ -353,11 +386,17 @@ __global__ __launch_bounds__(BLOCK) void k_pack_point_blocks(int O_, const float
 // LM residual reset (gauss_newton.t:1653-1657) as the epilogue of the two launches: with p = delta and ctc set, r = b - (J^T J + CtC) delta and the partials of
 // betaN = r . M^-1 r instead of A p and p . A p (nothing else is read from a reset in the single-reduction loop: M^-1 r is formed where p is)
 struct ResetArgs { float* r; const float* b; const float* pre; };
+// RB: the robust instantiation -- w[q] (what precomputeJ stored) is loaded next to q_pt[q] and the 24 rebuilt entries are multiplied by it before anything uses them: the
+// operator applied is then, bit for bit, the stored matrix that PCGInit1, the block diagonal, JP / k_pt2 and the Schur kernels read.  (Not J p scaled instead: another
+// rounding, and two matrices.)  The plain instantiation's argument struct is empty.
+template <bool RB> struct CamW { const float* w; };
+template <> struct CamW<false> {};
 
+template <bool RB>
 __global__ __launch_bounds__(BLOCK) void k_cam2(int C_, const int* __restrict__ cam_ptr, const int* __restrict__ q_pt,
                                                 const float* __restrict__ cams, const float* __restrict__ pts, const float* __restrict__ p, float* __restrict__ Ap, float2* __restrict__ JpC,
                                                 float* __restrict__ part_out, const float* __restrict__ rs, const float* __restrict__ prs, double* __restrict__ s3_out,
-                                                const unsigned* __restrict__ gate, const float* __restrict__ ctc, const float* __restrict__ delta, LmFin lm, ResetArgs rst)
+                                                const unsigned* __restrict__ gate, const float* __restrict__ ctc, const float* __restrict__ delta, LmFin lm, ResetArgs rst, CamW<RB> cw)
 {   // lm.b: the launch of a one-reduction LM iteration (thallo_hip_ba_pcg_apply_lm) -- also {U, T1, T2} of q's expansion in alpha (device_common.hpp SumsQ) per workgroup
     __shared__ float red[16];
     __shared__ double redd[6 * BLOCK / 64];
@@ -383,14 +422,23 @@ __global__ __launch_bounds__(BLOCK) void k_cam2(int C_, const int* __restrict__ 
         constexpr int NO = BA_CAM_OBS;
         const int q1e = cam_ptr[c + 1];
         for (int q = cam_ptr[c] + lane; q < q1e; q += 64 * NO) {
-            long pi[NO]; float x[NO][3], pp[NO][3]; bool h[NO];
+            long pi[NO]; float x[NO][3], pp[NO][3]; bool h[NO]; float wq[NO];
 #pragma unroll
-            for (int u = 0; u < NO; ++u) { h[u] = q + 64 * u < q1e; pi[u] = q_pt[h[u] ? q + 64 * u : q]; }
+            for (int u = 0; u < NO; ++u) {
+                h[u] = q + 64 * u < q1e; pi[u] = q_pt[h[u] ? q + 64 * u : q];
+                if constexpr (RB) wq[u] = cw.w[h[u] ? q + 64 * u : q];
+            }
 #pragma unroll
             for (int u = 0; u < NO; ++u) { const float* X = pts + 3L * pi[u]; const float* P3 = p + PB + 3L * pi[u]; x[u][0] = X[0]; x[u][1] = X[1]; x[u][2] = X[2]; pp[u][0] = P3[0]; pp[u][1] = P3[1]; pp[u][2] = P3[2]; }
             Blk b[NO]; float j0[NO], j1[NO];
 #pragma unroll
             for (int u = 0; u < NO; ++u) b[u] = ba_block(cp, x[u][0], x[u][1], x[u][2]);
+            if constexpr (RB) {
+#pragma unroll
+                for (int u = 0; u < NO; ++u)
+#pragma unroll
+                    for (int i = 0; i < 24; ++i) b[u].a[i] = b[u].a[i] * wq[u];
+            }
 #pragma unroll
             for (int u = 0; u < NO; ++u) {
                 j0[u] = b[u].a[9] * pp[u][0] + b[u].a[10] * pp[u][1] + b[u].a[11] * pp[u][2]; j1[u] = b[u].a[21] * pp[u][0] + b[u].a[22] * pp[u][1] + b[u].a[23] * pp[u][2];
@@ -498,6 +546,10 @@ inline void gather_shape(int C_, int P_, int& cam_blocks, int& grid)
     grid = cam_blocks + pb;                        // <= 960 partials
 }
 
+// kind: THALLO_HIP_LOSS_HUBER / _CAUCHY, scale finite and positive -- anything else is an error, never the squared loss
+inline bool loss_ok(int kind, float scale) { return (kind == THALLO_HIP_LOSS_HUBER || kind == THALLO_HIP_LOSS_CAUCHY) && scale > 0.0f && scale <= 3.402823466e38f; }
+template <int LOSS> inline LossArgs<LOSS> loss_args(float a) { LossArgs<LOSS> l; l.a = a; l.a2 = a * a; l.ia2 = 1.0f / (a * a); return l; }
+
 }  // namespace
 
 extern "C" {
@@ -507,7 +559,19 @@ int thallo_hip_ba_cost(int C_, int P_, int O_, const float* cameras, const float
 {
     (void)C_; (void)P_;
     int grid = (O_ + BLOCK - 1) / BLOCK; if (grid > THALLO_MAX_PARTIALS) grid = THALLO_MAX_PARTIALS; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_cost, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations, oToC, oToP, cost_out);
+    hipLaunchKernelGGL(k_cost<0>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations, oToC, oToP, cost_out, LossArgs<0>{});
+    int e = check_launch(); return e ? e : grid;
+}
+int thallo_hip_ba_cost_robust(int C_, int P_, int O_, const float* cameras, const float* points, const float* observations,
+                              const int* oToC, const int* oToP, int kind, float scale, float* cost_out, thallo_stream_t stream)
+{
+    (void)C_; (void)P_;
+    if (!loss_ok(kind, scale)) return -(int)hipErrorInvalidValue;
+    int grid = (O_ + BLOCK - 1) / BLOCK; if (grid > THALLO_MAX_PARTIALS) grid = THALLO_MAX_PARTIALS; if (grid < 1) grid = 1;
+    if (kind == THALLO_HIP_LOSS_HUBER)
+        hipLaunchKernelGGL(k_cost<1>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations, oToC, oToP, cost_out, loss_args<1>(scale));
+    else
+        hipLaunchKernelGGL(k_cost<2>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations, oToC, oToP, cost_out, loss_args<2>(scale));
     int e = check_launch(); return e ? e : grid;
 }
 
@@ -515,8 +579,22 @@ int thallo_hip_ba_compute_j(int O_, const float* cameras, const float* points, c
                             const int* cam_obs, const int* q_cam, const int* q_pt, float* Jb, float* F, thallo_stream_t stream)
 {
     int grid = (O_ + BLOCK - 1) / BLOCK; if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_compute_j<false>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
-                       cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F);
+    hipLaunchKernelGGL((k_compute_j<false, 0>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
+                       cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F, LossArgs<0>{}, LossOut<0>{});
+    return check_launch();
+}
+/* ... with a loss: w x block and w x F, and w[q] (O floats, camera order) */
+int thallo_hip_ba_compute_j_robust(int O_, const float* cameras, const float* points, const float* observations,
+                                   const int* cam_obs, const int* q_cam, const int* q_pt, int kind, float scale, float* Jb, float* F, float* w, thallo_stream_t stream)
+{
+    if (!loss_ok(kind, scale) || !w) return -(int)hipErrorInvalidValue;
+    int grid = (O_ + BLOCK - 1) / BLOCK; if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
+    if (kind == THALLO_HIP_LOSS_HUBER)
+        hipLaunchKernelGGL((k_compute_j<false, 1>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
+                           cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F, loss_args<1>(scale), LossOut<1>{ w });
+    else
+        hipLaunchKernelGGL((k_compute_j<false, 2>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
+                           cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F, loss_args<2>(scale), LossOut<2>{ w });
     return check_launch();
 }
 /* the same blocks from forward-mode dual numbers over the residual's expression (rounds 1-3's J): the closed form's reference in the tests */
@@ -524,8 +602,8 @@ int thallo_hip_ba_compute_j_ad(int O_, const float* cameras, const float* points
                                const int* cam_obs, const int* q_cam, const int* q_pt, float* Jb, float* F, thallo_stream_t stream)
 {
     int grid = (O_ + BLOCK - 1) / BLOCK; if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_compute_j<true>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
-                       cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F);
+    hipLaunchKernelGGL((k_compute_j<true, 0>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, O_, cameras, points, (const float2*)observations,
+                       cam_obs, q_cam, q_pt, (float4*)Jb, (float2*)F, LossArgs<0>{}, LossOut<0>{});
     return check_launch();
 }
 
@@ -558,8 +636,8 @@ int thallo_hip_ba_pack_point_blocks(int O_, const float* Jb, const int* q_ptk, f
 static int ba_apply2(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
                      const float* cameras, const float* points, const float* JP, float* JpC, const float* p, float* Ap, float* aD_out,
                      const float* r, const float* pre, double* s3_out, const unsigned* gate, thallo_fin_t fin, const float* ctc, thallo_stream_t stream,
-                     const float* delta = nullptr, LmFin lm = LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs rst = ResetArgs{ nullptr, nullptr, nullptr })
-{
+                     const float* delta = nullptr, LmFin lm = LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs rst = ResetArgs{ nullptr, nullptr, nullptr }, const float* w = nullptr)
+{   // w: the weights precomputeJ stored (a plan with a loss): the camera launch is the robust instantiation; the point launch reads the scaled JP either way
     if (rst.r && (!rst.b || !rst.pre || !ctc || s3_out || lm.b || fin.tickets)) return -(int)hipErrorInvalidValue;
     if (!cam_ptr || !q_pt || !pt_pos || !pt_ptr || !cameras || !points || !JP || !JpC || !p || !Ap || !aD_out) return -(int)hipErrorInvalidValue;
     if (s3_out && (!r || !pre)) return -(int)hipErrorInvalidValue;
@@ -567,7 +645,8 @@ static int ba_apply2(int C_, int P_, const int* cam_ptr, const int* q_pt, const 
     if (lm.b && (!ctc || !delta || !lm.q3_out || !lm.state)) return -(int)hipErrorInvalidValue;      // (fin.tickets NULL: partials only -- the next thallo_hip_pcg_update_lm_fin finishes)
     int cb, grid; gather_shape(C_, P_, cb, grid);
     // the camera launch fills slots [0, cb); the point launch the rest, and (fin) its last workgroup adds up all `grid` of them
-    hipLaunchKernelGGL(k_cam2, dim3(cb), dim3(BLOCK), 0, (hipStream_t)stream, C_, cam_ptr, q_pt, cameras, points, p, Ap, (float2*)JpC, aD_out, r, pre, s3_out, gate, ctc, delta, lm, rst);
+    if (w) hipLaunchKernelGGL(k_cam2<true>, dim3(cb), dim3(BLOCK), 0, (hipStream_t)stream, C_, cam_ptr, q_pt, cameras, points, p, Ap, (float2*)JpC, aD_out, r, pre, s3_out, gate, ctc, delta, lm, rst, CamW<true>{ w });
+    else hipLaunchKernelGGL(k_cam2<false>, dim3(cb), dim3(BLOCK), 0, (hipStream_t)stream, C_, cam_ptr, q_pt, cameras, points, p, Ap, (float2*)JpC, aD_out, r, pre, s3_out, gate, ctc, delta, lm, rst, CamW<false>{});
     hipLaunchKernelGGL(k_pt2, dim3(grid - cb), dim3(BLOCK), 0, (hipStream_t)stream, C_, P_, pt_ptr, pt_pos, (const float2*)JP, (const float2*)JpC, p, Ap, aD_out, r, pre,
                        s3_out, gate, FinArgs{ fin.alphaN, fin.tickets, fin.alphaD_word, fin.betaN_word, cb, grid }, ctc, delta, lm, rst);
     int e = check_launch(); return e ? e : grid;
@@ -605,6 +684,42 @@ int thallo_hip_ba_lm_reset_residual(int C_, int P_, const int* cam_ptr, const in
     const thallo_fin_t none = { { nullptr, 0 }, nullptr, nullptr, nullptr };
     return ba_apply2(C_, P_, cam_ptr, q_pt, pt_pos, pt_ptr, cameras, points, JP, JpC, delta, r /* (not written in this mode) */, betaN_out, nullptr, nullptr, nullptr, gate, none, CtC, stream,
                      nullptr, LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs{ r, b, pre });
+}
+/* The same four launches of a plan with a robust loss: w = what thallo_hip_ba_compute_j_robust stored (NULL is an error, never the plain operator) */
+int thallo_hip_ba_apply_jtj2_fin_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                        const float* cameras, const float* points, const float* JP, float* JpC, const float* p, float* Ap, float* aD_out,
+                                        const float* r, const float* pre, double* s3_out, const unsigned* gate, thallo_fin_t fin, const float* w, thallo_stream_t stream)
+{
+    if (!w) return -(int)hipErrorInvalidValue;
+    return ba_apply2(C_, P_, cam_ptr, q_pt, pt_pos, pt_ptr, cameras, points, JP, JpC, p, Ap, aD_out, r, pre, s3_out, gate, fin, nullptr, stream,
+                     nullptr, LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs{ nullptr, nullptr, nullptr }, w);
+}
+int thallo_hip_ba_apply_jtj2_lm_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                       const float* cameras, const float* points, const float* JP, float* JpC, const float* p, const float* CtC, float* Ap, float* aD_out,
+                                       const unsigned* gate, const float* w, thallo_stream_t stream)
+{
+    if (!CtC || !w) return -(int)hipErrorInvalidValue;
+    const thallo_fin_t none = { { nullptr, 0 }, nullptr, nullptr, nullptr };
+    return ba_apply2(C_, P_, cam_ptr, q_pt, pt_pos, pt_ptr, cameras, points, JP, JpC, p, Ap, aD_out, nullptr, nullptr, nullptr, gate, none, CtC, stream,
+                     nullptr, LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs{ nullptr, nullptr, nullptr }, w);
+}
+int thallo_hip_ba_pcg_apply_lm_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                      const float* cameras, const float* points, const float* JP, float* JpC, const float* p, const float* CtC, float* Ap, float* aD_out,
+                                      const float* r, const float* pre, const float* delta, const float* b, double* s3_out, double* q3_out, thallo_fin_t fin,
+                                      float* lm_state, int k, float q_tolerance, int q_in, int q_out, const float* w, thallo_stream_t stream)
+{
+    if (!CtC || !b || !delta || !lm_state || !q3_out || !s3_out || q_in < 0 || q_in > 7 || q_out < 0 || q_out > 7 || !w) return -(int)hipErrorInvalidValue;
+    return ba_apply2(C_, P_, cam_ptr, q_pt, pt_pos, pt_ptr, cameras, points, JP, JpC, p, Ap, aD_out, r, pre, s3_out, reinterpret_cast<const unsigned*>(lm_state) + 1, fin, CtC, stream,
+                     delta, LmFin{ b, q3_out, lm_state, k, q_tolerance, q_in, q_out }, ResetArgs{ nullptr, nullptr, nullptr }, w);
+}
+int thallo_hip_ba_lm_reset_residual_robust(int C_, int P_, const int* cam_ptr, const int* q_pt, const int* pt_pos, const int* pt_ptr,
+                                           const float* cameras, const float* points, const float* JP, float* JpC, const float* delta, const float* CtC, const float* b, const float* pre,
+                                           float* r, float* betaN_out, const unsigned* gate, const float* w, thallo_stream_t stream)
+{
+    if (!delta || !CtC || !b || !pre || !r || !betaN_out || !w) return -(int)hipErrorInvalidValue;
+    const thallo_fin_t none = { { nullptr, 0 }, nullptr, nullptr, nullptr };
+    return ba_apply2(C_, P_, cam_ptr, q_pt, pt_pos, pt_ptr, cameras, points, JP, JpC, delta, r /* (not written in this mode) */, betaN_out, nullptr, nullptr, nullptr, gate, none, CtC, stream,
+                     nullptr, LmFin{ nullptr, nullptr, nullptr, 0, 0.0f }, ResetArgs{ r, b, pre }, w);
 }
 #ifdef THALLO_RESEARCH
 #include "probe/ba_resident_host.inc"

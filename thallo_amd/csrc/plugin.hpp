@@ -239,6 +239,13 @@ public:
     // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
     virtual bool hold_ok() const { return false; }
     virtual void hold_to_internal(int /*k*/, const unsigned char* /*caller*/, unsigned char* /*flat*/) const {}
+    // ---- robust losses (opt-in: ThalloX_PlanSetRobustLoss; DESIGN.md "Robust losses"): plugins whose cost, precomputeJ and block-rebuilding apply routes have a robust
+    // instantiation.  robust_prepare, at Init behind prepare(): the loss of this solve (kind 0: none -- the routes launch what they launch without the call) and the
+    // buffer of weights -> 0, or -1 with the reason set.  robust_weights: rho'(s) per observation of the last linearisation into host_out[n], the caller's ids -> the
+    // number of observations, or -1 (no loss in force, another n)
+    virtual bool robust_ok() const { return false; }
+    virtual int robust_prepare(int /*kind*/, float /*scale*/) { return 0; }
+    virtual long robust_weights(LaunchCtx&, float* /*host_out*/, long /*n*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale

@@ -795,8 +795,18 @@ class BundleAdjustmentPlugin : public EnergyPlugin {
         import_pending_ = false;
         return 0;
     }
+    // Robust loss of this solve (ThalloX_PlanSetRobustLoss, decided at Init: robust_prepare): 0 none, else THALLO_HIP_LOSS_*; its scale; w = sqrt(rho') per observation in
+    // camera order, written by precomputeJ, read by the camera launch of every apply.  With a loss the cost, precomputeJ and apply routes below launch the robust
+    // instantiations; without one exactly what they launched before the loss existed.
+    int loss_kind_ = 0; float loss_scale_ = 0.0f;
+    DeviceBuffer wq_;
+    const float* W() const { return (const float*)wq_.ptr; }
     int apply2(LaunchCtx& c, SolverVectors* v, const float* p, float* Ap, float* out, const thallo_fin_t& fin = thallo_fin_t{ { nullptr, 0 }, nullptr, nullptr, nullptr })
     {
+        if (loss_kind_)
+            return thallo_hip_ba_apply_jtj2_fin_robust(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr,
+                                                       cameras, Pts(), (const float*)JP.ptr, (float*)JpP.ptr, p, Ap, out,
+                                                       v ? v->r : nullptr, v ? v->pre : nullptr, v ? v->s12 : nullptr, c.gate, fin, W(), c.stream);
         return thallo_hip_ba_apply_jtj2_fin(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr,
                                             cameras, Pts(), (const float*)JP.ptr, (float*)JpP.ptr, p, Ap, out,
                                             v ? v->r : nullptr, v ? v->pre : nullptr, v ? v->s12 : nullptr, c.gate, fin, c.stream);
@@ -897,12 +907,19 @@ public:
     void unknowns_written() override { if (perm_) (void)thallo_hip_permute3(P, (const int*)d_new2old.ptr, (const float*)ptsP.ptr, points, 1, stream_); }
     const char* schedule_name() const override { return perm_ ? "materialized J blocks, closed form; points renumbered by first observing camera" : "materialized J blocks, closed form"; }
     int cost(LaunchCtx& c, float* out) override
-    { if (import_points(c.stream) < 0) return -1; TimedLaunch t(c, "computeCost"); return thallo_hip_ba_cost(C, P, O, cameras, Pts(), obs, oToC, OToP(), out, c.stream); }
+    {
+        if (import_points(c.stream) < 0) return -1;
+        TimedLaunch t(c, "computeCost");
+        if (loss_kind_) return thallo_hip_ba_cost_robust(C, P, O, cameras, Pts(), obs, oToC, OToP(), loss_kind_, loss_scale_, out, c.stream);
+        return thallo_hip_ba_cost(C, P, O, cameras, Pts(), obs, oToC, OToP(), out, c.stream);
+    }
     int pcg_init(LaunchCtx& c, SolverVectors& v, int cur, float* aN) override
     {
         if (import_points(c.stream) < 0) return -1;
         { TimedLaunch t(c, "precomputeJ");
-          int rc = thallo_hip_ba_compute_j(O, cameras, Pts(), obs, (const int*)cam_obs.ptr, (const int*)q_cam.ptr, (const int*)q_pt.ptr, (float*)Jb.ptr, (float*)F.ptr, c.stream);
+          int rc = loss_kind_ ? thallo_hip_ba_compute_j_robust(O, cameras, Pts(), obs, (const int*)cam_obs.ptr, (const int*)q_cam.ptr, (const int*)q_pt.ptr, loss_kind_, loss_scale_,
+                                                               (float*)Jb.ptr, (float*)F.ptr, (float*)wq_.ptr, c.stream)
+                              : thallo_hip_ba_compute_j(O, cameras, Pts(), obs, (const int*)cam_obs.ptr, (const int*)q_cam.ptr, (const int*)q_pt.ptr, (float*)Jb.ptr, (float*)F.ptr, c.stream);
           if (rc < 0) return rc;
           if ((rc = thallo_hip_ba_pack_point_blocks(O, (const float*)Jb.ptr, (const int*)q_ptk.ptr, (float*)JP.ptr, c.stream)) < 0) return rc; }
         TimedLaunch t(c, "PCGInit1");
@@ -912,6 +929,9 @@ public:
     int apply_jtj(LaunchCtx& c, const float* p, float* Ap, float* out) override
     {
         TimedLaunch t(c, "PCGStep1");
+        if (c.lm_ctc && loss_kind_)
+            return thallo_hip_ba_apply_jtj2_lm_robust(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr,
+                                                      cameras, Pts(), (const float*)JP.ptr, (float*)JpP.ptr, p, c.lm_ctc, Ap, out, c.gate, W(), c.stream);
         if (c.lm_ctc)
             return thallo_hip_ba_apply_jtj2_lm(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr,
                                                cameras, Pts(), (const float*)JP.ptr, (float*)JpP.ptr, p, c.lm_ctc, Ap, out, c.gate, c.stream);
@@ -1066,6 +1086,32 @@ public:
         if (k == 0) { memcpy(flat, caller, 9 * (size_t)C); return; }
         for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3);
     }
+    // robust losses: cost, precomputeJ and the camera launch of every apply have a robust instantiation; every other route reads the stored (scaled) Jb, F and JP
+    bool robust_ok() const override { return true; }
+    int robust_prepare(int kind, float scale) override
+    {
+        loss_kind_ = 0; loss_scale_ = 0.0f;
+        if (kind == 0) return 0;
+        if (!wq_.ptr) {      // (w = 1 until the first linearisation writes it)
+            const std::vector<float> ones((size_t)O, 1.0f);
+            if (wq_.alloc(sizeof(float) * (size_t)O + 64) || hipMemcpy(wq_.ptr, ones.data(), sizeof(float) * (size_t)O, hipMemcpyHostToDevice) != hipSuccess) {
+                wq_.release(); set_error("bundle_adjustment: out of device memory for the robust loss's weights (%zu bytes)", sizeof(float) * (size_t)O); return -1;
+            }
+        }
+        loss_kind_ = kind; loss_scale_ = scale;
+        resident_ = false;      // (the research build's resident GN loop restates the block inside its launch, without w)
+        return 0;
+    }
+    long robust_weights(LaunchCtx& c, float* host_out, long n) override
+    {   // w^2 = rho'(s), camera order q -> the caller's observation ids (cam_obs[q]; observations are never renumbered)
+        if (!loss_kind_ || n != (long)O || !host_out) return -1;
+        std::vector<float> w((size_t)O); std::vector<int> co((size_t)O);
+        if (hipMemcpyAsync(w.data(), wq_.ptr, sizeof(float) * (size_t)O, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            hipMemcpyAsync(co.data(), cam_obs.ptr, sizeof(int) * (size_t)O, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the robust loss's weights"); return -1; }
+        for (int q = 0; q < O; ++q) host_out[co[(size_t)q]] = w[(size_t)q] * w[(size_t)q];
+        return O;
+    }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }
     int shared_split_slots() const override { return thallo_hip_ba_apply2_camera_slots(C, P); }
@@ -1079,6 +1125,9 @@ public:
     int lm_reset_residual(LaunchCtx& c, SolverVectors& v, float* bN_out) override
     {
         TimedLaunch t(c, "PCGStep2");
+        if (loss_kind_)
+            return thallo_hip_ba_lm_reset_residual_robust(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr, cameras, Pts(),
+                                                          (const float*)JP.ptr, (float*)JpP.ptr, v.delta, v.CtC, v.b, v.pre, v.r, bN_out, c.gate, W(), c.stream);
         return thallo_hip_ba_lm_reset_residual(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr, cameras, Pts(),
                                                (const float*)JP.ptr, (float*)JpP.ptr, v.delta, v.CtC, v.b, v.pre, v.r, bN_out, c.gate, c.stream);
     }
@@ -1093,6 +1142,10 @@ public:
           else rc = thallo_hip_pcg_update_lm(v.r, v.Ap, v.pre, v.p[cur], v.p[cur ^ 1], v.delta, v.n, first ? 1 : c.lm_reset_bn_word ? 2 : 0, aN, aD, bN, c.lm_reset_bn_word, lm_state, c.stream);
           if (rc < 0) return rc; }
         TimedLaunch t(c, "PCGStep1");
+        if (loss_kind_)
+            return thallo_hip_ba_pcg_apply_lm_robust(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr, cameras, Pts(),
+                                                     (const float*)JP.ptr, (float*)JpP.ptr, v.p[cur ^ 1], v.CtC, v.Ap, out, v.r, v.pre, v.delta, v.b, v.s12, v.s12b, fin, lm_state, k, q_tol,
+                                                     c.lm_q_in, c.lm_q_out, W(), c.stream);
         return thallo_hip_ba_pcg_apply_lm(C, P, (const int*)cam_ptr.ptr, (const int*)q_pt.ptr, (const int*)pt_pos.ptr, (const int*)pt_ptr.ptr, cameras, Pts(),
                                           (const float*)JP.ptr, (float*)JpP.ptr, v.p[cur ^ 1], v.CtC, v.Ap, out, v.r, v.pre, v.delta, v.b, v.s12, v.s12b, fin, lm_state, k, q_tol,
                                           c.lm_q_in, c.lm_q_out, c.stream);

@@ -391,6 +391,10 @@ void Plan::init(void** params)
         }
     }
     if (held_prepare()) return;
+    robust_on_ = 0;
+    if (robust_want_ && (dist_ || plugin->direct_solve() || !plugin->robust_ok())) { set_error("%s: a robust loss needs a one-GPU PCG plan", plugin->name()); return; }
+    if (plugin->robust_prepare(robust_want_, robust_want_scale_)) return;      // (kind 0: the plugin's routes launch what they launch without the call)
+    robust_on_ = robust_want_; robust_on_scale_ = robust_want_scale_;
     block_on_ = false;
     schur_on_ = false;
     if (schur_want_) { if (schur_prepare()) return; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
@@ -541,7 +545,7 @@ int Plan::step_gn(int ev_iter)
     }
     if (schur_on_) return step_gn_schur(ev_iter);
     if (block_on_) return step_gn_block(ev_iter);
-    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan)
+    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on() && !robust_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan; and the block, without w: not for a robust one)
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
     const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
@@ -563,6 +567,26 @@ int Plan::step_gn(int ev_iter)
     const int ev_fin = gn_finish(L, ev_lin);
     linear_update_tail(L, batched);
     return gn_end(ev_fin, ev_iter);
+}
+
+// ------------------------------------------------------------------ robust losses (opt-in; energy_ba.hip, DESIGN.md "Robust losses")
+int Plan::set_robust_loss(int kind, float scale)
+{
+    if (kind != THALLOX_LOSS_TRIVIAL && kind != THALLOX_LOSS_HUBER && kind != THALLOX_LOSS_CAUCHY) { set_error("%s: unknown robust loss kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_LOSS_TRIVIAL) { robust_want_ = 0; robust_want_scale_ = 0.0f; return 0; }
+    if (!ok_) return -1;
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no linearisation to reweight (no robust loss)", plugin->name()); return -1; }
+    if (!plugin->robust_ok()) { set_error("%s: no robust loss for this energy (its cost, precomputeJ and apply routes have no robust instantiation; bundle_adjustment's do)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: robust losses run on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (!(scale > 0.0f) || !std::isfinite(scale)) { set_error("%s: the scale of a robust loss must be finite and positive (got %g)", plugin->name(), (double)scale); return -1; }
+    robust_want_ = kind; robust_want_scale_ = scale;
+    return 0;
+}
+
+long Plan::robust_weights(float* host_out, long n)
+{
+    if (!ok_ || !robust_on()) return -1;
+    return plugin->robust_weights(ctx, host_out, n);
 }
 
 // ------------------------------------------------------------------ held unknowns (opt-in; held.hip, DESIGN.md "Held unknowns")
@@ -658,6 +682,12 @@ int Plan::preconditioner_fallbacks()
 const char* Plan::schedule_name()
 {
     const char* base = schedule_base();
+    const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
+    if (kind) {
+        char sc[32]; snprintf(sc, sizeof sc, "%g", (double)(ready_ ? robust_on_scale_ : robust_want_scale_));
+        robust_text_ = std::string(base) + (kind == THALLOX_LOSS_HUBER ? "; huber loss, scale " : "; cauchy loss, scale ") + sc;
+        base = robust_text_.c_str();
+    }
     if (!held_on()) return base;
     held_text_ = std::string(base) + "; " + std::to_string(held_count_) + " unknowns held";
     return held_text_.c_str();

@@ -159,6 +159,9 @@ public:
     // at the next Init.  0 = ok
     int  set_held_unknowns(int input, const unsigned char* held, long n);
     long held_unknowns() const { return ready_ ? held_count_ : -1; }      // held scalars since the last Init (-1: no mask in force)
+    // ThalloX_PlanSetRobustLoss: kind THALLOX_LOSS_*, scale in residual units; takes effect at the next Init.  0 = ok
+    int  set_robust_loss(int kind, float scale);
+    long robust_weights(float* host_out, long n);      // rho'(s) per observation of the last linearisation, the caller's ids -> O, or -1 (no loss in force, n != O)
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
     int  set_ghost_exchange(int n_boundary, const int* boundary_units, int n_ghost, const int* ghost_units, const int* ghost_src_rank, const int* ghost_src_pos);
@@ -304,7 +307,12 @@ private:
     bool  schur_empty() const { return schur_on_ && held_on() && held_first_ == schur_n_; }
     int   held_prepare();
     int   hold_pcg(float* rz_out);                      // pre = z = 0 at the held scalars, the partials of r . z anew -> their number
-    const char* schedule_base();                        // schedule_name() without the held count
+    const char* schedule_base();                        // schedule_name() without the loss and the held count
+    // ---- robust loss (opt-in; energy_ba.hip): want = what ThalloX_PlanSetRobustLoss asked for, on = what this solve runs (handed to the plugin at Init, behind prepare())
+    int   robust_want_ = 0, robust_on_ = 0;
+    float robust_want_scale_ = 0.0f, robust_on_scale_ = 0.0f;
+    std::string robust_text_;
+    bool  robust_on() const { return ready_ && robust_on_ != 0; }
     // ---- block-Jacobi preconditioner (opt-in; block_precond.hip).  want: what ThalloX_PlanSetPreconditioner asked for; on: what this solve runs (decided at Init, where
     // H, G and the status word are allocated -- never inside a step)
     bool block_want_ = false, block_on_ = false;
