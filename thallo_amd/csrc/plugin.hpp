@@ -215,7 +215,8 @@ public:
         return thallo_hip_pcg_step2(v.r, v.Ap, use_preconditioner() ? v.pre : nullptr, v.z, v.n, aN, aD, betaN_out, c.stream);
     }
     // ---- block-Jacobi preconditioner (opt-in: ThalloX_PlanSetPreconditioner; block_precond.hip): plugins whose unknowns come in dense blocks of J^T J say which
-    // (regions of the flat vector) and fill H -- thallo_hip_block_floats(block_regions()) floats, the blocks' lower triangles -- from what pcg_init has just left
+    // (regions of the flat vector) and fill H -- thallo_hip_block_floats(block_regions()) floats, the blocks' lower triangles -- from what pcg_init has just left.
+    // Such a plugin also has apply_adds_ctc(): the block forms' LM loop (Plan::lm_loop_blocks) takes (J^T J + CtC) p from one apply_jtj launch; Init refuses one without
     virtual bool block_precond_ok() const { return false; }
     virtual thallo_block_regions_t block_regions() const { thallo_block_regions_t r; r.n = 0; return r; }
     virtual int block_diag(LaunchCtx&, float* /*H*/) { return -1; }

@@ -17,8 +17,6 @@ void set_error(const char* fmt, ...)
 }
 const char* last_error() { return g_err; }
 
-#define HIP_OK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) set_error("%s failed: %s", #call, hipGetErrorString(e__)); } while (0)
-
 // ------------------------------------------------------------------ KernelTimer
 hipEvent_t KernelTimer::get_event()
 {
@@ -189,11 +187,8 @@ Plan::Plan(EnergyPlugin* pl, const Thallo_InitializationParameters& ip_, bool lm
     v_.n = plugin->n_unknowns();
     v_.n_alloc = thallo_hip_vector_elems(v_.n);
     float** vecs[] = { &v_.delta, &v_.r, &v_.z, &v_.Ap, &v_.pre, &v_.p[0], &v_.p[1] };
-    for (float** vp : vecs) {     // zero-filled like UnknownType:initGPU (thallo.t:1104-1126)
-        DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b);
-        if (b->alloc((size_t)v_.n_alloc * sizeof(float))) return;
-        *vp = (float*)b->ptr;
-    }
+    for (float** vp : vecs)       // zero-filled like UnknownType:initGPU (thallo.t:1104-1126)
+        if (!(*vp = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return;
     if (scratch_.alloc(64 * sizeof(float))) return;
     ctx.timer = &ktimer;
     timer_.enabled = ip.timingLevel >= 1;
@@ -214,6 +209,10 @@ Plan::~Plan()
     for (auto b : bufs_) delete b;
     delete plugin;
 }
+
+// Every device buffer that lives as long as the plan is registered in bufs_ (a step that allocated is one whose bufs_.size() moved: bufs_at_step_)
+DeviceBuffer* Plan::register_buffer() { bufs_.push_back(new DeviceBuffer()); return bufs_.back(); }
+void* Plan::device_alloc(size_t bytes) { DeviceBuffer* b = register_buffer(); return b->alloc(bytes) ? nullptr : b->ptr; }
 
 int Plan::ensure_slots(int L)
 {
@@ -347,20 +346,23 @@ float Plan::compute_cost()
     HIP_OK(hipMemcpyAsync(hw ? hw : &f, scratch_.ptr, sizeof(float), hipMemcpyDeviceToHost, ctx.stream));
     HIP_OK(hipStreamSynchronize(ctx.stream));
     if (hw) f = hw[0];
-    if (resident_used_) {     // the resident PCG kernel's waits are bounded; one that ran out voids the steps since the last check
-        resident_used_ = false;
-        unsigned pm[5] = { 0, 0, 0, 0, 0 };
-        if (plugin->resident_status(ctx, 1, pm) != 0) {
-            // (something kept the kernel's workgroups from being co-resident -- a long-running foreign kernel, a second resident plan on another stream: the launch
-            //  itself checks what the device can hold.)  This plan runs one launch per PCG iteration from now on; the voided steps are reported, not silently redone:
-            //  the unknowns already carry their update.
-            plugin->resident_disable();
-            set_error("%s: a bounded wait inside the resident PCG kernel ran out (wait kind %u, workgroup %u, wave %u, index %u, tag %u): the steps since the last cost evaluation are void; "
-                      "the plan runs one launch per PCG iteration from now on (Thallo_ProblemInit and solve again)", plugin->name(), pm[0], pm[1], pm[2], pm[3], pm[4]);
-            return NAN;
-        }
-    }
+    if (resident_wait_ran_out("the steps since the last cost evaluation are void")) return NAN;
     return f;
+}
+
+// The resident PCG kernel's waits are bounded; one that ran out voids what ran since the last check (`void_what`).  Something kept the kernel's workgroups from being
+// co-resident -- a long-running foreign kernel, a second resident plan on another stream: the launch itself checks what the device can hold.  This plan runs one launch
+// per PCG iteration from now on; what is void is reported, not silently redone: the unknowns already carry their update.
+bool Plan::resident_wait_ran_out(const char* void_what)
+{
+    if (!resident_used_) return false;
+    resident_used_ = false;
+    unsigned pm[5] = { 0, 0, 0, 0, 0 };
+    if (plugin->resident_status(ctx, 1, pm) == 0) return false;
+    plugin->resident_disable();
+    set_error("%s: a bounded wait inside the resident PCG kernel ran out (wait kind %u, workgroup %u, wave %u, index %u, tag %u): %s; "
+              "the plan runs one launch per PCG iteration from now on (Thallo_ProblemInit and solve again)", plugin->name(), pm[0], pm[1], pm[2], pm[3], pm[4], void_what);
+    return true;
 }
 
 void Plan::init(void** params)
@@ -390,16 +392,7 @@ void Plan::init(void** params)
             return;
         }
     }
-    if (held_prepare()) return;
-    robust_on_ = 0;
-    if (robust_want_ && (dist_ || plugin->direct_solve() || !plugin->robust_ok())) { set_error("%s: a robust loss needs a one-GPU PCG plan", plugin->name()); return; }
-    if (plugin->robust_prepare(robust_want_, robust_want_scale_)) return;      // (kind 0: the plugin's routes launch what they launch without the call)
-    robust_on_ = robust_want_; robust_on_scale_ = robust_want_scale_;
-    block_on_ = false;
-    schur_on_ = false;
-    if (schur_want_) { if (schur_prepare()) return; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
-    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes)
-    if (!schur_want_ && block_want_) { if (block_prepare()) return; block_on_ = true; }
+    if (forms_prepare()) return;               // the opt-in forms (solver_forms.cpp): what this solve runs, and their buffers
     ready_ = true;
     if (dist_ && dist_->want_p2p && !dist_->checked && dist_self_check()) { ready_ = false; return; }
     if (dist_ && dist_->checked && dist_->p2p_on && dist_->form == DistForm::Slab) {      // (also right behind a self-check that has just passed: ADVICE r5)
@@ -496,7 +489,8 @@ Plan::Owned Plan::owned_range(size_t u) const
 }
 
 // The head and the tail that every PCG-loop form of a GN step shares (the direct solve records other coarse events and keeps its own lines).
-// gn_begin: "Nonlinear Setup" around PCGInit1 (alphaN_0's partials into slot B = 2), "Linear Solve" started; false: the launch failed, the step ends.
+// gn_begin: "Nonlinear Setup" around PCGInit1 (alphaN_0's partials into slot B = 2) and what the opt-in forms put behind it (forms_setup: the mask of held unknowns,
+// the blocks; p_0 = M^-1 r_0 is formed behind them), "Linear Solve" started; false: a launch failed, the step ends.
 // delta_unset: PCGInit1 stores no zeros into delta -- the caller has proved that this step's first reader of delta is a launch that takes "delta is zero" instead.
 bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
 {
@@ -508,7 +502,8 @@ bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
     if (delta_unset) v_init.delta = nullptr;
     int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
-    if (held_on() && (nb = hold_pcg(slot(2))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return false; }      // (p_0 = M^-1 r_0 is formed behind it, from pre)
+    const char* what = nullptr;
+    if (forms_behind_init() && (nb = forms_setup(nullptr, v_.r, slot(2), nb, what)) < 0) { set_error("%s failed (%d)", what, nb); return false; }
     set_nb(2, nb); finish(2);
     ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
     return true;
@@ -543,8 +538,7 @@ int Plan::step_gn(int ev_iter)
         timer_.stop(ev_iter, s);
         return 1;
     }
-    if (schur_on_) return step_gn_schur(ev_iter);
-    if (block_on_) return step_gn_block(ev_iter);
+    if (schur_on_ || block_on_) return step_gn_blocks(ev_iter);      // (solver_forms.cpp: the block forms live in the unfused loop only)
     if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on() && !robust_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan; and the block, without w: not for a robust one)
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
     if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
@@ -569,325 +563,6 @@ int Plan::step_gn(int ev_iter)
     return gn_end(ev_fin, ev_iter);
 }
 
-// ------------------------------------------------------------------ robust losses (opt-in; energy_ba.hip, DESIGN.md "Robust losses")
-int Plan::set_robust_loss(int kind, float scale)
-{
-    if (kind != THALLOX_LOSS_TRIVIAL && kind != THALLOX_LOSS_HUBER && kind != THALLOX_LOSS_CAUCHY) { set_error("%s: unknown robust loss kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_LOSS_TRIVIAL) { robust_want_ = 0; robust_want_scale_ = 0.0f; return 0; }
-    if (!ok_) return -1;
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no linearisation to reweight (no robust loss)", plugin->name()); return -1; }
-    if (!plugin->robust_ok()) { set_error("%s: no robust loss for this energy (its cost, precomputeJ and apply routes have no robust instantiation; bundle_adjustment's do)", plugin->name()); return -1; }
-    if (dist_) { set_error("%s: robust losses run on one GPU (this plan is distributed)", plugin->name()); return -1; }
-    if (!(scale > 0.0f) || !std::isfinite(scale)) { set_error("%s: the scale of a robust loss must be finite and positive (got %g)", plugin->name(), (double)scale); return -1; }
-    robust_want_ = kind; robust_want_scale_ = scale;
-    return 0;
-}
-
-long Plan::robust_weights(float* host_out, long n)
-{
-    if (!ok_ || !robust_on()) return -1;
-    return plugin->robust_weights(ctx, host_out, n);
-}
-
-// ------------------------------------------------------------------ held unknowns (opt-in; held.hip, DESIGN.md "Held unknowns")
-int Plan::set_held_unknowns(int input, const unsigned char* held, long n)
-{
-    if (!ok_) return -1;
-    const auto& imgs = plugin->unknown_images();
-    int k = -1;
-    for (size_t i = 0; i < imgs.size(); ++i) if (imgs[i].param_index == input) k = (int)i;
-    if (!held) { if (k >= 0) held_masks_.erase(k); return 0; }
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to hold unknowns in", plugin->name()); return -1; }
-    if (!plugin->hold_ok()) { set_error("%s: no held unknowns for this energy (not every PCG route of its plugin takes M^-1 from the stored vector; bundle_adjustment's do)", plugin->name()); return -1; }
-    if (dist_) { set_error("%s: held unknowns run on one GPU (this plan is distributed)", plugin->name()); return -1; }
-    if (k < 0) { set_error("%s: input %d is not an Unknown of this energy", plugin->name(), input); return -1; }
-    if (n != imgs[(size_t)k].n_floats) { set_error("%s: the mask of input %d has %ld bytes, the unknown has %ld scalars (elements x components)", plugin->name(), input, n, imgs[(size_t)k].n_floats); return -1; }
-    held_masks_[k].assign(held, held + n);
-    return 0;
-}
-
-int Plan::held_prepare()
-{   // Init, behind prepare() (the plugin's numbering is decided): the masks in the plan's internal ids, counted, uploaded -- never inside a step
-    held_count_ = -1; held_first_ = 0;
-    if (held_masks_.empty()) return 0;
-    if (dist_ || plugin->direct_solve() || !plugin->hold_ok()) { set_error("%s: held unknowns need a one-GPU PCG plan", plugin->name()); return -1; }
-    std::vector<unsigned char> flat((size_t)v_.n, 0);
-    for (const auto& m : held_masks_) plugin->hold_to_internal(m.first, m.second.data(), flat.data());
-    long count = 0;
-    for (unsigned char f : flat) count += f != 0;
-    if (count == v_.n) { set_error("%s: the mask holds every unknown (%ld scalars): nothing is left to solve for", plugin->name(), count); return -1; }
-    { const long n0 = plugin->unknown_images()[0].n_floats; for (long i = 0; i < n0; ++i) held_first_ += flat[(size_t)i] != 0; }
-    held_count_ = count;
-    if (count == 0) return 0;      // (nothing held: the plan launches what it launches without a mask)
-    if (!held_mask_) {
-        DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b);
-        if (b->alloc((size_t)v_.n_alloc + 64)) { held_count_ = -1; set_error("%s: out of device memory for the mask of held unknowns", plugin->name()); return -1; }
-        held_mask_ = (unsigned char*)b->ptr;
-    }
-    if (hipMemcpy(held_mask_, flat.data(), flat.size(), hipMemcpyHostToDevice) != hipSuccess) { held_count_ = -1; set_error("%s: cannot upload the mask of held unknowns", plugin->name()); return -1; }
-    return 0;
-}
-
-int Plan::hold_pcg(float* rz_out)
-{
-    TimedLaunch t(ctx, "HoldPCG");
-    return thallo_hip_hold_pcg(held_mask_, v_.r, v_.pre, v_.z, v_.n, rz_out, ctx.stream);
-}
-
-// ------------------------------------------------------------------ block-Jacobi preconditioner (opt-in; block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
-int Plan::set_preconditioner(int kind)
-{
-    if (kind != THALLOX_PRECOND_JACOBI && kind != THALLOX_PRECOND_BLOCK_JACOBI) { set_error("%s: unknown preconditioner kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_PRECOND_JACOBI) { block_want_ = false; return 0; }
-    if (!ok_) return -1;
-    if (!plugin->block_precond_ok()) { set_error("%s: no block-Jacobi preconditioner for this energy (its plugin states no blocks; bundle_adjustment does)", plugin->name()); return -1; }
-    if (dist_) { set_error("%s: the block-Jacobi preconditioner runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to precondition", plugin->name()); return -1; }
-    block_want_ = true;
-    return 0;
-}
-
-int Plan::block_prepare()
-{
-    if (dist_ || plugin->direct_solve() || !plugin->block_precond_ok()) { set_error("%s: the block-Jacobi preconditioner needs a one-GPU PCG plan", plugin->name()); return -1; }
-    block_regions_ = plugin->block_regions();
-    const long nf = thallo_hip_block_floats(block_regions_);
-    if (nf < 0) { set_error("%s: invalid block regions", plugin->name()); return -1; }
-    if (block_H_) return 0;
-    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
-    block_H_ = (float*)get(((size_t)nf + 64) * sizeof(float)); block_G_ = (float*)get(((size_t)nf + 64) * sizeof(float)); block_status_ = (unsigned*)get(64);
-    if (!block_H_ || !block_G_ || !block_status_) { block_H_ = block_G_ = nullptr; block_status_ = nullptr; set_error("%s: out of device memory for the block preconditioner", plugin->name()); return -1; }
-    return 0;
-}
-
-int Plan::block_setup(const float* shift, const unsigned* gate, float* rz_out)
-{
-    int rc = plugin->block_diag(ctx, block_H_);
-    if (rc < 0) return rc;
-    if (held_on()) { TimedLaunch t(ctx, "BlockHold"); if ((rc = thallo_hip_block_hold(block_regions_, held_mask_, block_H_, ctx.stream)) < 0) return rc; }
-    { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(block_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
-    if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(block_regions_, held_mask_, block_G_, ctx.stream)) < 0) return rc; }
-    TimedLaunch t(ctx, "BlockApply");
-    return thallo_hip_block_apply(block_regions_, block_G_, v_.r, v_.z, rz_out, gate, ctx.stream);
-}
-
-int Plan::preconditioner_fallbacks()
-{
-    if (!(block_on_ || schur_on_) || !block_status_) return -1;
-    unsigned n = 0;
-    if (hipMemcpyAsync(&n, block_status_, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
-    return (int)n;
-}
-
-const char* Plan::schedule_name()
-{
-    const char* base = schedule_base();
-    const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
-    if (kind) {
-        char sc[32]; snprintf(sc, sizeof sc, "%g", (double)(ready_ ? robust_on_scale_ : robust_want_scale_));
-        robust_text_ = std::string(base) + (kind == THALLOX_LOSS_HUBER ? "; huber loss, scale " : "; cauchy loss, scale ") + sc;
-        base = robust_text_.c_str();
-    }
-    if (!held_on()) return base;
-    held_text_ = std::string(base) + "; " + std::to_string(held_count_) + " unknowns held";
-    return held_text_.c_str();
-}
-
-const char* Plan::schedule_base()
-{
-    if ((schur_on_ || schur_want_) && (schur_on_ ? schur_explicit_ : schur_explicit_want_)) {
-        schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras, assembled";
-        if (schur_on_ && schur_blocks_ >= 0) schedule_text_ += " (" + std::to_string(schur_blocks_) + " blocks)";
-        schedule_text_ += "; block-Jacobi on S";
-        return schedule_text_.c_str();
-    }
-    if (schur_on_ || schur_want_) {
-        schedule_text_ = std::string(plugin->schedule_name()) + "; Schur complement on the cameras; block-Jacobi on S";
-        return schedule_text_.c_str();
-    }
-    if (!block_on_ && !block_want_) return plugin->schedule_name();
-    schedule_text_ = std::string(plugin->schedule_name()) + "; block-Jacobi preconditioner (unfused PCG loop)";
-    return schedule_text_.c_str();
-}
-
-int Plan::step_gn_block(int ev_iter)
-{   // the generic GN loop (step_gn's last branch) with M^-1 = G^T G: behind PCGInit1 the blocks, their factors and z = M^-1 r with alphaN_0's partials (they replace
-    // PCGInit1's point-Jacobi z and sum); PCGStep2 is thallo_hip_block_step2.  PCGInit1 leaves p_prev = 0 and the first PCGStep1 forms p = z, as in every schedule.
-    const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    hipStream_t s = ctx.stream;
-    const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    if (held_on() && (nb = hold_pcg(slot(B))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return 0; }      // (pre: the blocks' fallback)
-    nb = block_setup(nullptr, nullptr, slot(B));
-    if (nb < 0) { set_error("block preconditioner set-up failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    const int ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
-    for (int k = 0; k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        const PrevAlpha a = prev_alpha(k);
-        nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
-        if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
-        set_nb(jD, nb); finish(jD); cur_ ^= 1;
-        {   TimedLaunch t(ctx, "BlockStep2");
-            nb = thallo_hip_block_step2(block_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
-        if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
-        set_nb(jB, nb); finish(jB);
-    }
-    const int ev_fin = gn_finish(L, ev_lin);
-    linear_update_tail(L, false);
-    return gn_end(ev_fin, ev_iter);
-}
-
-// ------------------------------------------------------------------ Schur complement on the cameras (opt-in; ba_schur.hip, DESIGN.md "Schur complement on the cameras")
-int Plan::set_linear_solver(int kind)
-{
-    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG && kind != THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; schur_explicit_want_ = false; return 0; }
-    if (!ok_) return -1;
-    const bool ex = kind == THALLOX_SOLVER_SCHUR_EXPLICIT_PCG;
-    const char* what = ex ? "assembled Schur-complement solve" : "Schur-complement solve";
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a"); return -1; }
-    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
-    if (dist_) { set_error("%s: the %s runs on one GPU (this plan is distributed)", plugin->name(), what); return -1; }
-    schur_want_ = true; schur_explicit_want_ = ex;
-    return 0;
-}
-
-int Plan::schur_prepare()
-{
-    if (dist_ || plugin->direct_solve() || !plugin->schur_ok()) { set_error("%s: the Schur-complement solve needs a one-GPU PCG plan", plugin->name()); return -1; }
-    if (block_prepare()) return -1;                      // H, G, the status word (G's camera region: the preconditioner of S)
-    if (block_regions_.n != 2 || block_regions_.r[0].offset != 0) { set_error("%s: the Schur-complement solve needs two block regions, the kept one first", plugin->name()); return -1; }
-    schur_regions_ = block_regions_; schur_regions_.n = 1;
-    schur_n_ = (long)block_regions_.r[0].size * block_regions_.r[0].count;
-    schur_hp_off_ = thallo_hip_block_floats(schur_regions_);
-    schur_pt_off_ = block_regions_.r[1].offset;
-    // the assembled form: the structure of S, sized and checked against its budget before it is allocated; here, never inside a step
-    schur_explicit_ = false;
-    schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
-    if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
-    schur_explicit_ = schur_explicit_want_;
-    if (schur_Ge_) return 0;
-    const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
-    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
-    schur_Ge_ = (float*)get((ns * (ns + 1) / 2 * np + 64) * sizeof(float)); schur_y_ = (float*)get((ns * np + 64) * sizeof(float));
-    schur_g_ = (float*)get(((size_t)v_.n_alloc + 64) * sizeof(float)); schur_held_ = (unsigned*)get(64);
-    if (!schur_Ge_ || !schur_y_ || !schur_g_ || !schur_held_) {
-        schur_Ge_ = schur_y_ = schur_g_ = nullptr; schur_held_ = nullptr;
-        set_error("%s: out of device memory for the Schur-complement solve", plugin->name()); return -1;
-    }
-    return 0;
-}
-
-int Plan::schur_setup(const float* shift, const float* b, float* rz_out)
-{   // behind PCGInit1 (+ PCGFinalizeDiagonal in LM): r = b = -J^T F over all unknowns, pre = the point-Jacobi M^-1 (the camera blocks' fallback)
-    int rc = plugin->block_diag(ctx, block_H_);
-    if (rc < 0) return rc;
-    // held unknowns: H of both regions in one launch (the camera blocks and the point blocks lie one behind the other), G of the camera region here, the elimination
-    // factor inside schur_reduce; g, W, the assembly, both applies and the back-substitution inherit the rule through the two factors
-    if (held_on()) { TimedLaunch t(ctx, "BlockHold"); if ((rc = thallo_hip_block_hold(block_regions_, held_mask_, block_H_, ctx.stream)) < 0) return rc; }
-    { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(schur_regions_, block_H_, shift, v_.pre, block_G_, block_status_, ctx.stream)) < 0) return rc; }
-    if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(schur_regions_, held_mask_, block_G_, ctx.stream)) < 0) return rc; }
-    if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
-    if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;      // (every step: B, the factor and in LM CtC are the step's)
-    TimedLaunch t(ctx, "BlockApply");
-    return thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, ctx.stream);
-}
-
-int Plan::schur_held_points()
-{
-    if (!schur_on_ || !schur_held_) return -1;
-    unsigned n = 0;
-    if (hipMemcpyAsync(&n, schur_held_, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
-    return (int)n;
-}
-
-int Plan::step_gn_schur(int ev_iter)
-{   // step_gn_block's loop on the reduced system (S, g): every vector of the loop is its camera part ([0, 9 C) of the plan's vectors); the point part of r stays b_p, which
-    // the back-substitution reads.  The loop's last delta_c += alpha p rides in the back-substitution's camera launch; PCGLinearUpdate then adds the complete delta.
-    const int L = schur_empty() ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
-    hipStream_t s = ctx.stream;
-    const int ev_setup = bufs_.size() == bufs_at_step_ ? timer_.start_with(ev_iter, "Nonlinear Setup", s) : timer_.start("Nonlinear Setup", s);
-    cur_ = 0;
-    int nb = plugin->pcg_init(ctx, v_, cur_, slot(B));
-    if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return 0; }
-    if (held_on() && (nb = hold_pcg(slot(B))) < 0) { set_error("held unknowns: the mask launch failed (%d)", nb); return 0; }      // (pre: the camera blocks' fallback)
-    nb = schur_setup(nullptr, v_.r, slot(B));
-    if (nb < 0) { set_error("Schur-complement set-up failed (%d)", nb); return 0; }
-    set_nb(B, nb); finish(B);
-    const int ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
-    for (int k = 0; k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        const PrevAlpha a = prev_alpha(k);
-        {   TimedLaunch t(ctx, "PCGStep3");
-            nb = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, schur_n_, k == 0 ? 1 : 0, a.aN, a.aD, sum(jN), s); }
-        if (nb < 0) { set_error("PCGStep3 launch failed (%d)", nb); return 0; }
-        nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], nullptr, v_.Ap, slot(jD), nullptr);
-        if (nb < 0) { set_error("Schur apply launch failed (%d)", nb); return 0; }
-        set_nb(jD, nb); finish(jD); cur_ ^= 1;
-        {   TimedLaunch t(ctx, "BlockStep2");
-            nb = thallo_hip_block_step2(schur_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
-        if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
-        set_nb(jB, nb); finish(jB);
-    }
-    const int jL = B + 2 * (L - 1);
-    nb = plugin->schur_back(ctx, schur_Ge_, v_.r, v_.delta, L > 0 ? v_.p[cur_] : nullptr, sum(L > 0 ? jL : B), sum(L > 0 ? jL + 1 : B));
-    if (nb < 0) { set_error("Schur back-substitution launch failed (%d)", nb); return 0; }
-    const int ev_fin = gn_finish(L, ev_lin);
-    linear_update_tail(0, false);
-    return gn_end(ev_fin, ev_iter);
-}
-
-// The reference-shaped LM loop (lm_loop_reference on one GPU) on the reduced system: b := g, Q_k = 0.5 delta_c . (r_c + g) -- the full model's value minus the constant
-// 0.5 b_p . Cp^-1 b_p, which the zeta test (Ceres' criterion on the reduced model) does not use.  Every launch of the loop takes the gate word; the back-substitution behind
-// it does not.
-void Plan::lm_loop_schur(LmStep& st)
-{
-    hipStream_t s = st.s;
-    const int L = schur_empty() ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
-    const long n = schur_n_;
-    float* p = v_.p[0];
-    int nb = 0;
-    for (int k = 0; k < L; ++k) {
-        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
-        {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
-            st.check(thallo_hip_pcg_pupdate(v_.z, p, p, nullptr, n, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch"); }
-        if (st.failed) return;
-        nb = plugin->schur_apply(ctx, schur_Ge_, p, v_.CtC, v_.Ap, slot(jD), ctx.gate);      // (S + CtC_c) p ; alphaD
-        st.check(nb, "Schur apply launch");
-        if (st.failed) return;
-        set_nb(jD, nb);
-        int nbq = 0;
-        if (((k + 1) % sp.residual_reset_period) == 0) {      // :1653-1657 on the reduced system: r_c = g - (S + CtC_c) delta_c, one more apply
-            { TimedLaunch t(ctx, "PCGStep2"); st.check(thallo_hip_lm_step2_first_half(v_.delta, p, n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
-            if (st.failed) return;
-            nb = plugin->schur_apply(ctx, schur_Ge_, v_.delta, v_.CtC, v_.Adelta, slot(T0), ctx.gate);
-            st.check(nb, "Schur apply (reset) launch");
-            if (st.failed) return;
-            // (as in the block form: the second half's point-Jacobi z and betaN partials go to waste -- the partials into the scratch slot T1 --, the block apply forms both anew)
-            { TimedLaunch t(ctx, "PCGStep2"); nb = thallo_hip_lm_step2_second_half(v_.r, schur_g_, v_.Adelta, v_.pre, v_.z, v_.delta, n, slot(T1), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
-            if (st.failed) return;
-            nbq = nb;
-            { TimedLaunch t(ctx, "BlockApply"); nb = thallo_hip_block_apply(schur_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
-        } else {
-            TimedLaunch t(ctx, "BlockStep2LM");
-            nb = thallo_hip_block_step2_lm(schur_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, schur_g_, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);
-            st.check(nb, "PCGStep2 launch");
-            nbq = nb;
-        }
-        if (st.failed) return;
-        set_nb(jB, nb); set_nb(QS, nbq);
-        st.k_done = k + 1;
-        {   TimedLaunch t(ctx, "PCGZeta");
-            st.check(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, st.lmst, s), "PCGZeta launch"); }
-        if (st.failed) return;
-    }
-    const thallo_sum_t none = { nullptr, 0 };
-    st.check(plugin->schur_back(ctx, schur_Ge_, v_.b, v_.delta, nullptr, none, none), "Schur back-substitution launch");
-}
-
 // ------------------------------------------------------------------ Levenberg-Marquardt branch
 void Plan::enable_lm(bool on) { lm_ = on; }
 void Plan::unknowns_changed()
@@ -901,11 +576,8 @@ int Plan::ensure_lm_vectors()
 {
     if (v_.b) return 0;
     float** vecs[] = { &v_.b, &v_.Adelta, &v_.CtC, &v_.SSq, &v_.prevX, &v_.diag };
-    for (float** vp : vecs) {
-        DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b);
-        if (b->alloc((size_t)v_.n_alloc * sizeof(float))) return -1;
-        *vp = (float*)b->ptr;
-    }
+    for (float** vp : vecs)
+        if (!(*vp = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return -1;
     return 0;
 }
 
@@ -1128,8 +800,8 @@ void Plan::ring_prepare(int L)
         if (hipMalloc(&ptr, bytes) != hipSuccess) { (void)hipGetLastError(); break; }      // fewer planes, not a failed step: the sticky error goes, no error text is left
         // zeroed once, in stream order on the plan's own stream: a launch writes every unknown of its plane but not the padding behind them, which the flat update reads
         if (hipMemsetAsync(ptr, 0, bytes, ctx.stream) != hipSuccess) { (void)hipGetLastError(); hipFree(ptr); break; }
-        DeviceBuffer* b = new DeviceBuffer(); b->ptr = ptr; b->bytes = bytes;
-        bufs_.push_back(b); ring_.push_back((float*)ptr);
+        DeviceBuffer* b = register_buffer(); b->ptr = ptr; b->bytes = bytes;
+        ring_.push_back((float*)ptr);
     }
 }
 int Plan::ring_planes(int L)
@@ -1203,19 +875,17 @@ int Plan::step_gn_expanded(int ev_iter)
 
 int Plan::ensure_sums_buffer()
 {   // per-workgroup double sums + the arrival tickets of the in-kernel finish
-    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
-    if (!v_.s12 && !(v_.s12 = (double*)get((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)))) return -1;
-    if (!v_.s12b && !(v_.s12b = (double*)get((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)))) return -1;
-    if (!v_.fin_tickets && !(v_.fin_tickets = (unsigned*)get(THALLO_HIP_FIN_TICKET_WORDS * sizeof(unsigned)))) return -1;
+    if (!v_.s12 && !(v_.s12 = (double*)device_alloc((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)))) return -1;
+    if (!v_.s12b && !(v_.s12b = (double*)device_alloc((size_t)3 * THALLO_HIP_MAX_PARTIALS * sizeof(double)))) return -1;
+    if (!v_.fin_tickets && !(v_.fin_tickets = (unsigned*)device_alloc(THALLO_HIP_FIN_TICKET_WORDS * sizeof(unsigned)))) return -1;
     return 0;
 }
 
 int Plan::ensure_iter_buffers()
 {
     if (ensure_sums_buffer()) return -1;
-    auto get = [&](size_t bytes) -> void* { DeviceBuffer* b = new DeviceBuffer(); bufs_.push_back(b); return b->alloc(bytes) ? nullptr : b->ptr; };
-    if (!v_.r2 && !(v_.r2 = (float*)get((size_t)v_.n_alloc * sizeof(float)))) return -1;            // (a row slab's r' / Ap' live in its exchange block)
-    if (!v_.Ap2 && !(v_.Ap2 = (float*)get((size_t)v_.n_alloc * sizeof(float)))) return -1;
+    if (!v_.r2 && !(v_.r2 = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return -1;            // (a row slab's r' / Ap' live in its exchange block)
+    if (!v_.Ap2 && !(v_.Ap2 = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return -1;
     return 0;
 }
 
@@ -1228,7 +898,7 @@ float Plan::read_sum(int j)
     return f;
 }
 
-// ---- One LM step (gauss_newton.t:1545-1785 with every UsesLambda() branch taken): lm_setup, ONE of four PCG loops (lm_schedule), lm_finish.
+// ---- One LM step (gauss_newton.t:1545-1785 with every UsesLambda() branch taken): lm_setup, ONE of five PCG loops (lm_schedule), lm_finish.
 //
 // The zeta test (:1666-1686) runs ON THE DEVICE: all lIterations iterations are enqueued, a one-wave kernel behind each PCGStep2
 // (or PCGStep2's own last workgroup) applies the test and sets the gate word, after which the remaining launches of the loop return at
@@ -1271,7 +941,7 @@ int Plan::step_lm(int ev_iter)
         case LmSchedule::OneKernel:     lm_loop_one_kernel(st); break;
         case LmSchedule::OneKernelSlab: lm_loop_one_kernel_slab(st); break;
         case LmSchedule::Reference:     lm_loop_reference(st); break;
-        case LmSchedule::Schur:         lm_loop_schur(st); break;
+        case LmSchedule::Blocks:        lm_loop_blocks(st); break;
         }
     }
     if (st.failed || st.coll_failed) return 0;
@@ -1304,17 +974,10 @@ bool Plan::lm_setup(LmStep& st)
             st.check(nb, "PCGFinalizeDiagonal launch");
         }
     }
-    if (held_on() && !st.skip()) {      // pre = z = 0 at the held scalars, alphaN_0 over the free ones; behind it every launch forms M^-1 r from pre (or from the blocks below)
-        nb = hold_pcg(slot(B));
-        st.check(nb, "held unknowns: the mask launch");
-    }
-    if (schur_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; r_c becomes g, z_c and alphaN_0 the reduced system's.  Every step: CtC follows the trust-region radius
-        nb = schur_setup(v_.CtC, v_.b, slot(B));
-        st.check(nb, "Schur-complement set-up");
-    }
-    if (block_on_ && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; z and alphaN_0 become the block form's.  Every step: CtC follows the trust-region radius
-        nb = block_setup(v_.CtC, nullptr, slot(B));
-        st.check(nb, "block preconditioner set-up");
+    if (forms_behind_init() && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; z and alphaN_0 (Schur: r_c = g too) become the form's.  Every step: CtC follows the trust-region radius
+        const char* what = nullptr;
+        nb = forms_setup(v_.CtC, v_.b, slot(B), nb, what);
+        st.check(nb, what);
     }
     if (st.failed) return false;
     if (!st.skip()) set_nb(B, nb);
@@ -1332,8 +995,7 @@ bool Plan::lm_setup(LmStep& st)
 Plan::LmSchedule Plan::lm_schedule(const LmStep& st)
 {
     const int L = st.L, period = st.period;
-    if (schur_on_) return LmSchedule::Schur;
-    if (block_on_) return LmSchedule::Reference;      // (the block form lives in the unfused loop only)
+    if (schur_on_ || block_on_) return LmSchedule::Blocks;      // (the block forms live in the unfused loop only)
     // round 6: the loop, the zeta test, the owed update of delta, the model cost and the update of the unknowns in ONE resident launch (plugins whose state fits the chip's
     // registers: shape_from_shading at the size of the reference's data set).  THALLO_RESIDENT=0: one launch per iteration (A/B).
     if (!st.slab && st.fold_init && lm_fold_step_ && lm_fold_p_ && st.fold_ctc && one_kernel_ && plugin->resident_lm_ok() && L >= 1 && L <= period) return LmSchedule::Resident;
@@ -1515,20 +1177,16 @@ void Plan::lm_loop_reference(LmStep& st)
                 ctx.lm_ctc = nullptr;
                 st.check(nb, "computeAdelta launch");
                 if (!st.skip() && !fold_ctc) st.check(thallo_hip_lm_step1_finish(v_.Adelta + o, v_.CtC + o, v_.delta + o, n, slot(T1), s), "computeAdelta (CtC) launch");
-                // (block form: the second half's point-Jacobi z and betaN partials go to waste -- the partials into the scratch slot T1 --, thallo_hip_block_apply behind it
-                //  forms both anew: two launches on every residual_reset_period-th iteration rather than one more fused kernel)
-                if (!st.skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(block_on_ ? T1 : jB), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
+                if (!st.skip()) { nb = thallo_hip_lm_step2_second_half(v_.r + o, v_.b + o, v_.Adelta + o, v_.pre + o, v_.z + o, v_.delta + o, n, slot(jB), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
                 nbq = nb;
-                if (block_on_ && !st.skip()) { nb = thallo_hip_block_apply(block_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
             }
         } else if (!st.skip()) {
-            TimedLaunch t(ctx, block_on_ ? "BlockStep2LM" : "PCGStep2");
-            if (block_on_) nb = thallo_hip_block_step2_lm(block_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, v_.b, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);      // (the zeta test: the PCGZeta launch below)
-            else if (zeta_in_step2) nb = thallo_hip_pcg_step2_full_zeta(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS),
+            TimedLaunch t(ctx, "PCGStep2");
+            if (zeta_in_step2) nb = thallo_hip_pcg_step2_full_zeta(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS),
                                                                     v_.fin_tickets, k, sp.q_tolerance, lmst, s);
             else nb = thallo_hip_pcg_step2_full(v_.delta + o, p + o, v_.r + o, v_.Ap + o, v_.pre + o, v_.z + o, v_.b + o, n, sum(jN), sum(jD), slot(jB), slot(QS), 1, s);
             st.check(nb, "PCGStep2 launch");
-            nbq = nb; zeta_done = zeta_in_step2 && !block_on_;
+            nbq = nb; zeta_done = zeta_in_step2;
         }
         if (st.failed) return;
         if (!st.skip()) { set_nb(jB, nb); set_nb(QS, nbq); }
@@ -1635,16 +1293,7 @@ int Plan::lm_finish(LmStep& st)
         if (hw) memcpy(rep, hw, sizeof(rep));
     }
     if (late_agree && (failed_before_cost_exchange || !std::isfinite(rep[5])) && !lm_agree_all()) return 0;      // (a failed rank skipped its own cost launches: its rep[5] says nothing)
-    if (resident_used_) {     // (the LM step's resident launch: its waits are bounded; one that ran out voids THIS step -- nothing of its report can be trusted)
-        resident_used_ = false;
-        unsigned pm[5] = { 0, 0, 0, 0, 0 };
-        if (plugin->resident_status(ctx, 1, pm) != 0) {
-            plugin->resident_disable();
-            set_error("%s: a bounded wait inside the resident PCG kernel ran out (wait kind %u, workgroup %u, wave %u, index %u, tag %u): this step is void; "
-                      "the plan runs one launch per PCG iteration from now on (Thallo_ProblemInit and solve again)", plugin->name(), pm[0], pm[1], pm[2], pm[3], pm[4]);
-            return 0;
-        }
-    }
+    if (resident_wait_ran_out("this step is void")) return 0;      // (the LM step's resident launch: nothing of its report can be trusted)
     return lm_accept_or_revert(rep[3], rep[4], rep[5], lm_iterations_done(rep, st.k_done), ev_fin, st.ev_iter);
 }
 

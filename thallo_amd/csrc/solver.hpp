@@ -9,6 +9,8 @@
 
 namespace thallo {
 
+#define HIP_OK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) set_error("%s failed: %s", #call, hipGetErrorString(e__)); } while (0)
+
 struct SolverParameters {   // gauss_newton.t:200-216, defaults :41-55
     float min_relative_decrease = 1e-3f;
     float min_trust_region_radius = 1e-32f;
@@ -150,7 +152,7 @@ public:
     // ThalloX_PlanSetPreconditioner: THALLOX_PRECOND_JACOBI (the reference's, default) or THALLOX_PRECOND_BLOCK_JACOBI; takes effect at the next Init.  0 = ok
     int  set_preconditioner(int kind);
     int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
-    const char* schedule_name();          // the plugin's, and the block preconditioner / the Schur form when it runs
+    const char* schedule_name();          // the plugin's, and the opt-in forms that run (before the first Init: that were asked for)
     // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG or THALLOX_SOLVER_SCHUR_EXPLICIT_PCG; takes effect at the next Init.  0 = ok
     int  set_linear_solver(int kind);
     int  schur_blocks() const { return schur_on_ && schur_explicit_ ? (int)schur_blocks_ : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
@@ -190,6 +192,8 @@ private:
     float prev_cost_ = 0.0f;
     SolverVectors v_;
     std::vector<DeviceBuffer*> bufs_;
+    DeviceBuffer* register_buffer();     // a new, empty entry of bufs_ (released with the plan)
+    void* device_alloc(size_t bytes);    // ... allocated and zero-filled -> its pointer, or nullptr
     DeviceBuffer parts_;            // reduction partial slots: (2*L+4) x THALLO_HIP_MAX_PARTIALS floats
     int parts_slots_ = 0;
     DeviceBuffer scratch_;          // a few scalar words (cost, trace)
@@ -287,19 +291,30 @@ private:
     bool gn_loop_deferred(GnStep& st, int k_end);       // iterations [0, k_end)
     bool gn_loop_finish_in_launch(GnStep& st);
     int  step_gn_resident(int ev_iter);
-    bool gn_begin(int ev_iter, int& ev_lin, bool delta_unset = false);      // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2 (delta_unset: it stores no zeros into delta), "Linear Solve" started
+    bool gn_begin(int ev_iter, int& ev_lin, bool delta_unset = false);      // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2 (delta_unset: it stores no zeros into delta), forms_setup, "Linear Solve" started
     int  gn_finish(int L, int ev_lin);                  // ... its tail: "Nonlinear Finish" started (the caller's update of the unknowns follows) ...
     int  gn_end(int ev_fin, int ev_iter);               // ... and the step counted, its events ended
     bool resident_used_ = false;    // a resident launch ran since the last cost evaluation (its error word is read there)
+    bool resident_wait_ran_out(const char* void_what);      // ... read: true = a bounded wait of the resident kernel ran out, the error says that `void_what`
     float compute_cost();
     float* host_words();
     int   step_gn(int ev_iter);
-    // ---- held unknowns (opt-in; held.hip): the caller's masks by unknown image; since the last Init their count and the mask over the flat vector in the plan's internal
-    // ids on the device (built and uploaded at Init, never inside a step).  The launches run only when something is held
+    // solver_forms.cpp: the opt-in forms of a one-GPU PCG plan.  Each is asked for by its setter, decided at Init (forms_prepare, where everything it needs is allocated --
+    // never inside a step) and runs until the next Init: want = what was asked for, on = what this solve runs
+    int   forms_prepare();                              // Init, behind prepare(): held_prepare, the robust loss, schur_prepare or block_prepare, precond_regions_; nonzero: not ready
+    bool  refuse_unless_one_gpu_pcg(bool ok, const char* what_needs);      // "<what_needs> a one-GPU PCG plan" unless ok (the plugin's *_ok()) on a one-GPU PCG plan
+    bool  forms_behind_init() const { return held_on() || schur_on_ || block_on_; }
+    // behind PCGInit1 (GN: gn_begin; LM: lm_setup), if forms_behind_init(): the mask, the blocks, both factors, the Schur reduction, z = M^-1 r -> the partial count of
+    // r . z in rz_out (nb: PCGInit1's, where nothing replaces them) or a negative code, `what` failed.  shift: the LM CtC or NULL; b: the right-hand side
+    int   forms_setup(const float* shift, const float* b, float* rz_out, int nb, const char*& what);
+    int   step_gn_blocks(int ev_iter);                  // the GN step of the block-Jacobi and the Schur form: the generic loop with thallo_hip_block_step2 as PCGStep2; Schur: on (S, g), then the back-substitution
+    int   read_word(const unsigned* dev);               // a status word of the last step, read back (-1: the copy failed)
+    std::string schedule_text_;                         // schedule_name()'s text
+    // ---- held unknowns (held.hip): the caller's masks by unknown image; since the last Init their count and the mask over the flat vector in the plan's internal ids on
+    // the device.  The launches run only when something is held
     std::map<int, std::vector<unsigned char>> held_masks_;
     long held_count_ = -1;
     unsigned char* held_mask_ = nullptr;
-    std::string held_text_;
     long held_first_ = 0;                               // ... of them in the first unknown image (the Schur form's kept region)
     bool  held_on() const { return held_count_ > 0; }
     // every unknown of the reduced system is held (structure-only bundle adjustment on a Schur plan): the reduced system is empty, its PCG loop takes no iteration (p_0 = 0
@@ -307,36 +322,28 @@ private:
     bool  schur_empty() const { return schur_on_ && held_on() && held_first_ == schur_n_; }
     int   held_prepare();
     int   hold_pcg(float* rz_out);                      // pre = z = 0 at the held scalars, the partials of r . z anew -> their number
-    const char* schedule_base();                        // schedule_name() without the loss and the held count
-    // ---- robust loss (opt-in; energy_ba.hip): want = what ThalloX_PlanSetRobustLoss asked for, on = what this solve runs (handed to the plugin at Init, behind prepare())
+    // ---- robust loss (energy_ba.hip): handed to the plugin at Init
     int   robust_want_ = 0, robust_on_ = 0;
     float robust_want_scale_ = 0.0f, robust_on_scale_ = 0.0f;
-    std::string robust_text_;
     bool  robust_on() const { return ready_ && robust_on_ != 0; }
-    // ---- block-Jacobi preconditioner (opt-in; block_precond.hip).  want: what ThalloX_PlanSetPreconditioner asked for; on: what this solve runs (decided at Init, where
-    // H, G and the status word are allocated -- never inside a step)
+    // ---- block-Jacobi preconditioner (block_precond.hip): H, G (the blocks and their factors) and the status word
     bool block_want_ = false, block_on_ = false;
-    thallo_block_regions_t block_regions_;
+    thallo_block_regions_t block_regions_;              // the plugin's regions
+    thallo_block_regions_t precond_regions_;            // ... those the preconditioner runs on (set once per Init): all of them; on a Schur plan the first, the cameras
     float *block_H_ = nullptr, *block_G_ = nullptr;
     unsigned* block_status_ = nullptr;
-    std::string schedule_text_;
     int   block_prepare();                              // Init: the regions and the buffers
-    int   block_setup(const float* shift, const unsigned* gate, float* rz_out);      // block_diag, block_factor (shift: the LM CtC or NULL), block_apply: z and the partials of r . z -> their number
-    int   step_gn_block(int ev_iter);                   // the generic GN loop with thallo_hip_block_step2 as PCGStep2
-    // ---- Schur complement on the cameras (opt-in; ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
-    // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are allocated at Init too
+    // ---- Schur complement on the cameras (ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
+    // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are its own
     bool schur_want_ = false, schur_on_ = false;
     bool schur_explicit_want_ = false, schur_explicit_ = false;      // kind 2 (asked for / running since the last Init): S assembled once per step by the plugin (ba_schur_explicit.hip), the loop's applies multiply by it
     long schur_blocks_ = -1;                            // ... its stored blocks, known at Init
-    thallo_block_regions_t schur_regions_;              // the camera region alone
     long schur_n_ = 0, schur_hp_off_ = 0, schur_pt_off_ = 0;      // camera unknowns; the point blocks' place in H; the points' place in the flat vector
     float *schur_Ge_ = nullptr, *schur_y_ = nullptr, *schur_g_ = nullptr;
     unsigned* schur_held_ = nullptr;
     int   schur_prepare();                              // Init: the buffers
-    int   schur_setup(const float* shift, const float* b, float* rz_out);      // blocks, both factors, g (r_c = g), z_c = M_c^-1 r_c and the partials of r_c . z_c -> their number
-    int   step_gn_schur(int ev_iter);                   // step_gn_block's loop on (S, g), then the back-substitution
-    // ---- Levenberg-Marquardt: step_lm = lm_setup, one of four PCG loops (lm_schedule), lm_finish
-    enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident, Schur };
+    // ---- Levenberg-Marquardt: step_lm = lm_setup, one of five PCG loops (lm_schedule), lm_finish
+    enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident, Blocks };
     // Between the LM state reset and the end of the PCG loop the plugin's launches are gated on the state's gate word (the zeta test on the device); whichever way
     // the loop is left, the gate is off again before the next launch that has to run
     struct GateOff {
@@ -372,7 +379,7 @@ private:
     bool  lm_setup(LmStep& st);
     LmSchedule lm_schedule(const LmStep& st);
     void  lm_loop_reference(LmStep& st);
-    void  lm_loop_schur(LmStep& st);                    // the reference-shaped loop on the reduced system (S + CtC_c, g), then the back-substitution
+    void  lm_loop_blocks(LmStep& st);                   // solver_forms.cpp: the reference-shaped loop of the block-Jacobi and the Schur form; Schur: on (S + CtC_c, g), then the back-substitution
     void  lm_loop_one_kernel(LmStep& st);
     void  lm_loop_one_kernel_slab(LmStep& st);
     void  lm_loop_resident(LmStep& st);

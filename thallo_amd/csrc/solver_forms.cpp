@@ -1,0 +1,324 @@
+// solver_forms.cpp -- the opt-in forms of a one-GPU PCG plan (solver.hpp "solver_forms.cpp"): robust losses, held unknowns, the block-Jacobi preconditioner and the
+// Schur complement on the cameras.  What they ask for is set between Plan and Init (the setters), decided and allocated at Init (forms_prepare: never inside a step) and
+// run by ONE set-up behind PCGInit1 (forms_setup), ONE GN step (step_gn_blocks) and ONE LM loop (lm_loop_blocks) for the block-Jacobi and the Schur form alike.
+#include "solver.hpp"
+#include <cmath>
+#include <cstdio>
+
+namespace thallo {
+
+// Init: every opt-in form needs a one-GPU PCG plan (`ok`: the plugin's *_ok() answer; `what_needs`: "a robust loss needs").  true: refused, the error is set
+bool Plan::refuse_unless_one_gpu_pcg(bool ok, const char* what_needs)
+{
+    if (!dist_ && !plugin->direct_solve() && ok) return false;
+    set_error("%s: %s a one-GPU PCG plan", plugin->name(), what_needs);
+    return true;
+}
+
+// The blocking read-back of one status word of the last step (-1: the copy failed)
+int Plan::read_word(const unsigned* dev)
+{
+    unsigned n = 0;
+    if (hipMemcpyAsync(&n, dev, sizeof(n), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
+    return (int)n;
+}
+
+// Init, behind prepare() (the plugin's numbering is decided): what this solve runs, in this order; every buffer of a form is allocated here.  Nonzero: the plan is not ready
+int Plan::forms_prepare()
+{
+    if (held_prepare()) return -1;
+    robust_on_ = 0;
+    if (robust_want_ && refuse_unless_one_gpu_pcg(plugin->robust_ok(), "a robust loss needs")) return -1;
+    if (plugin->robust_prepare(robust_want_, robust_want_scale_)) return -1;      // (kind 0: the plugin's routes launch what they launch without the call)
+    robust_on_ = robust_want_; robust_on_scale_ = robust_want_scale_;
+    block_on_ = false;
+    schur_on_ = false;
+    if (schur_want_) { if (schur_prepare()) return -1; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
+    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes)
+    if (!schur_want_ && block_want_) { if (block_prepare()) return -1; block_on_ = true; }
+    if (schur_on_ || block_on_) { precond_regions_ = block_regions_; if (schur_on_) precond_regions_.n = 1; }      // (Schur: the camera region alone)
+    return 0;
+}
+
+// Behind PCGInit1 (+ PCGFinalizeDiagonal in LM; r = b = -J^T F over all unknowns, pre = the point-Jacobi M^-1, the blocks' fallback), what the forms put in front of the
+// loop.  shift: the LM CtC or NULL; b: the right-hand side (GN: r); rz_out: the slot of alphaN_0; nb: PCGInit1's partial count.  -> the slot's partial count (nb where no form
+// writes it anew), or a negative code with `what` naming what failed.
+//   held unknowns: pre = z = 0 at the held scalars, alphaN_0 over the free ones; behind it every launch forms M^-1 r from pre or from the blocks
+//   block forms:   H of both regions (held: its rows and columns in one launch -- the camera blocks and the point blocks lie one behind the other), G of the preconditioner's
+//                  regions, z = G^T G r and alphaN_0 anew.  Schur: in between the elimination factor, y and g (r_c becomes g; the point part of r stays b_p) and, assembled,
+//                  W and S -- every step: B, the factor and in LM CtC are the step's.  g, W, the assembly, both applies and the back-substitution inherit the held rule
+//                  through the two factors
+int Plan::forms_setup(const float* shift, const float* b, float* rz_out, int nb, const char*& what)
+{
+    hipStream_t s = ctx.stream;
+    what = "held unknowns: the mask launch";
+    if (held_on() && (nb = hold_pcg(rz_out)) < 0) return nb;
+    if (!schur_on_ && !block_on_) return nb;
+    what = schur_on_ ? "Schur-complement set-up" : "block preconditioner set-up";
+    int rc = plugin->block_diag(ctx, block_H_);
+    if (rc < 0) return rc;
+    if (held_on()) { TimedLaunch t(ctx, "BlockHold"); if ((rc = thallo_hip_block_hold(block_regions_, held_mask_, block_H_, s)) < 0) return rc; }
+    { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(precond_regions_, block_H_, shift, v_.pre, block_G_, block_status_, s)) < 0) return rc; }
+    if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(precond_regions_, held_mask_, block_G_, s)) < 0) return rc; }
+    if (schur_on_) {
+        if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
+        if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;
+    }
+    TimedLaunch t(ctx, "BlockApply");
+    return thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, s);
+}
+
+// One GN step of the block-Jacobi and of the Schur form: the generic GN loop (step_gn's last branch) with M^-1 = G^T G -- forms_setup behind PCGInit1 replaces its
+// point-Jacobi z and sum, PCGStep2 is thallo_hip_block_step2; PCGInit1 leaves p_prev = 0 and the first iteration forms p = z, as in every schedule.
+// Schur: the loop runs on the reduced system (S, g) -- PCGStep3 and the plugin's apply instead of its PCGStep1 --, every vector of it is its camera part ([0, 9 C) of the
+// plan's vectors), the point part of r stays b_p, which the back-substitution reads.  The loop's last delta_c += alpha p rides in the back-substitution's camera launch;
+// PCGLinearUpdate then adds the complete delta.
+int Plan::step_gn_blocks(int ev_iter)
+{
+    const int L = schur_empty() ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    hipStream_t s = ctx.stream;
+    int ev_lin, nb;
+    if (!gn_begin(ev_iter, ev_lin)) return 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        const PrevAlpha a = prev_alpha(k);
+        if (schur_on_) {
+            {   TimedLaunch t(ctx, "PCGStep3");
+                nb = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, schur_n_, k == 0 ? 1 : 0, a.aN, a.aD, sum(jN), s); }
+            if (nb < 0) { set_error("PCGStep3 launch failed (%d)", nb); return 0; }
+            nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], nullptr, v_.Ap, slot(jD), nullptr);
+            if (nb < 0) { set_error("Schur apply launch failed (%d)", nb); return 0; }
+        } else {
+            nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
+            if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
+        }
+        set_nb(jD, nb); finish(jD); cur_ ^= 1;
+        {   TimedLaunch t(ctx, "BlockStep2");
+            nb = thallo_hip_block_step2(precond_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
+        if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
+        set_nb(jB, nb); finish(jB);
+    }
+    if (schur_on_) {
+        const int jL = B + 2 * (L - 1);
+        nb = plugin->schur_back(ctx, schur_Ge_, v_.r, v_.delta, L > 0 ? v_.p[cur_] : nullptr, sum(L > 0 ? jL : B), sum(L > 0 ? jL + 1 : B));
+        if (nb < 0) { set_error("Schur back-substitution launch failed (%d)", nb); return 0; }
+    }
+    const int ev_fin = gn_finish(L, ev_lin);
+    linear_update_tail(schur_on_ ? 0 : L, false);
+    return gn_end(ev_fin, ev_iter);
+}
+
+// The LM loop of the block-Jacobi and of the Schur form, on one GPU: the reference-shaped loop (PCGStep3 / the apply with CtC folded in / PCGStep2 / zeta, the residual
+// reset every residual_reset_period iterations) with thallo_hip_block_step2_lm as PCGStep2; every launch takes the gate word.  Block-Jacobi: on the full system, through
+// the plugin's applyJTJ (EnergyPlugin::block_precond_ok: it adds CtC p).  Schur: on the reduced system (S + CtC_c, g): b := g, Q_k = 0.5 delta_c . (r_c + g) -- the full
+// model's value minus the constant 0.5 b_p . Cp^-1 b_p, which the zeta test (Ceres' criterion on the reduced model) does not use --, then the back-substitution, which
+// does not take the gate word.
+void Plan::lm_loop_blocks(LmStep& st)
+{
+    hipStream_t s = st.s;
+    const bool schur = schur_on_;
+    const int L = schur_empty() ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const long n = schur ? schur_n_ : v_.n;
+    const float* b = schur ? schur_g_ : v_.b;
+    float* p = v_.p[0];
+    auto apply = [&](const float* x, float* Ax, float* xAx_out) {      // (S + CtC_c) x or (J^T J + CtC) x ; the partials of x . that
+        if (schur) return plugin->schur_apply(ctx, schur_Ge_, x, v_.CtC, Ax, xAx_out, ctx.gate);
+        ctx.lm_ctc = v_.CtC;
+        const int rc = plugin->apply_jtj(ctx, x, Ax, xAx_out);
+        ctx.lm_ctc = nullptr;
+        return rc;
+    };
+    int nb = 0;
+    for (int k = 0; k < L; ++k) {
+        const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
+        {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
+            st.check(thallo_hip_pcg_pupdate(v_.z, p, p, nullptr, n, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch"); }
+        if (st.failed) return;
+        nb = apply(p, v_.Ap, slot(jD));                       // alphaD
+        st.check(nb, schur ? "Schur apply launch" : "PCGStep1 launch");
+        if (st.failed) return;
+        set_nb(jD, nb);
+        int nbq = 0;
+        if (((k + 1) % sp.residual_reset_period) == 0) {      // :1653-1657: r = b - A delta, one more apply
+            { TimedLaunch t(ctx, "PCGStep2"); st.check(thallo_hip_lm_step2_first_half(v_.delta, p, n, sum(jN), sum(jD), s), "PCGStep2 (first half) launch"); }
+            if (st.failed) return;
+            nb = apply(v_.delta, v_.Adelta, slot(T0));
+            st.check(nb, schur ? "Schur apply (reset) launch" : "computeAdelta launch");
+            if (st.failed) return;
+            // (the second half's point-Jacobi z and betaN partials go to waste -- the partials into the scratch slot T1 --, the block apply behind it forms both anew: two
+            //  launches on every residual_reset_period-th iteration rather than one more fused kernel)
+            { TimedLaunch t(ctx, "PCGStep2"); nb = thallo_hip_lm_step2_second_half(v_.r, b, v_.Adelta, v_.pre, v_.z, v_.delta, n, slot(T1), slot(QS), s); st.check(nb, "PCGStep2 (second half) launch"); }
+            if (st.failed) return;
+            nbq = nb;
+            { TimedLaunch t(ctx, "BlockApply"); nb = thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
+        } else {
+            TimedLaunch t(ctx, "BlockStep2LM");
+            nb = thallo_hip_block_step2_lm(precond_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, b, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);
+            st.check(nb, "PCGStep2 launch");
+            nbq = nb;
+        }
+        if (st.failed) return;
+        set_nb(jB, nb); set_nb(QS, nbq);
+        st.k_done = k + 1;
+        {   TimedLaunch t(ctx, "PCGZeta");
+            st.check(thallo_hip_lm_zeta(sum(QS), k, sp.q_tolerance, st.lmst, s), "PCGZeta launch"); }
+        if (st.failed) return;
+    }
+    if (!schur) return;
+    const thallo_sum_t none = { nullptr, 0 };
+    st.check(plugin->schur_back(ctx, schur_Ge_, v_.b, v_.delta, nullptr, none, none), "Schur back-substitution launch");
+}
+
+const char* Plan::schedule_name()
+{
+    std::string& t = schedule_text_;
+    t = plugin->schedule_name();
+    if (schur_on_ || schur_want_) {
+        if (schur_on_ ? schur_explicit_ : schur_explicit_want_) {
+            t += "; Schur complement on the cameras, assembled";
+            if (schur_on_ && schur_blocks_ >= 0) t += " (" + std::to_string(schur_blocks_) + " blocks)";
+        } else t += "; Schur complement on the cameras";
+        t += "; block-Jacobi on S";
+    } else if (block_on_ || block_want_) t += "; block-Jacobi preconditioner (unfused PCG loop)";
+    const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
+    if (kind) {
+        char sc[32]; snprintf(sc, sizeof sc, "%g", (double)(ready_ ? robust_on_scale_ : robust_want_scale_));
+        t += kind == THALLOX_LOSS_HUBER ? "; huber loss, scale " : "; cauchy loss, scale ";
+        t += sc;
+    }
+    if (held_on()) t += "; " + std::to_string(held_count_) + " unknowns held";
+    return t.c_str();
+}
+
+// ------------------------------------------------------------------ robust losses (energy_ba.hip, DESIGN.md "Robust losses")
+int Plan::set_robust_loss(int kind, float scale)
+{
+    if (kind != THALLOX_LOSS_TRIVIAL && kind != THALLOX_LOSS_HUBER && kind != THALLOX_LOSS_CAUCHY) { set_error("%s: unknown robust loss kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_LOSS_TRIVIAL) { robust_want_ = 0; robust_want_scale_ = 0.0f; return 0; }
+    if (!ok_) return -1;
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no linearisation to reweight (no robust loss)", plugin->name()); return -1; }
+    if (!plugin->robust_ok()) { set_error("%s: no robust loss for this energy (its cost, precomputeJ and apply routes have no robust instantiation; bundle_adjustment's do)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: robust losses run on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (!(scale > 0.0f) || !std::isfinite(scale)) { set_error("%s: the scale of a robust loss must be finite and positive (got %g)", plugin->name(), (double)scale); return -1; }
+    robust_want_ = kind; robust_want_scale_ = scale;
+    return 0;
+}
+
+long Plan::robust_weights(float* host_out, long n)
+{
+    if (!ok_ || !robust_on()) return -1;
+    return plugin->robust_weights(ctx, host_out, n);
+}
+
+// ------------------------------------------------------------------ held unknowns (held.hip, DESIGN.md "Held unknowns")
+int Plan::set_held_unknowns(int input, const unsigned char* held, long n)
+{
+    if (!ok_) return -1;
+    const auto& imgs = plugin->unknown_images();
+    int k = -1;
+    for (size_t i = 0; i < imgs.size(); ++i) if (imgs[i].param_index == input) k = (int)i;
+    if (!held) { if (k >= 0) held_masks_.erase(k); return 0; }
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to hold unknowns in", plugin->name()); return -1; }
+    if (!plugin->hold_ok()) { set_error("%s: no held unknowns for this energy (not every PCG route of its plugin takes M^-1 from the stored vector; bundle_adjustment's do)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: held unknowns run on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (k < 0) { set_error("%s: input %d is not an Unknown of this energy", plugin->name(), input); return -1; }
+    if (n != imgs[(size_t)k].n_floats) { set_error("%s: the mask of input %d has %ld bytes, the unknown has %ld scalars (elements x components)", plugin->name(), input, n, imgs[(size_t)k].n_floats); return -1; }
+    held_masks_[k].assign(held, held + n);
+    return 0;
+}
+
+int Plan::held_prepare()
+{   // the masks in the plan's internal ids, counted, uploaded
+    held_count_ = -1; held_first_ = 0;
+    if (held_masks_.empty()) return 0;
+    if (refuse_unless_one_gpu_pcg(plugin->hold_ok(), "held unknowns need")) return -1;
+    std::vector<unsigned char> flat((size_t)v_.n, 0);
+    for (const auto& m : held_masks_) plugin->hold_to_internal(m.first, m.second.data(), flat.data());
+    long count = 0;
+    for (unsigned char f : flat) count += f != 0;
+    if (count == v_.n) { set_error("%s: the mask holds every unknown (%ld scalars): nothing is left to solve for", plugin->name(), count); return -1; }
+    { const long n0 = plugin->unknown_images()[0].n_floats; for (long i = 0; i < n0; ++i) held_first_ += flat[(size_t)i] != 0; }
+    held_count_ = count;
+    if (count == 0) return 0;      // (nothing held: the plan launches what it launches without a mask)
+    if (!held_mask_ && !(held_mask_ = (unsigned char*)device_alloc((size_t)v_.n_alloc + 64))) { held_count_ = -1; set_error("%s: out of device memory for the mask of held unknowns", plugin->name()); return -1; }
+    if (hipMemcpy(held_mask_, flat.data(), flat.size(), hipMemcpyHostToDevice) != hipSuccess) { held_count_ = -1; set_error("%s: cannot upload the mask of held unknowns", plugin->name()); return -1; }
+    return 0;
+}
+
+int Plan::hold_pcg(float* rz_out)
+{
+    TimedLaunch t(ctx, "HoldPCG");
+    return thallo_hip_hold_pcg(held_mask_, v_.r, v_.pre, v_.z, v_.n, rz_out, ctx.stream);
+}
+
+// ------------------------------------------------------------------ block-Jacobi preconditioner (block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
+int Plan::set_preconditioner(int kind)
+{
+    if (kind != THALLOX_PRECOND_JACOBI && kind != THALLOX_PRECOND_BLOCK_JACOBI) { set_error("%s: unknown preconditioner kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_PRECOND_JACOBI) { block_want_ = false; return 0; }
+    if (!ok_) return -1;
+    if (!plugin->block_precond_ok()) { set_error("%s: no block-Jacobi preconditioner for this energy (its plugin states no blocks; bundle_adjustment does)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: the block-Jacobi preconditioner runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to precondition", plugin->name()); return -1; }
+    block_want_ = true;
+    return 0;
+}
+
+int Plan::block_prepare()
+{   // the regions; H, G and the status word
+    if (refuse_unless_one_gpu_pcg(plugin->block_precond_ok(), "the block-Jacobi preconditioner needs")) return -1;
+    if (!plugin->apply_adds_ctc()) { set_error("%s: the block-Jacobi preconditioner needs a plugin whose applyJTJ adds the LM diagonal (apply_adds_ctc)", plugin->name()); return -1; }
+    block_regions_ = plugin->block_regions();
+    const long nf = thallo_hip_block_floats(block_regions_);
+    if (nf < 0) { set_error("%s: invalid block regions", plugin->name()); return -1; }
+    if (block_H_) return 0;
+    block_H_ = (float*)device_alloc(((size_t)nf + 64) * sizeof(float)); block_G_ = (float*)device_alloc(((size_t)nf + 64) * sizeof(float)); block_status_ = (unsigned*)device_alloc(64);
+    if (!block_H_ || !block_G_ || !block_status_) { block_H_ = block_G_ = nullptr; block_status_ = nullptr; set_error("%s: out of device memory for the block preconditioner", plugin->name()); return -1; }
+    return 0;
+}
+
+int Plan::preconditioner_fallbacks() { return (block_on_ || schur_on_) && block_status_ ? read_word(block_status_) : -1; }
+
+// ------------------------------------------------------------------ Schur complement on the cameras (ba_schur.hip, DESIGN.md "Schur complement on the cameras")
+int Plan::set_linear_solver(int kind)
+{
+    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG && kind != THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; schur_explicit_want_ = false; return 0; }
+    if (!ok_) return -1;
+    const bool ex = kind == THALLOX_SOLVER_SCHUR_EXPLICIT_PCG;
+    const char* what = ex ? "assembled Schur-complement solve" : "Schur-complement solve";
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a"); return -1; }
+    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
+    if (dist_) { set_error("%s: the %s runs on one GPU (this plan is distributed)", plugin->name(), what); return -1; }
+    schur_want_ = true; schur_explicit_want_ = ex;
+    return 0;
+}
+
+int Plan::schur_prepare()
+{
+    if (refuse_unless_one_gpu_pcg(plugin->schur_ok(), "the Schur-complement solve needs")) return -1;
+    if (block_prepare()) return -1;                      // H, G, the status word (G's camera region: the preconditioner of S)
+    if (block_regions_.n != 2 || block_regions_.r[0].offset != 0) { set_error("%s: the Schur-complement solve needs two block regions, the kept one first", plugin->name()); return -1; }
+    thallo_block_regions_t cameras = block_regions_; cameras.n = 1;
+    schur_n_ = (long)block_regions_.r[0].size * block_regions_.r[0].count;
+    schur_hp_off_ = thallo_hip_block_floats(cameras);
+    schur_pt_off_ = block_regions_.r[1].offset;
+    // the assembled form: the structure of S, sized and checked against its budget before it is allocated
+    schur_explicit_ = false;
+    schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
+    if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
+    schur_explicit_ = schur_explicit_want_;
+    if (schur_Ge_) return 0;
+    const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
+    schur_Ge_ = (float*)device_alloc((ns * (ns + 1) / 2 * np + 64) * sizeof(float)); schur_y_ = (float*)device_alloc((ns * np + 64) * sizeof(float));
+    schur_g_ = (float*)device_alloc(((size_t)v_.n_alloc + 64) * sizeof(float)); schur_held_ = (unsigned*)device_alloc(64);
+    if (!schur_Ge_ || !schur_y_ || !schur_g_ || !schur_held_) {
+        schur_Ge_ = schur_y_ = schur_g_ = nullptr; schur_held_ = nullptr;
+        set_error("%s: out of device memory for the Schur-complement solve", plugin->name()); return -1;
+    }
+    return 0;
+}
+
+int Plan::schur_held_points() { return schur_on_ && schur_held_ ? read_word(schur_held_) : -1; }
+
+}  // namespace thallo
