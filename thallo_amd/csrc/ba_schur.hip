@@ -2,7 +2,7 @@
 // With A = J^T J (+ diag(CtC) in LM) = [[B, E], [E^T, Cp]] over [cameras | points] and b = -J^T F = [b_c; b_p], the points are eliminated exactly through their 3 x 3
 // blocks Cp and PCG runs on the cameras only:  S = B - E Cp^-1 E^T,  g = b_c - E Cp^-1 b_p,  S delta_c = g,  delta_p = Cp^-1 (b_p - E^T delta_c).
 //
-//   schur_factor  Cp^-1 = G^T G per point: block_precond.hip's scaled Cholesky (s_i = 1 / sqrt(B_ii), L L^T = S B S, G = L^-1 S) with the ELIMINATION failure rule: a point
+//   schur_factor  Cp^-1 = G^T G per point: block_chol.hpp's scaled Cholesky (s_i = 1 / sqrt(B_ii), L L^T = S B S, G = L^-1 S) with the ELIMINATION failure rule: a point
 //                 whose block has a B_ii that is not a positive finite number, a squared pivot of the unit-diagonal scaled block below 2^-16, or a G that is not finite is
 //                 HELD FIXED for the step: G = 0, so delta_p = 0 and the point contributes no coupling term.  (Dropping a point's rows and columns leaves a principal
 //                 submatrix of A, whose Schur complement stays positive semidefinite; a diagonal fallback in place of Cp^-1 would not.)  Held points are counted.
@@ -13,97 +13,22 @@
 //   schur_back    camera launch u_q = J_c,q delta_c (GN: the loop's last delta_c += alpha p rides in it);  point launch delta_p = G^T (G (b_p - sum J_p,q^T u_q))
 //
 // Camera launches: one wave per camera, lanes striding its observations, two observations per trip with every load of the trip in flight before the first use (k_cam2's
-// shape).  They LOAD the camera half of an observation's block from Jb (72 of its 96 bytes) rather than rebuild it in closed form as k_cam2 does: the blocks are what
+// shape).  They LOAD the camera half of an observation's block from Jb (ba_blocks.hpp: 72 of its 96 bytes) rather than rebuild it in closed form as k_cam2 does: the blocks are what
 // thallo_hip_ba_block_diag and the point blocks JP were formed from, so B, E and Cp of one step come from one set of numbers and S is the Schur complement of exactly
 // the matrix whose blocks were factored.  Point launches: one thread per point over its list, four observations per trip (k_pt2's shape); a point's G (6 words) lives in
 // registers.  Every observation belongs to exactly one point, so the in-place v_q over u_q races with nobody; a thread has read all of its u_q before it writes any.
 // Nothing is indexed dynamically, every loop over a block is unrolled.  Sums: one partial per workgroup, fixed order, no float atomics; the held count is an integer.
 #include "device_common.hpp"
+#include "block_chol.hpp"
+#include "ba_blocks.hpp"
 #include "../../include/thallo_hip.h"
 
 using namespace thallo;
+using thallo::launch::check_launch;
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr float PIVOT_FLOOR = 1.0f / 65536.0f;      // 2^-16: the pivots of a unit-diagonal block lie in (0, 1] and carry a few ulps (2^-24) of error; below this fewer than two digits survive
-inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
-inline int cam_grid(int C_) { int g = (C_ + 3) / 4; if (g > 448) g = 448; return g < 1 ? 1 : g; }
-inline int pt_grid(int P_) { int g = (P_ + BLOCK - 1) / BLOCK; if (g > 512) g = 512; return g < 1 ? 1 : g; }
-
-__host__ __device__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }      // packed index of (i, j), j <= i
-
-// a: in, the lower triangle of the point's block of J^T J; out, G = L^-1 S with L L^T = S (H + diag(sh)) S.  false: the point is held (the caller stores G = 0)
-__device__ __forceinline__ bool factor3(float (&a)[6], const float (&sh)[3])
-{
-    float s[3], inv[3];
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float d = a[tri(i, i)] + sh[i];
-        ok = ok && d > 0.0f && d < INFINITY;
-        s[i] = 1.0f / sqrtf(d);
-        a[tri(i, i)] = d;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) a[tri(i, j)] = (a[tri(i, j)] * s[i]) * s[j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float d = a[tri(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= a[tri(j, k)] * a[tri(j, k)];
-        ok = ok && d >= PIVOT_FLOOR && d < INFINITY;
-        inv[j] = 1.0f / sqrtf(d);
-#pragma unroll
-        for (int i = j + 1; i < 3; ++i) {
-            float v = a[tri(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= a[tri(i, k)] * a[tri(j, k)];
-            a[tri(i, j)] = v * inv[j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float li[3];
-#pragma unroll
-        for (int k = 0; k < i; ++k) li[k] = a[tri(i, k)];
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-            float v = li[j] * inv[j];
-#pragma unroll
-            for (int k = j + 1; k < i; ++k) v += li[k] * a[tri(k, j)];
-            a[tri(i, j)] = -inv[i] * v;
-        }
-        a[tri(i, i)] = inv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) { a[tri(i, j)] *= s[j]; ok = ok && fabsf(a[tri(i, j)]) < INFINITY; }
-    return ok;
-}
-
-// y = G^T (G w)  (block_precond.hip apply_g<3>)
-__device__ __forceinline__ void apply_g3(const float (&g)[6], const float (&w)[3], float (&y)[3])
-{
-    float t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j <= i; ++j) s += g[tri(i, j)] * w[j];
-        t[i] = s;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float s = 0.0f;
-#pragma unroll
-        for (int i = j; i < 3; ++i) s += g[tri(i, j)] * t[i];
-        y[j] = s;
-    }
-}
+constexpr int BLOCK = BA_WG;
 
 __global__ __launch_bounds__(BLOCK) void k_schur_factor(int P_, const float* __restrict__ Hp, const float* __restrict__ shift, float* __restrict__ G, unsigned* __restrict__ held)
 {
@@ -115,7 +40,7 @@ __global__ __launch_bounds__(BLOCK) void k_schur_factor(int P_, const float* __r
         for (int k = 0; k < 6; ++k) a[k] = Hp[(long)k * P_ + j];
 #pragma unroll
         for (int i = 0; i < 3; ++i) sh[i] = shift ? shift[3L * j + i] : 0.0f;
-        const bool ok = factor3(a, sh);
+        const bool ok = factor<3, true>(a, sh);      // false: the point is held, G = 0
 #pragma unroll
         for (int k = 0; k < 6; ++k) G[(long)k * P_ + j] = ok ? a[k] : 0.0f;
         bad += ok ? 0u : 1u;
@@ -132,22 +57,6 @@ __global__ __launch_bounds__(BLOCK) void k_schur_factor(int P_, const float* __r
         for (int k = 0; k < BLOCK / THALLO_WAVE; ++k) s += cnt[k];
         if (s) atomicAdd(held, s);
     }
-}
-
-// the camera half of observation q's block: row 0 = entries 0 .. 8, row 1 = entries 12 .. 20 of the 24 floats
-struct CamRows { float4 a0, a1, b0, b1; float a8, b8; };
-__device__ __forceinline__ CamRows ld_cam_rows(const float4* __restrict__ Jb, long q)
-{
-    const float4* s = Jb + 6 * q;
-    CamRows r;
-    r.a0 = s[0]; r.a1 = s[1]; r.a8 = reinterpret_cast<const float*>(s + 2)[0];
-    r.b0 = s[3]; r.b1 = s[4]; r.b8 = reinterpret_cast<const float*>(s + 5)[0];
-    return r;
-}
-__device__ __forceinline__ void rows_of(const CamRows& r, float (&r0)[9], float (&r1)[9])
-{
-    r0[0] = r.a0.x; r0[1] = r.a0.y; r0[2] = r.a0.z; r0[3] = r.a0.w; r0[4] = r.a1.x; r0[5] = r.a1.y; r0[6] = r.a1.z; r0[7] = r.a1.w; r0[8] = r.a8;
-    r1[0] = r.b0.x; r1[1] = r.b0.y; r1[2] = r.b0.z; r1[3] = r.b0.w; r1[4] = r.b1.x; r1[5] = r.b1.y; r1[6] = r.b1.z; r1[7] = r.b1.w; r1[8] = r.b8;
 }
 
 // u_q = J_c,q x_cam(q), two floats per observation in camera order.  p != NULL (the GN loop's last term): x = delta_c + alpha p, alpha = alphaN / alphaD (0 if alphaD == 0),
@@ -170,7 +79,7 @@ __global__ __launch_bounds__(BLOCK) void k_schur_cam_u(int C_, const int* __rest
         const int q1e = cam_ptr[c + 1];
         for (int q = cam_ptr[c] + lane; q < q1e; q += 128) {
             const bool h1 = q + 64 < q1e;
-            const CamRows A = ld_cam_rows(Jb, q), Bq = ld_cam_rows(Jb, h1 ? q + 64 : q);
+            const CamLd A = ld_cam_rows(Jb, q), Bq = ld_cam_rows(Jb, h1 ? q + 64 : q);
             float a0[9], a1[9], b0[9], b1[9];
             rows_of(A, a0, a1); rows_of(Bq, b0, b1);
             float ja0 = 0.0f, ja1 = 0.0f, jb0 = 0.0f, jb1 = 0.0f;
@@ -209,7 +118,7 @@ __global__ __launch_bounds__(BLOCK) void k_schur_cam_gather(int C_, const int* _
         for (int q = cam_ptr[c] + lane; q < q1e; q += 128) {
             const bool h1 = q + 64 < q1e;
             const int qb = h1 ? q + 64 : q;
-            const CamRows A = ld_cam_rows(Jb, q), Bq = ld_cam_rows(Jb, qb);
+            const CamLd A = ld_cam_rows(Jb, q), Bq = ld_cam_rows(Jb, qb);
             const float2 ta = T[q], tb = T[qb];
             float a0[9], a1[9], b0[9], b1[9];
             rows_of(A, a0, a1); rows_of(Bq, b0, b1);
@@ -259,30 +168,30 @@ __global__ __launch_bounds__(BLOCK) void k_schur_pt(int P_, const int* __restric
         if (MODE != 0) {
             // four observations per trip, all their loads in flight together; added up in the list's order
             for (int k0 = k0b; k0 < k1; k0 += 4) {
-                float2 a[4], b[4], c[4], jp[4]; int q[4];
+                PtLd jq[4]; float2 jp[4]; int q[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; a[u] = JP[3L * k]; b[u] = JP[3L * k + 1]; c[u] = JP[3L * k + 2]; }     // (r0.d9, r0.d10), (r0.d11, r1.d9), (r1.d10, r1.d11)
+                for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; jq[u] = ld_pt_rows(JP, k); }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) jp[u] = U[q[u]];
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (k0 + u < k1) { w[0] += a[u].x * jp[u].x + b[u].y * jp[u].y; w[1] += a[u].y * jp[u].x + c[u].x * jp[u].y; w[2] += b[u].x * jp[u].x + c[u].y * jp[u].y; }
+                    if (k0 + u < k1) { w[0] += jq[u].a.x * jp[u].x + jq[u].b.y * jp[u].y; w[1] += jq[u].a.y * jp[u].x + jq[u].c.x * jp[u].y; w[2] += jq[u].b.x * jp[u].x + jq[u].c.y * jp[u].y; }
             }
         }
-        if (MODE == 0) { apply_g3(g, bv, y); }
-        else if (MODE == 1) { apply_g3(g, w, y); }
-        else { const float d[3] = { bv[0] - w[0], bv[1] - w[1], bv[2] - w[2] }; apply_g3(g, d, y); }
+        if (MODE == 0) { apply_g<3>(g, bv, y); }
+        else if (MODE == 1) { apply_g<3>(g, w, y); }
+        else { const float d[3] = { bv[0] - w[0], bv[1] - w[1], bv[2] - w[2] }; apply_g<3>(g, d, y); }
         if (MODE != 1) { yout[3L * j] = y[0]; yout[3L * j + 1] = y[1]; yout[3L * j + 2] = y[2]; }
         if (MODE == 2) continue;
         for (int k0 = k0b; k0 < k1; k0 += 4) {
-            float2 a[4], b[4], c[4], jp[4]; int q[4];
+            PtLd jq[4]; float2 jp[4]; int q[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; a[u] = JP[3L * k]; b[u] = JP[3L * k + 1]; c[u] = JP[3L * k + 2]; }
+            for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; jq[u] = ld_pt_rows(JP, k); }
 #pragma unroll
             for (int u = 0; u < 4; ++u) jp[u] = MODE == 1 ? U[q[u]] : make_float2(0.0f, 0.0f);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float t0 = a[u].x * y[0] + a[u].y * y[1] + b[u].x * y[2], t1 = b[u].y * y[0] + c[u].x * y[1] + c[u].y * y[2];
+                float t0, t1; pt_j_mul(jq[u], y, t0, t1);
                 if (k0 + u < k1) U[q[u]] = MODE == 1 ? make_float2(jp[u].x - t0, jp[u].y - t1) : make_float2(t0, t1);
             }
         }
@@ -303,7 +212,7 @@ int thallo_hip_ba_schur_factor(int P_, const float* Hp, const float* shift_p, fl
     const hipError_t me = hipMemsetAsync(held, 0, sizeof(unsigned), s);
     if (me != hipSuccess) return -(int)me;
     if (P_ < 1) return 0;
-    hipLaunchKernelGGL(k_schur_factor, dim3(pt_grid(P_)), dim3(BLOCK), 0, s, P_, Hp, shift_p, G, held);
+    hipLaunchKernelGGL(k_schur_factor, dim3(ba_pt_grid(P_)), dim3(BLOCK), 0, s, P_, Hp, shift_p, G, held);
     return check_launch();
 }
 
@@ -312,8 +221,8 @@ int thallo_hip_ba_schur_rhs(int C_, int P_, const int* cam_ptr, const int* pt_pt
 {
     if (!lists_ok(C_, P_, cam_ptr, pt_ptr, pt_pos, Jb, JP, G, U) || !b || !y || !g) return -(int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<0>, dim3(pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, b + 9L * C_, (float2*)U, y, (const unsigned*)nullptr);
-    if (C_ > 0) hipLaunchKernelGGL(k_schur_cam_gather<true>, dim3(cam_grid(C_)), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, (const float2*)U, b, (const float*)nullptr, g, r_out,
+    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<0>, dim3(ba_pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, b + 9L * C_, (float2*)U, y, (const unsigned*)nullptr);
+    if (C_ > 0) hipLaunchKernelGGL(k_schur_cam_gather<true>, dim3(ba_cam_grid(C_)), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, (const float2*)U, b, (const float*)nullptr, g, r_out,
                                    (float*)nullptr, (const unsigned*)nullptr);
     return check_launch();
 }
@@ -323,10 +232,10 @@ int thallo_hip_ba_schur_apply(int C_, int P_, const int* cam_ptr, const int* pt_
 {
     if (!lists_ok(C_, P_, cam_ptr, pt_ptr, pt_pos, Jb, JP, G, U) || C_ < 1 || !x || !Sx || !xSx_out) return -(int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    const int cb = cam_grid(C_);
+    const int cb = ba_cam_grid(C_);
     const thallo_sum_t none = { nullptr, 0 };
     hipLaunchKernelGGL(k_schur_cam_u, dim3(cb), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, const_cast<float*>(x), (const float*)nullptr, none, none, (float2*)U, gate);
-    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<1>, dim3(pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, (const float*)nullptr, (float2*)U, (float*)nullptr, gate);
+    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<1>, dim3(ba_pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, (const float*)nullptr, (float2*)U, (float*)nullptr, gate);
     hipLaunchKernelGGL(k_schur_cam_gather<false>, dim3(cb), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, (const float2*)U, x, ctc, Sx, (float*)nullptr, xSx_out, gate);
     int e = check_launch(); return e ? e : cb;
 }
@@ -337,8 +246,8 @@ int thallo_hip_ba_schur_back(int C_, int P_, const int* cam_ptr, const int* pt_p
     if (!lists_ok(C_, P_, cam_ptr, pt_ptr, pt_pos, Jb, JP, G, U) || !b || !delta) return -(int)hipErrorInvalidValue;
     if (p && (!alphaN.partials || !alphaD.partials || alphaN.count < 1 || alphaD.count < 1)) return -(int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    if (C_ > 0) hipLaunchKernelGGL(k_schur_cam_u, dim3(cam_grid(C_)), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, delta, p, alphaN, alphaD, (float2*)U, (const unsigned*)nullptr);
-    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<2>, dim3(pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, b + 9L * C_, (float2*)U, delta + 9L * C_, (const unsigned*)nullptr);
+    if (C_ > 0) hipLaunchKernelGGL(k_schur_cam_u, dim3(ba_cam_grid(C_)), dim3(BLOCK), 0, s, C_, cam_ptr, (const float4*)Jb, delta, p, alphaN, alphaD, (float2*)U, (const unsigned*)nullptr);
+    if (P_ > 0) hipLaunchKernelGGL(k_schur_pt<2>, dim3(ba_pt_grid(P_)), dim3(BLOCK), 0, s, P_, pt_ptr, pt_pos, (const float2*)JP, G, b + 9L * C_, (float2*)U, delta + 9L * C_, (const unsigned*)nullptr);
     return check_launch();
 }
 

@@ -6,7 +6,7 @@
 // is formed as a block-sparse matrix over the co-visible camera pairs (E Cp^-1 E^T = sum over the points of (E_q G^T) (E_q' G^T)^T with Cp^-1 = G^T G; a held point has
 // G = 0, so W = 0 and it contributes no coupling), and every S x of the PCG loop is one block-sparse mat-vec on 9 C floats.
 //
-//   schur_w         one thread per observation (camera order): E = J_c^T J_p summed over the two residual rows from the 24 floats of Jb, W = E G^T.  W is stored
+//   schur_w         one thread per observation (camera order): E = J_c^T J_p summed over the two residual rows from the 24 floats of Jb (ba_blocks.hpp), W = E G^T.  W is stored
 //                   observation-major, 27 floats at a stride of 32 (one 128-byte line per observation, seven 16-byte stores): the assembly's wave reads the W of ONE
 //                   observation pair per term, every lane a few words of the same two lines, so a term costs two lines whatever the lane's entry is.  (Entry-major planes
 //                   would make this launch's stores coalesced and every load of the assembly a line of its own.)
@@ -19,36 +19,33 @@
 //                   planes S[e * nblk + blk] -- consecutive lanes read consecutive words --, nine sums per lane, the wave butterfly, lanes 0 .. 8 store.  Gated.
 // Nothing is indexed dynamically, every loop over a block is unrolled.  Sums: one partial per workgroup, fixed order, no float atomics.
 #include "device_common.hpp"
+#include "block_regions.hpp"      // tri
+#include "ba_blocks.hpp"
 #include "../../include/thallo_hip.h"
 
 using namespace thallo;
+using thallo::launch::check_launch;
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = BA_WG;
 constexpr int WSTRIDE = THALLO_HIP_SCHUR_W_STRIDE;
-inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
 inline int wave_grid(long n) { long g = (n + 3) / 4; if (g > 65536) g = 65536; return g < 1 ? 1 : (int)g; }
-inline int cam_grid(int C_) { int g = (C_ + 3) / 4; if (g > 448) g = 448; return g < 1 ? 1 : g; }      // thallo_hip_ba_schur_apply's: the same number of partials
-__host__ __device__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }      // packed index of (i, j), j <= i
 
 __global__ __launch_bounds__(BLOCK) void k_schur_w(int O_, int P_, const int* __restrict__ q_pt, const float4* __restrict__ Jb, const float* __restrict__ G, float4* __restrict__ W)
 {
     for (int q = blockIdx.x * BLOCK + threadIdx.x; q < O_; q += gridDim.x * BLOCK) {
-        const float4* src = Jb + 6L * q;
-        const float4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4], v5 = src[5];
+        const Blk b = ld_blk(Jb, q);
         const int j = q_pt[q];
         float g[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) g[k] = G[(long)k * P_ + j];
-        const float a0[9] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x }, a1[9] = { v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w, v5.x };
-        const float p0[3] = { v2.y, v2.z, v2.w }, p1[3] = { v5.y, v5.z, v5.w };
         float w[28];
 #pragma unroll
         for (int a = 0; a < 9; ++a) {
             float e[3];
 #pragma unroll
-            for (int n = 0; n < 3; ++n) e[n] = a0[a] * p0[n] + a1[a] * p1[n];
+            for (int n = 0; n < 3; ++n) e[n] = b.a[a] * b.a[BA_NC + n] + b.a[BA_ROW + a] * b.a[BA_ROW + BA_NC + n];
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 float s = 0.0f;
@@ -183,7 +180,7 @@ int thallo_hip_ba_schur_apply_s(int C_, long nblk, const int* row_ptr, const int
                                 thallo_stream_t stream)
 {
     if (C_ < 1 || nblk < C_ || !row_ptr || !col || !S || !x || !Sx || !xSx_out) return -(int)hipErrorInvalidValue;
-    const int cb = cam_grid(C_);
+    const int cb = ba_cam_grid(C_);
     hipLaunchKernelGGL(k_schur_apply_s, dim3(cb), dim3(BLOCK), 0, (hipStream_t)stream, C_, nblk, row_ptr, col, S, x, Sx, xSx_out, gate);
     const int e = check_launch(); return e ? e : cb;
 }

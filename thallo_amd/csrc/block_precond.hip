@@ -3,7 +3,7 @@
 // 1 / (CtC + diag) in LM; gauss_newton.t:638-648, 929-969).
 //
 //   block_diag    H  = the lower triangles of the blocks of J^T J, once per GN / LM step, from what precomputeJ wrote          (bundle adjustment's: k_ba_block_diag)
-//   block_factor  B  = H + diag(shift);  s_i = 1 / sqrt(B_ii);  L L^T = S B S (Cholesky);  G = L^-1 S, lower triangular, packed
+//   block_factor  B  = H + diag(shift);  s_i = 1 / sqrt(B_ii);  L L^T = S B S (Cholesky);  G = L^-1 S, lower triangular, packed          (the factor and its apply: block_chol.hpp)
 //   block_apply   z  = G^T (G r)  (= B^-1 r), partials of r . z
 //   block_step2   the GN PCGStep2 with that z;  block_step2_lm  the LM PCGStep2 (delta, r, z, betaN, q)
 //
@@ -18,14 +18,16 @@
 // Reductions as everywhere (device_common.hpp): one partial per workgroup, fixed order, no float atomics; bitwise reproducible for a launch shape.
 #include "device_common.hpp"
 #include "block_regions.hpp"      // tri, regions_ok, locate: shared with held.hip
+#include "block_chol.hpp"         // factor, apply_g: shared with ba_schur.hip
+#include "ba_blocks.hpp"          // bundle adjustment's blocks and launch shapes (k_ba_block_diag)
 #include "../../include/thallo_hip.h"
 
 using namespace thallo;
+using thallo::launch::check_launch;
 
 namespace {
 
 constexpr int BLOCK = 256;
-inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
 
 inline int block_grid(long blocks)
 {
@@ -50,81 +52,6 @@ template <int N> __device__ __forceinline__ void store_vec(float* __restrict__ v
     for (int i = 0; i < N; ++i) v[w.first + (long)N * w.b + i] = x[i];
 }
 
-// z = G^T (G r)
-template <int N> __device__ __forceinline__ void apply_g(const float (&g)[tri_n(N)], const float (&r)[N], float (&z)[N])
-{
-    float y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j <= i; ++j) s += g[tri(i, j)] * r[j];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        float s = 0.0f;
-#pragma unroll
-        for (int i = j; i < N; ++i) s += g[tri(i, j)] * y[i];
-        z[j] = s;
-    }
-}
-
-// a: in, the lower triangle of H; out, G = L^-1 S with L L^T = S (H + diag(sh)) S.  false: the block has a diagonal entry or a pivot that is not a positive
-// finite number, or G came out non-finite -- the caller falls back to the diagonal
-template <int N> __device__ __forceinline__ bool factor(float (&a)[tri_n(N)], const float (&sh)[N])
-{
-    float s[N], inv[N];
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float d = a[tri(i, i)] + sh[i];
-        ok = ok && d > 0.0f && d < INFINITY;
-        s[i] = 1.0f / sqrtf(d);
-        a[tri(i, i)] = d;
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) a[tri(i, j)] = (a[tri(i, j)] * s[i]) * s[j];
-    // Cholesky, column by column, in place
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        float d = a[tri(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= a[tri(j, k)] * a[tri(j, k)];
-        ok = ok && d > 0.0f && d < INFINITY;
-        inv[j] = 1.0f / sqrtf(d);
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            float v = a[tri(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= a[tri(i, k)] * a[tri(j, k)];
-            a[tri(i, j)] = v * inv[j];
-        }
-    }
-    // L^-1, row by row, in place: row i of L is needed for every entry of row i of the inverse, the rows above are the inverse's already
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float li[N];
-#pragma unroll
-        for (int k = 0; k < i; ++k) li[k] = a[tri(i, k)];
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-            float v = li[j] * inv[j];
-#pragma unroll
-            for (int k = j + 1; k < i; ++k) v += li[k] * a[tri(k, j)];
-            a[tri(i, j)] = -inv[i] * v;
-        }
-        a[tri(i, i)] = inv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) { a[tri(i, j)] *= s[j]; ok = ok && fabsf(a[tri(i, j)]) < INFINITY; }
-    return ok;
-}
-
 template <int N> __device__ __forceinline__ bool factor_one(const Where& w, const float* __restrict__ H, const float* __restrict__ shift, const float* __restrict__ pre,
                                                             float* __restrict__ G)
 {
@@ -133,7 +60,7 @@ template <int N> __device__ __forceinline__ bool factor_one(const Where& w, cons
 #pragma unroll
     for (int i = 0; i < N; ++i) sh[i] = shift ? shift[w.first + (long)N * w.b + i] : 0.0f;
     const bool ok = factor<N>(a, sh);
-    if (!ok) {      // G = diag(sqrt(pre)): G^T G r = pre . r, the point-Jacobi preconditioner the plan already holds
+    if (!ok) {      // the preconditioner's failure rule: G = diag(sqrt(pre)): G^T G r = pre . r, the point-Jacobi preconditioner the plan already holds
 #pragma unroll
         for (int k = 0; k < tri_n(N); ++k) a[k] = 0.0f;
 #pragma unroll
@@ -252,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) void k_block_step2_lm(thallo_block_regions_t
 // ------------------------------------------------------------------------------------------ bundle adjustment's blocks
 // Workgroups [0, cam_blocks): one wave per camera, lanes striding its observations (as energy_ba.hip k_gather<0> does for the nine diagonal sums: the diagonal entries
 // here are the same sums in the same order), 45 sums of J_c^T J_c over both residual rows from the 96-byte blocks Jb; the rest: one thread per point over its packed
-// point blocks JP (contiguous per point), 6 sums.
+// point blocks JP (contiguous per point), 6 sums.  The two layouts and the launch shape: ba_blocks.hpp.
 __global__ __launch_bounds__(BLOCK) void k_ba_block_diag(int C_, int P_, int cam_blocks, const int* __restrict__ cam_ptr, const int* __restrict__ pt_ptr,
                                                          const float4* __restrict__ Jb, const float2* __restrict__ JP, float* __restrict__ H)
 {
@@ -263,10 +190,8 @@ __global__ __launch_bounds__(BLOCK) void k_ba_block_diag(int C_, int P_, int cam
 #pragma unroll
             for (int k = 0; k < 45; ++k) s[k] = 0.0f;
             for (int q = cam_ptr[c] + lane; q < cam_ptr[c + 1]; q += 64) {
-                const float4* src = Jb + 6L * q;
-                const float4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4], v5 = src[5];
-                const float r0[9] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x };      // d r0 / d camera (entries 0..8 of the block)
-                const float r1[9] = { v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w, v5.x };      // d r1 / d camera (entries 12..20)
+                float r0[9], r1[9];
+                rows_of(ld_cam_rows(Jb, q), r0, r1);
 #pragma unroll
                 for (int i = 0; i < 9; ++i)
 #pragma unroll
@@ -287,8 +212,8 @@ __global__ __launch_bounds__(BLOCK) void k_ba_block_diag(int C_, int P_, int cam
         for (int j = (blockIdx.x - cam_blocks) * BLOCK + threadIdx.x; j < P_; j += nb * BLOCK) {
             float s[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
             for (int k = pt_ptr[j]; k < pt_ptr[j + 1]; ++k) {
-                const float2 a = JP[3L * k], b = JP[3L * k + 1], c = JP[3L * k + 2];      // (r0.d9, r0.d10), (r0.d11, r1.d9), (r1.d10, r1.d11)
-                const float r0[3] = { a.x, a.y, b.x }, r1[3] = { b.y, c.x, c.y };
+                float r0[3], r1[3];
+                rows_of(ld_pt_rows(JP, k), r0, r1);
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -315,9 +240,8 @@ long thallo_hip_block_floats(thallo_block_regions_t regions)
 int thallo_hip_ba_block_diag(int C_, int P_, const int* cam_ptr, const int* pt_ptr, const float* Jb, const float* JP, float* H, thallo_stream_t stream)
 {
     if (C_ < 0 || P_ < 0 || C_ + P_ < 1 || !cam_ptr || !pt_ptr || !Jb || !JP || !H) return -(int)hipErrorInvalidValue;
-    int cb = (C_ + 3) / 4; if (cb > 448) cb = 448;
-    int pb = (P_ + BLOCK - 1) / BLOCK; if (pb > 512) pb = 512; if (pb < 1) pb = 1;
-    hipLaunchKernelGGL(k_ba_block_diag, dim3(cb + pb), dim3(BLOCK), 0, (hipStream_t)stream, C_, P_, cb, cam_ptr, pt_ptr, (const float4*)Jb, (const float2*)JP, H);
+    int cb, grid; gather_shape(C_, P_, cb, grid);
+    hipLaunchKernelGGL(k_ba_block_diag, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, C_, P_, cb, cam_ptr, pt_ptr, (const float4*)Jb, (const float2*)JP, H);
     return check_launch();
 }
 

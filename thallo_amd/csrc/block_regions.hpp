@@ -1,4 +1,5 @@
-// block_regions.hpp -- what the launches over block regions share (block_precond.hip, held.hip): the packed lower triangle and which region a block belongs to.
+// block_regions.hpp -- what the launches over block regions share (block_precond.hip, held.hip; tri also block_chol.hpp, ba_schur_explicit.hip): the packed lower triangle
+// and which region a block belongs to.
 // Storage as in block_precond.hip: H and G hold the regions one after the other, each as n (n + 1) / 2 planes of `count` floats; one lane handles one block.
 #pragma once
 #include "../../include/thallo_hip.h"

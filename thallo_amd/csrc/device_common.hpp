@@ -437,6 +437,9 @@ __device__ __forceinline__ float guarded_invert(float d)
     return 1.0f / (s * s);
 }
 
+// Host: what an entry point returns after its launches, 0 or -hipError_t.  (A namespace of its own: most kernel files still define a copy; the others say `using`.)
+namespace launch { inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; } }
+
 // XCD-aware persistent tile schedule.  Workgroups are dealt round-robin over the 8 XCDs
 // (blockIdx % 8 labels the XCD group), so group g owns the contiguous tile range
 // [g*T/8, (g+1)*T/8) and its members sweep it together: x/y-neighbouring tiles -- whose halos

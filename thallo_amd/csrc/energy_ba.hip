@@ -6,7 +6,7 @@
 // transposes it (csr2csc :1375-1378) and every PCG iteration runs two csrmv: Jp = J p, Ap = J^T (Jp)
 // (:1493-1517).  282.7 MB of values+column indices per iteration at ladybug-1723 size.
 //
-// Here J is materialised once per GN iteration as ONE 96-byte block per observation
+// Here J is materialised once per GN iteration as ONE 96-byte block per observation (ba_blocks.hpp: the layout, its loads, the packed point half, the launch shapes)
 //   Jb[q] = { dr0/dcam[9], dr0/dpt[3], dr1/dcam[9], dr1/dpt[3] }      (24 floats, 16-byte aligned)
 // stored in camera-sorted order q (camera incidence CSR).  The column indices are implicit (camera block,
 // point block), so no colInd array and no transposed copy exist: J^T(Jp) is a GATHER
@@ -19,15 +19,16 @@
 //
 // Flat vector layout: [cameras 9*c+k | points 9*C + 3*p + k]  (thallo.t:1104-1125).
 #include "device_common.hpp"
+#include "ba_blocks.hpp"      // the block of an observation, its packed point half, the launch shapes
 #include <cstring>
 #include "../../include/thallo_hip.h"
 
 using namespace thallo;
+using thallo::launch::check_launch;
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
+constexpr int BLOCK = BA_WG;
 
 struct Jet {
     float v; float d[12];
@@ -145,7 +146,6 @@ __device__ __forceinline__ CamPre ba_cam_pre(const float* __restrict__ cam)
     }
     return o;
 }
-struct Blk { float a[24]; };
 __device__ __forceinline__ Blk ba_block(const CamPre& c, float X0, float X1, float X2)
 {
     Blk b;
@@ -245,14 +245,6 @@ __global__ __launch_bounds__(BLOCK) void k_compute_j(int O_, const float* __rest
             F[q] = make_float2(r0, r1);
         }
     }
-}
-
-__device__ __forceinline__ Blk ld_blk(const float4* __restrict__ Jb, long q)
-{
-    Blk b; const float4* s = Jb + 6 * q;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { const float4 v = s[k]; b.a[4 * k] = v.x; b.a[4 * k + 1] = v.y; b.a[4 * k + 2] = v.z; b.a[4 * k + 3] = v.w; }
-    return b;
 }
 
 // Gather kernels: workgroups [0, cam_blocks) = 4 cameras each (one wave per camera); the rest = one thread per point.
@@ -377,9 +369,7 @@ __global__ __launch_bounds__(BLOCK) void k_inverse_perm(int O_, const int* __res
 __global__ __launch_bounds__(BLOCK) void k_pack_point_blocks(int O_, const float4* __restrict__ Jb, const int* __restrict__ q_ptk, float2* __restrict__ JP)
 {
     for (int q = blockIdx.x * BLOCK + threadIdx.x; q < O_; q += gridDim.x * BLOCK) {
-        const float4 a = Jb[6L * q + 2], b = Jb[6L * q + 5];       // (r0.d8, r0.d9, r0.d10, r0.d11), (r1.d8 .. r1.d11): entries 9..11 are the point's
-        float2* d = JP + 3L * q_ptk[q];
-        d[0] = make_float2(a.y, a.z); d[1] = make_float2(a.w, b.y); d[2] = make_float2(b.z, b.w);
+        pack_pt_rows(Jb, q, JP, q_ptk[q]);
     }
 }
 
@@ -509,14 +499,14 @@ __global__ __launch_bounds__(BLOCK) void k_pt2(int C_, int P_, const int* __rest
         // the gather behind it are the kernel's critical path); added up in the list's order, as the one-at-a-time loop did
         const int k1 = pt_ptr[j + 1];
         for (int k0 = pt_ptr[j]; k0 < k1; k0 += 4) {
-            float2 a[4], b[4], c[4], jp[4]; int q[4];
+            PtLd jq[4]; float2 jp[4]; int q[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; a[u] = JP[3L * k]; b[u] = JP[3L * k + 1]; c[u] = JP[3L * k + 2]; }     // (r0.d9, r0.d10), (r0.d11, r1.d9), (r1.d10, r1.d11)
+            for (int u = 0; u < 4; ++u) { const int k = min(k0 + u, k1 - 1); q[u] = pt_pos[k]; jq[u] = ld_pt_rows(JP, k); }
 #pragma unroll
             for (int u = 0; u < 4; ++u) jp[u] = JpC[q[u]];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (k0 + u < k1) { s0 += a[u].x * jp[u].x + b[u].y * jp[u].y; s1 += a[u].y * jp[u].x + c[u].x * jp[u].y; s2 += b[u].x * jp[u].x + c[u].y * jp[u].y; }
+                if (k0 + u < k1) { s0 += jq[u].a.x * jp[u].x + jq[u].b.y * jp[u].y; s1 += jq[u].a.y * jp[u].x + jq[u].c.x * jp[u].y; s2 += jq[u].b.x * jp[u].x + jq[u].c.y * jp[u].y; }
         }
         if (ctc) { s0 += cv[0] * pv[0]; s1 += cv[1] * pv[1]; s2 += cv[2] * pv[2]; }
         if (rst.r) {
@@ -538,13 +528,6 @@ __global__ __launch_bounds__(BLOCK) void k_pt2(int C_, int P_, const int* __rest
 #ifdef THALLO_RESEARCH
 #include "probe/ba_resident_device.inc"      // the one-launch PCG loop (round 5: bit-identical, slower; research builds only)
 #endif
-
-inline void gather_shape(int C_, int P_, int& cam_blocks, int& grid)
-{
-    cam_blocks = (C_ + 3) / 4; if (cam_blocks > 448) cam_blocks = 448;
-    int pb = (P_ + BLOCK - 1) / BLOCK; if (pb > 512) pb = 512; if (pb < 1) pb = 1;
-    grid = cam_blocks + pb;                        // <= 960 partials
-}
 
 // kind: THALLO_HIP_LOSS_HUBER / _CAUCHY, scale finite and positive -- anything else is an error, never the squared loss
 inline bool loss_ok(int kind, float scale) { return (kind == THALLO_HIP_LOSS_HUBER || kind == THALLO_HIP_LOSS_CAUCHY) && scale > 0.0f && scale <= 3.402823466e38f; }

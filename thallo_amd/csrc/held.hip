@@ -13,11 +13,11 @@
 #include "../../include/thallo_hip.h"
 
 using namespace thallo;
+using thallo::launch::check_launch;
 
 namespace {
 
 constexpr int BLOCK = 256;
-inline int check_launch() { hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
 inline int grid_for(long items)
 {
     long g = (items + BLOCK - 1) / BLOCK;
