@@ -80,7 +80,7 @@ typedef struct thallo_fin_t {
     float*       betaN_word;
 } thallo_fin_t;
 
-/* DEFERRED finish of the one-kernel PCG iteration (thallo_hip_iw_pcg_iter*_deferred): instead of the launch's last workgroup reading the partials
+/* DEFERRED finish of the one-kernel PCG iteration (thallo_iw_iter_t.prev): instead of the launch's last workgroup reading the partials
    back, the NEXT launch receives iteration k-1's raw partials -- alphaD (float) and {N, S1, S2} (double), `count` workgroups -- and every wave adds
    them up itself while its first rows load; its workgroup 0 leaves alphaD_{k-1} / betaN_{k-1} behind in the two words.  Same summation order, same
    bits as thallo_hip_iw_pcg_iter_finish.  The s12 buffer a launch writes must differ from the one it reads (ping-pong).  After the last iteration
@@ -298,96 +298,70 @@ int thallo_hip_iw_pcg_step1(int W, int H, int row0, int row1, const float* cs, c
  * doubles).  pcg_iter_finish (one wave) then writes alphaD_k and betaN_k = N - 2 alpha_k S1 + alpha_k^2 S2
  * (= r_{k+1}.M^-1 r_{k+1}, evaluated in double from exact products of the float data), i.e. both PCG scalars of the iteration come
  * from ONE reduction point.  r, Ap and p ping-pong (in != out); ghost rows of a slab: r and p are
- * kept current by the kernel, Ap_in's ghost rows have to be refreshed from the neighbour.  81 B/pixel (+18 deferred delta). */
-int thallo_hip_iw_pcg_iter(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                           float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                           const float* p_in, float* p_out, float* delta, int mode,
-                           thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev,
-                           thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                           const int* irregular, float* alphaD_out, double* s12_out,
-                           unsigned* fin_tickets, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
-/* fin_tickets / alphaD_word / betaN_word (all or none): THALLO_HIP_FIN_TICKET_WORDS zeroed device words + the two scalar words.  When given,
+ * kept current by the kernel, Ap_in's ghost rows have to be refreshed from the neighbour.  81 B/pixel (+18 deferred delta).
+ *
+ * Three kernels run it, each in up to four forms; ONE argument block, thallo_iw_iter_t, says everything a launch carries, and the form follows from
+ * which of its fields are set:
+ *   prev                deferred finish: the launch adds up iteration k-1's partials itself (thallo_prev_t above); alphaN_prev = alphaN_{k-1} must be a
+ *                       finished sum, alphaD_prev / betaN_prev and the tickets are not looked at, `prev` is ignored for mode & 1 (first iteration of a GN step)
+ *   dist                a row slab of a multi-GPU run: additionally stores the first / last owned row of Ap_out into the neighbours' ghost rows
+ *                       (dist->peer_r[k] + dist->peer_off_o/a[k] = that row inside the neighbour's Ap_out buffer), peer-to-peer
+ *   dist and gs         the slab iteration with the DEFERRED cross-rank finish (round 4; the recomputing kernel only): the launch stores this rank's partials
+ *                       only, and it finishes iteration k-1 itself: `prev` = that iteration's partials of THIS rank and its two words, prev_slot0 = the mailbox
+ *                       slots of its exchange, gs = two device words of 8 bytes (zeroed once) through which the launch's designated wave (first segment of
+ *                       strip 0) hands the two GLOBAL words to the other waves.  Same granules, slots, rank order and summation order as the exchange at the
+ *                       end of a launch: same bits.  alphaN_prev must be a finished word.  thallo_hip_iw_dist_finish_deferred: one wave that finishes a GN
+ *                       step's last iteration the same way.
+ * fin_tickets / alphaD_word / betaN_word (all or none): THALLO_HIP_FIN_TICKET_WORDS zeroed device words + the two scalar words.  When given,
  * the launch's last workgroup does pcg_iter_finish's job itself (same summation order, same bits) and no separate launch is needed; the
- * tickets are zero again when the kernel ends.  alphaN_k is taken from betaN_prev (which is alphaN_k by definition). */
+ * tickets are zero again when the kernel ends.  alphaN_k is taken from betaN_prev (which is alphaN_k by definition).  With `dist` the launch's last
+ * workgroup then IS the exchange (thallo_hip_dist_exchange_iter's job, mailbox slots slot0 .. slot0+6, betaN_prev must be a one-word sum): one launch
+ * per PCG iteration on every rank. */
 #define THALLO_HIP_FIN_TICKET_WORDS 528
-/* the same over a row slab of a multi-GPU run: additionally stores the first / last owned row of Ap_out into the neighbours' ghost rows
-   (d.peer_r[k] + d.peer_off_o/a[k] = that row inside the neighbour's Ap_out buffer), peer-to-peer */
-int thallo_hip_iw_pcg_iter_dist(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                                float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                const float* p_in, float* p_out, float* delta, int mode,
-                                thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev,
-                                thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                                const int* irregular, thallo_dist_t d, float* alphaD_out, double* s12_out,
-                                unsigned* fin_tickets, int slot0, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
-/* fin_tickets / alphaD_word / betaN_word (all or none): the launch's last workgroup then IS the exchange (thallo_hip_dist_exchange_iter's job,
-   mailbox slots slot0 .. slot0+6, betaN_prev must be a one-word sum): one launch per PCG iteration on every rank. */
-/* The same iteration as a barrier-free marching stencil (energy_image_warping_march.hip): a wave owns a 128-pixel column strip, keeps a
+typedef struct thallo_iw_iter_t {
+    int W, H, row0, row1;                       /* the LOCAL image and its owned rows (row0 = 0, row1 = H: a whole image) */
+    const float* cs;                            /* per-step planes: (cos, sin), UrShape, flags byte, M^-1 (urshape / pre: the tile kernel only) */
+    const float* urshape;
+    const unsigned char* flags;
+    const float* pre;
+    const int* irregular;                       /* the word pcg_init wrote (may be NULL) */
+    float w_fit, w_reg;
+    const float* r_in;  float* r_out;           /* ping-pong planes */
+    const float* Ap_in; float* Ap_out;
+    const float* p_in;  float* p_out;
+    float* delta;
+    int mode;                                   /* as in pcg_step1 */
+    thallo_sum_t alphaN_prev, alphaD_prev, betaN_prev, alphaN_prev2, alphaD_prev2;
+    float* alphaD_out; double* s12_out;         /* this launch's partials */
+    unsigned* fin_tickets; float* alphaD_word; float* betaN_word; int slot0;      /* in-kernel finish (slot0: with dist) */
+    const thallo_dist_t* dist;                  /* NULL on one GPU */
+    const thallo_prev_t* prev;                  /* NULL: no deferred finish */
+    int prev_slot0; unsigned long long* gs;     /* deferred cross-rank finish (dist and prev) */
+} thallo_iw_iter_t;
+unsigned thallo_hip_iw_iter_size(void);         /* sizeof(thallo_iw_iter_t) as the library was built: a mirror of the block in another language checks itself against it */
+/* THALLO_IW_ITER_TILE: the LDS tile kernel (energy_image_warping.hip), any UrShape, any W.
+ * THALLO_IW_ITER_MARCH: the same iteration as a barrier-free marching stencil (energy_image_warping_march.hip): a wave owns a 128-pixel column strip, keeps a
  * three-row window in registers, x neighbours through DPP lane shifts, rows prefetched ahead; unit-pixel-grid UrShape ONLY (W even).
  * The caller establishes that property once per Init (thallo_hip_iw_urshape_irregular: *count_out == 0); if the word pcg_init wrote
  * (`irregular`, may be NULL = trust the caller) is nonzero the kernel writes NaN scalars instead of computing.  Same buffers, modes,
- * partial / ticket / scalar-word conventions as thallo_hip_iw_pcg_iter (no urshape / pre arguments: never read). */
-int thallo_hip_iw_pcg_iter_march(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                 float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                 const float* p_in, float* p_out, float* delta, int mode,
-                                 thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev,
-                                 thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                                 const int* irregular, float* alphaD_out, double* s12_out,
-                                 unsigned* fin_tickets, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
-int thallo_hip_iw_pcg_iter_march_dist(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                      float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                      const float* p_in, float* p_out, float* delta, int mode,
-                                      thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev,
-                                      thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                                      const int* irregular, thallo_dist_t d, float* alphaD_out, double* s12_out,
-                                      unsigned* fin_tickets, int slot0, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
-/* The slab iteration with the DEFERRED cross-rank finish (round 4; energy_image_warping_march_rc.hip): as thallo_hip_iw_pcg_iter_march_rc_dist without tickets -- the launch
-   stores this rank's partials only --, and it finishes iteration k-1 itself: `prev` = that iteration's partials of THIS rank and its two words, prev_slot0 = the mailbox
-   slots of its exchange, gs = two device words of 8 bytes (zeroed once) through which the launch's designated wave (first segment of strip 0) hands the two GLOBAL words to
-   the other waves.  Same granules, slots, rank order and summation order as the exchange at the end of a launch: same bits.  alphaN_prev must be a finished word.
-   thallo_hip_iw_dist_finish_deferred: one wave that finishes a GN step's last iteration the same way. */
-int thallo_hip_iw_pcg_iter_march_rc_dist_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                                  const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                                  thallo_sum_t alphaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2, thallo_prev_t prev, int prev_slot0,
-                                                  unsigned long long* gs, const int* irregular, thallo_dist_t d, float* alphaD_out, double* s12_out, thallo_stream_t stream);
-/* 1: the deferred cross-rank finish may run on `rows` owned rows of a W-wide slab (every workgroup of its launch, the eight extra ones included, is resident at once:
-   its working waves wait for the last workgroup's granules); 0: the caller runs thallo_hip_iw_pcg_iter_march_rc_dist */
-int thallo_hip_iw_march_rc_deferred_fits(int W, int rows);
-int thallo_hip_iw_dist_finish_deferred(thallo_prev_t prev, int prev_slot0, thallo_sum_t alphaN_prev, thallo_dist_t d, unsigned long long* gs, thallo_stream_t stream);
-/* the two one-kernel iterations with the deferred finish (thallo_prev_t above): alphaN_prev = alphaN_{k-1} (a finished sum), alphaN_prev2 / alphaD_prev2 as
-   in the plain forms; `prev` is ignored for mode & 1 (first iteration of a GN step) */
-int thallo_hip_iw_pcg_iter_deferred(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                                    float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                    const float* p_in, float* p_out, float* delta, int mode,
-                                    thallo_sum_t alphaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2, thallo_prev_t prev,
-                                    const int* irregular, float* alphaD_out, double* s12_out, thallo_stream_t stream);
-int thallo_hip_iw_pcg_iter_march_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                          float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                          const float* p_in, float* p_out, float* delta, int mode,
-                                          thallo_sum_t alphaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2, thallo_prev_t prev,
-                                          const int* irregular, float* alphaD_out, double* s12_out, thallo_stream_t stream);
-/* The marching iteration WITHOUT an A p plane (round 4; energy_image_warping_march_rc.hip): iteration k >= 1 on the unit pixel grid.
+ * partial / ticket / scalar-word conventions as the tile kernel (urshape / pre: never read).  Its slab form has no delta mode 2.
+ * THALLO_IW_ITER_MARCH_RC: the marching iteration WITHOUT an A p plane (round 4; energy_image_warping_march_rc.hip): iteration k >= 1 on the unit pixel grid.
  * r_out = r_in - alpha_{k-1} (J^T J p_in) with J^T J p_{k-1} RECOMPUTED from the rows of p_in the launch loads anyway, p_out = M^-1 r_out + beta_{k-1} p_in,
- * the delta update of `mode` (never mode & 1: a GN step's first iteration has no A p_{k-1}; thallo_hip_iw_pcg_iter_march runs it), and the partials of
+ * the delta update of `mode` (never mode & 1: a GN step's first iteration has no A p_{k-1}; THALLO_IW_ITER_MARCH runs it), and the partials of
  * alphaD_k / N, S1, S2 from J^T J p_out -- which is not stored.  57 B/pixel instead of 81 (+ 18 of deferred delta); r, p, delta and every alpha / beta are
- * bit-identical to thallo_hip_iw_pcg_iter_march with the same rows per segment.  Scalars / partials / tickets as there.
+ * bit-identical to THALLO_IW_ITER_MARCH with the same rows per segment.  Scalars / partials / tickets as there.
  * Whole images (row0 = 0, row1 = H): Ap_in / Ap_out are not touched (NULL is fine).  A row slab of a multi-GPU run (one ghost row towards each neighbour): the
- * exchange stays the stored-plane kernel's -- rows row0 and row1 - 1 of J^T J p_out are written to Ap_out (the _dist form: into the neighbours' ghost rows,
+ * exchange stays the stored-plane kernel's -- rows row0 and row1 - 1 of J^T J p_out are written to Ap_out (with `dist`: into the neighbours' ghost rows,
  * peer-to-peer, and its last workgroup is the scalar exchange), and on a ghost row J^T J p_in is READ from Ap_in, where the exchange put it -- so the two kernels
  * are interchangeable launch by launch.  Replaces PCGStep1 + PCGStep2 + PCGStep3 (gauss_newton.t:734-752,801-843,889-899). */
-int thallo_hip_iw_pcg_iter_march_rc(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                    const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                    thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                                    const int* irregular, float* alphaD_out, double* s12_out,
-                                    unsigned* fin_tickets, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
-int thallo_hip_iw_pcg_iter_march_rc_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                             const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                             thallo_sum_t alphaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2, thallo_prev_t prev,
-                                             const int* irregular, float* alphaD_out, double* s12_out, thallo_stream_t stream);
-int thallo_hip_iw_pcg_iter_march_rc_dist(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                         const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                         thallo_sum_t alphaN_prev, thallo_sum_t alphaD_prev, thallo_sum_t betaN_prev, thallo_sum_t alphaN_prev2, thallo_sum_t alphaD_prev2,
-                                         const int* irregular, thallo_dist_t d, float* alphaD_out, double* s12_out,
-                                         unsigned* fin_tickets, int slot0, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
+enum { THALLO_IW_ITER_TILE = 0, THALLO_IW_ITER_MARCH = 1, THALLO_IW_ITER_MARCH_RC = 2 };
+/* Returns the workgroup count (= number of partials), or a negative hipError_t: -hipErrorInvalidValue for a malformed block, -hipErrorNotSupported for a form
+ * the kernel does not have (the deferred cross-rank finish on the tile or stored-plane kernel, `prev` with `dist` but no gs) or a shape it does not take. */
+int thallo_hip_iw_pcg_iter(int kernel, const thallo_iw_iter_t* a, thallo_stream_t stream);
+/* 1: the deferred cross-rank finish may run on `rows` owned rows of a W-wide slab (every workgroup of its launch, the eight extra ones included, is resident at once:
+   its working waves wait for the last workgroup's granules); 0: the caller leaves gs NULL (the exchange at the launch's end) */
+int thallo_hip_iw_march_rc_deferred_fits(int W, int rows);
+int thallo_hip_iw_dist_finish_deferred(thallo_prev_t prev, int prev_slot0, thallo_sum_t alphaN_prev, thallo_dist_t d, unsigned long long* gs, thallo_stream_t stream);
 void thallo_hip_march_rc_debug_set(int what, int value);  /* sweep builds (tools/rc_probe.py) only: 0 rows of prefetch (1, 2, 4), 1 register budget (workgroups per CU: 1, 2, 3), 2 cache-policy mask */
 /* *count_out (device int) = number of pixels whose right / down UrShape neighbour is not at the exact unit offset (0 = pixel grid) */
 int thallo_hip_iw_urshape_irregular(int W, int H, const float* urshape, int* count_out, thallo_stream_t stream);
@@ -395,7 +369,7 @@ void thallo_hip_march_debug_set(int what, int value);     /* tools / tests only:
 /* ---- the PCG loop of a whole Gauss-Newton step in ONE launch (energy_image_warping_resident.hip), for images whose solver state fits the chip's
  * registers: a wave keeps r, p, A p of its pixels in registers (delta in LDS) for all L iterations; per iteration the boundary of A p goes to the four
  * neighbouring waves and the workgroup's sums to every workgroup as 8-byte {value | tag} granules, no launch boundary, no grid barrier.  Same geometry,
- * arithmetic and summation order as thallo_hip_iw_pcg_iter_march with the same rows per segment: bit-identical r, p, delta, A p, alpha, beta.
+ * arithmetic and summation order as the marching kernel (THALLO_IW_ITER_MARCH) with the same rows per segment: bit-identical r, p, delta, A p, alpha, beta.
  * Replaces gauss_newton.t:1615-1687 for these shapes. */
 /* rows per wave segment (1..6), or 0: does not fit (the caller runs one launch per PCG iteration).  Host logic, no launch. */
 int  thallo_hip_iw_resident_rows(int W, int rows);
@@ -415,7 +389,7 @@ int  thallo_hip_iw_resident_status(void* xbuf, int clear, int spin_ms, unsigned*
 /* One rank's row slab of a multi-GPU run (local image W x H including its ghost rows, owned rows [row0, row1)): the first / last owned row of A p_k goes
  * straight into the neighbouring ranks' ghost areas -- thallo_hip_iw_resident_ghost_bytes(W) bytes at byte offset ghost_off (a multiple of 16) of EVERY rank's
  * mailbox block, d.peer_mail[rank -+ 1] -- workgroup 0 adds this rank's sums up, exchanges them through the mailbox slots slot0 + 7 k .. (the granules, slots
- * and rank order of thallo_hip_iw_pcg_iter_march_dist: same bits) and publishes alphaD_k / betaN_k for the rest of the chip.  alphaN0: the GLOBAL alphaN_0.
+ * and rank order of the marching kernel's slab form: same bits) and publishes alphaD_k / betaN_k for the rest of the chip.  alphaN0: the GLOBAL alphaN_0.
  * L <= 4095.  The caller has advanced the GN step counter (thallo_hip_dist_begin_step).  thallo_hip_iw_resident_rows_slab: rows per segment for such a slab
  * (below != 0: a rank below -- the last segment must then be a full one), 0 = does not fit. */
 int  thallo_hip_iw_resident_rows_slab(int W, int rows, int below);
@@ -425,7 +399,7 @@ int  thallo_hip_iw_pcg_resident_dist(int W, int H, int row0, int row1, const flo
                                      thallo_sum_t alphaN0, float* words, const int* irregular, void* xbuf, thallo_dist_t d, long ghost_off, int slot0, int L, thallo_stream_t stream);
 void thallo_hip_resident_debug_set(int what, int value);    /* tools / tests only: 0 rows per wave segment, 1 workgroup budget, 2 fault injection (one workgroup withholds its sums of iteration 2), 3 the waits' bound in ms for the next launches (-1: leave) */
 /* rows per wave segment the marching kernels use on `rows` owned rows of a W-wide image; 0 = more column strips than the device has workgroup
- * slots: the marching entry points return -hipErrorNotSupported, the caller stays on thallo_hip_iw_pcg_iter (host logic, no launch) */
+ * slots: the marching kernels return -hipErrorNotSupported, the caller stays on THALLO_IW_ITER_TILE (host logic, no launch) */
 int thallo_hip_iw_march_rows(int W, int rows);
 int thallo_hip_iw_pcg_iter_finish(const float* alphaD_partials, const double* s12_partials, int count, thallo_sum_t alphaN,
                                   float* alphaD_word, float* betaN_word, thallo_stream_t stream);
@@ -882,7 +856,7 @@ int thallo_hip_jtj_scatter(long rows, int K, const float* val, const int* dest, 
  * [0, npix).  count: ptr[0 .. npix] (device) becomes the CSR row pointer of the lists (an instance counts once per distinct owner), *total_dev (device, 8 bytes) their
  * total length.  fill: els[ptr[px] .. ptr[px + 1]) = the instances of owner px in ascending order; cursor: npix ints of scratch.  K <= THALLO_HIP_INC_MAX_SLOTS. */
 #define THALLO_HIP_INC_MAX_SLOTS 48
-/* Measurement (the library's per-kernel timer, bench.py's roofline figure): arm -- the NEXT marching PCG iteration this thread launches (thallo_hip_iw_pcg_iter_march_rc*)
+/* Measurement (the library's per-kernel timer, bench.py's roofline figure): arm -- the NEXT marching PCG iteration this thread launches (THALLO_IW_ITER_MARCH_RC)
  * carries the two events as hipExtLaunchKernelGGL's start / stop events, i.e. they take the kernel's own begin / end timestamps (what rocprofv3 reports as its duration;
  * events recorded around a launch also contain the dispatch gap in front of it).  take -- disarm; 1 if a launch used them (then, and only then, they are recorded). */
 void thallo_hip_launch_events_arm(void* start_event, void* stop_event);
@@ -943,7 +917,7 @@ int thallo_hip_dist_begin_step(thallo_dist_t d, thallo_stream_t stream);
    their granule) ahead of every later read. */
 int thallo_hip_dist_exchange(thallo_dist_t d, int slot, thallo_sum_t local, float* out, thallo_stream_t stream);
 /* The exchange of the one-kernel-per-iteration schedule: local fixed-order sums of the alphaD partials (float) and of the N, S1, S2
-   partials (double) of thallo_hip_iw_pcg_iter(_dist), 7 granules to every rank (slots slot0 .. slot0+6), bounded wait, rank-ordered
+   partials (double) of thallo_hip_iw_pcg_iter, 7 granules to every rank (slots slot0 .. slot0+6), bounded wait, rank-ordered
    sums, then alphaD_word[0] = alphaD_k and betaN_word[0] = N - 2 alpha_k S1 + alpha_k^2 S2 with alpha_k = alphaN / alphaD_k
    (alphaN: a one-word sum).  ONE exchange per PCG iteration. */
 int thallo_hip_dist_exchange_iter(thallo_dist_t d, int slot0, const float* alphaD_partials, const double* s12_partials, int count, thallo_sum_t alphaN,

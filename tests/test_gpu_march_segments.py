@@ -222,3 +222,39 @@ def test_slabs_at_depth_4_agree_across_transports_and_with_a_float64_pcg(torch, 
         dev = _deviation(W, H, p, off, ang, trace, ref, rows=(g0, g1))
         print(f"MARCHREF slab {W}x{H} counts={counts} R={R} rank {rank}: oracle {_fmt(dev_orc)} | tile {_fmt(dev_tile)} | march {_fmt(dev)}")
         assert all(d <= bar for d, bar in zip(dev, BARS)), (rank, dev, BARS)
+
+
+# ------------------------------------------------------------------ the slab iteration whose last workgroup is the exchange
+def _slab_worker_budget(rank, world, port, W, H, lit, q, rows, counts, cap):
+    """_slab_worker on the device-side transport with the marching kernels' workgroup budget forced to `cap` (0: the device's)"""
+    import torch  # noqa: F401  (before libThallo.so: the HIP runtime torch ships must be the one that gets loaded)
+    thallo_amd.lib().thallo_hip_march_debug_set(6, cap)
+    _slab_worker(rank, world, port, W, H, lit, q, True, rows, counts)
+
+
+def test_launch_end_exchange_of_the_recomputing_kernel_is_bitwise_the_deferred_cross_rank_finish(torch):
+    """The recomputing kernel on a slab with the scalar exchange at the END of its launch (tickets, the last workgroup trades the sums) is what a rank runs
+    where the deferred cross-rank finish does not fit the device; every other slab test here fits, so a budget of 8 workgroups is forced: the launch of 8 workgroups
+    plus the deferred form's 8 extra ones no longer fits, thallo_hip_iw_march_rc_deferred_fits says 0 on every rank.  One GN step on 128 x 32 split 16 + 16 with R = 8
+    (two column strips, two row segments per rank), bit for bit against the same run under the device's own budget -- the deferred finish, which leaves one
+    PCGScalars launch per GN step behind (the finish of the last iteration) where the launch-end exchange leaves none."""
+    import torch.multiprocessing as mp
+    from test_gpu_distributed import _collect, _free_port
+    world, W, counts, R = 2, 128, (16, 16), 8
+    runs = []
+    for cap in (0, 8):
+        ctx = mp.get_context("spawn")
+        q = ctx.Queue()
+        port = _free_port()
+        procs = [ctx.Process(target=_slab_worker_budget, args=(r, world, port, W, sum(counts), LIT, q, R, counts, cap)) for r in range(world)]
+        for p_ in procs:
+            p_.start()
+        runs.append(sorted(_collect(q, procs, world), key=lambda t: t[0]))
+    for ra, rb in zip(*runs):
+        print(f"SLABFORMS rank {ra[0]}: deferred {sorted(ra[9])} | launch end {sorted(rb[9])}")
+        assert ra[6]["exchange"] == "p2p-mailbox" and rb[6]["exchange"] == "p2p-mailbox" and ra[7] == 0 and rb[7] == 0, (ra[6], rb[6])
+        assert ra[9]["PCGIteration"]["launches"] >= LIT and rb[9]["PCGIteration"]["launches"] >= LIT
+        assert "PCGScalars" in ra[9] and "PCGScalars" not in rb[9], (sorted(ra[9]), sorted(rb[9]))
+        assert np.isfinite(ra[1]).all() and len(ra[8]) == LIT
+        assert ra[8] == rb[8] and ra[1] == rb[1]
+        assert (ra[4] == rb[4]).all() and (ra[5] == rb[5]).all()

@@ -39,6 +39,12 @@ def test_model_follows_the_librarys_rows_per_segment(L, cap):
         L.thallo_hip_march_debug_set(6, 0)
 
 
+def test_the_iteration_block_mirror_has_the_librarys_size(L):
+    """api.IwIterT mirrors thallo_iw_iter_t field by field; a field added on one side only changes the size on that side"""
+    from thallo_amd import api
+    assert C.sizeof(api.IwIterT) == L.thallo_hip_iw_iter_size()
+
+
 def test_depth_n_pairs_of_the_automatic_geometry_on_256_cus():
     """what the automatic rows per segment reach on a 256-CU device: the table the forced-R sweep was written against"""
     pairs = mc.depth_n_pairs(SHAPES_BEFORE, cus=256)

@@ -42,6 +42,25 @@ class DistT(C.Structure):
                 ("peer_off_a", C.c_long * 2), ("ctl", C.c_void_p), ("world", C.c_int), ("rank", C.c_int)]
 
 
+class PrevT(C.Structure):     # thallo_prev_t of include/thallo_hip.h
+    _fields_ = [("alphaD_partials", C.c_void_p), ("s12_partials", C.c_void_p), ("count", C.c_int), ("alphaD_word", C.c_void_p), ("betaN_word", C.c_void_p)]
+
+
+class IwIterT(C.Structure):
+    """thallo_iw_iter_t (include/thallo_hip.h): everything a launch of the one-kernel PCG iteration carries.  tests/test_march_classes.py pins
+    its size against thallo_hip_iw_iter_size()."""
+    _fields_ = ([(n, C.c_int) for n in ("W", "H", "row0", "row1")]
+                + [(n, C.c_void_p) for n in ("cs", "urshape", "flags", "pre", "irregular")]
+                + [("w_fit", C.c_float), ("w_reg", C.c_float)]
+                + [(n, C.c_void_p) for n in ("r_in", "r_out", "Ap_in", "Ap_out", "p_in", "p_out", "delta")] + [("mode", C.c_int)]
+                + [(n, SumT) for n in ("alphaN_prev", "alphaD_prev", "betaN_prev", "alphaN_prev2", "alphaD_prev2")]
+                + [(n, C.c_void_p) for n in ("alphaD_out", "s12_out", "fin_tickets", "alphaD_word", "betaN_word")] + [("slot0", C.c_int)]
+                + [("dist", C.POINTER(DistT)), ("prev", C.POINTER(PrevT)), ("prev_slot0", C.c_int), ("gs", C.c_void_p)])
+
+
+IW_ITER_TILE, IW_ITER_MARCH, IW_ITER_MARCH_RC = 0, 1, 2      # THALLO_IW_ITER_* of include/thallo_hip.h
+
+
 class SegsT(C.Structure):     # thallo_segs_t of include/thallo_hip.h
     _fields_ = [("off", C.c_long * 8), ("len", C.c_long * 8), ("n", C.c_int)]
 
@@ -139,12 +158,9 @@ def lib():
     L.thallo_hip_slab_unpack_iter.argtypes = [vp, SegsT, vp, SegsT, vp, vp, cl, ci, SumT, vp, vp, vp]
     L.thallo_hip_dist_exchange.argtypes = [DistT, ci, SumT, vp, vp]
     L.thallo_hip_dist_exchange_iter.argtypes = [DistT, ci, vp, vp, ci, SumT, vp, vp, vp]
-    _iter = [ci, ci, ci, ci, vp, vp, vp, vp, fl, fl, vp, vp, vp, vp, vp, vp, vp, ci, SumT, SumT, SumT, SumT, SumT, vp]
-    L.thallo_hip_iw_pcg_iter.argtypes = _iter + [vp, vp, vp, vp, vp, vp]
-    L.thallo_hip_iw_pcg_iter_dist.argtypes = _iter + [DistT, vp, vp, vp, ci, vp, vp, vp]
-    _march = [ci, ci, ci, ci, vp, vp, fl, fl, vp, vp, vp, vp, vp, vp, vp, ci, SumT, SumT, SumT, SumT, SumT, vp]     # no urshape / pre
-    L.thallo_hip_iw_pcg_iter_march.argtypes = _march + [vp, vp, vp, vp, vp, vp]
-    L.thallo_hip_iw_pcg_iter_march_dist.argtypes = _march + [DistT, vp, vp, vp, ci, vp, vp, vp]
+    L.thallo_hip_iw_pcg_iter.argtypes = [ci, C.POINTER(IwIterT), vp]
+    if hasattr(L, "thallo_hip_iw_iter_size"):      # (THALLO_LIB may name an A/B build from before the block existed)
+        L.thallo_hip_iw_iter_size.argtypes = []; L.thallo_hip_iw_iter_size.restype = C.c_uint
     L.thallo_hip_iw_urshape_irregular.argtypes = [ci, ci, vp, vp, vp]
     L.thallo_hip_march_debug_set.argtypes = [ci, ci]
     L.thallo_hip_iw_pcg_iter_finish.argtypes = [vp, vp, ci, SumT, vp, vp, vp]

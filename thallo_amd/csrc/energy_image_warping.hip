@@ -892,84 +892,40 @@ int thallo_hip_iw_pcg_step2_dist(int W, int H, int row0, int row1, const unsigne
     int e = check_launch(); return e ? e : grid;
 }
 
-int thallo_hip_iw_pcg_iter(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                           float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                           const float* p_in, float* p_out, float* delta, int mode,
-                           thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                           const int* irregular, float* aD_out, double* s12_out,
-                           unsigned* fin_tickets, float* aD_word, float* bN_word, thallo_stream_t stream)
+}  // extern "C"
+
+int thallo::launch_iter(const thallo_iw_iter_t& a, hipStream_t stream)
 {
-    if (!rows_ok(H, row0, row1) || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if (!(mode & 1) && !Ap_in) return -(int)hipErrorInvalidValue;
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    const Geo g = make_geo(W, H, row0, row1);
+    if (!a.Ap_out || (!(a.mode & 1) && !a.Ap_in)) return -(int)hipErrorInvalidValue;
+    if (a.dist && a.gs) return -(int)hipErrorNotSupported;      // (the deferred cross-rank finish: the recomputing kernel only)
+    const IterForm f(a);
+    const Geo g = make_geo(a.W, a.H, a.row0, a.row1);
     const int grid = grid_for(g, g_iter_per_cu);
+#define ITER_LAUNCH(MINW, DIST) hipLaunchKernelGGL((k_iter<MINW, 512, DIST>), dim3(grid), dim3(512), 0, stream, g, (const float2*)a.cs, (const float2*)a.urshape, a.flags, a.pre, \
+        a.w_fit * a.w_fit, a.w_reg * a.w_reg, a.r_in, a.r_out, a.Ap_in, a.Ap_out, a.p_in, a.p_out, a.delta, a.mode, a.alphaN_prev, f.aDp, f.bNp, a.alphaN_prev2, a.alphaD_prev2, \
+        a.alphaD_out, a.s12_out, g_iter_nt, g_no_grid ? nullptr : a.irregular, f.d, f.tickets, f.aD_word, f.bN_word, f.xslot, f.prev)
     // two register budgets of the same kernel: up to one workgroup per CU (every image the plugin sends here by default: < 0.4 Mpixel) the
     // 139 registers it wants, no scratch; beyond that the 128-register build -- two workgroups per CU, 28 B/lane of scratch -- is 30 % faster
     // (2048^2 with an irregular UrShape: 9.0 vs 11.8 ms per GN step)
-    if (grid <= thallo_hip_device_cu_count())
-        hipLaunchKernelGGL((k_iter<3, 512, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, thallo_dist_t{}, fin_tickets, aD_word, bN_word, 0, PrevSums{ nullptr, nullptr, 0, nullptr, nullptr });
-    else
-        hipLaunchKernelGGL((k_iter<4, 512, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, thallo_dist_t{}, fin_tickets, aD_word, bN_word, 0, PrevSums{ nullptr, nullptr, 0, nullptr, nullptr });
+    const bool roomy = grid <= thallo_hip_device_cu_count();
+    if (!a.dist) { if (roomy) ITER_LAUNCH(3, false); else ITER_LAUNCH(4, false); }
+    else         { if (roomy) ITER_LAUNCH(3, true); else ITER_LAUNCH(4, true); }
+#undef ITER_LAUNCH
     int e = check_launch(); return e ? e : grid;
 }
 
-int thallo_hip_iw_pcg_iter_deferred(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                                    float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                    const float* p_in, float* p_out, float* delta, int mode,
-                                    thallo_sum_t aNp, thallo_sum_t aNpp, thallo_sum_t aDpp, thallo_prev_t prev,
-                                    const int* irregular, float* aD_out, double* s12_out, thallo_stream_t stream)
-{
-    if (!rows_ok(H, row0, row1) || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if (!(mode & 1) && (!Ap_in || prev.count < 1 || prev.count > THALLO_MAX_PARTIALS || !prev.alphaD_partials || !prev.s12_partials || !prev.alphaD_word || !prev.betaN_word ||
-                        prev.s12_partials == s12_out)) return -(int)hipErrorInvalidValue;
-    const Geo g = make_geo(W, H, row0, row1);
-    const int grid = grid_for(g, g_iter_per_cu);
-    const thallo_sum_t none = { nullptr, 0 };
-    const PrevSums ps = (mode & 1) ? PrevSums{ nullptr, nullptr, 0, nullptr, nullptr } : PrevSums{ prev.alphaD_partials, prev.s12_partials, prev.count, prev.alphaD_word, prev.betaN_word };
-    // two register budgets of the same kernel: up to one workgroup per CU (every image the plugin sends here by default: < 0.4 Mpixel) the
-    // 139 registers it wants, no scratch; beyond that the 128-register build -- two workgroups per CU, 28 B/lane of scratch -- is 30 % faster
-    // (2048^2 with an irregular UrShape: 9.0 vs 11.8 ms per GN step)
-    if (grid <= thallo_hip_device_cu_count())
-        hipLaunchKernelGGL((k_iter<3, 512, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, none, none, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, thallo_dist_t{}, nullptr, nullptr, nullptr, 0, ps);
-    else
-        hipLaunchKernelGGL((k_iter<4, 512, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, none, none, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, thallo_dist_t{}, nullptr, nullptr, nullptr, 0, ps);
-    int e = check_launch(); return e ? e : grid;
-}
+extern "C" {
 
-int thallo_hip_iw_pcg_iter_dist(int W, int H, int row0, int row1, const float* cs, const float* urshape, const unsigned char* flags, const float* pre,
-                                float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                const float* p_in, float* p_out, float* delta, int mode,
-                                thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                                const int* irregular, thallo_dist_t d, float* aD_out, double* s12_out,
-                                unsigned* fin_tickets, int slot0, float* aD_word, float* bN_word, thallo_stream_t stream)
+unsigned thallo_hip_iw_iter_size(void) { return (unsigned)sizeof(thallo_iw_iter_t); }
+
+int thallo_hip_iw_pcg_iter(int kernel, const thallo_iw_iter_t* a, thallo_stream_t stream)
 {
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    if (fin_tickets && (slot0 < 0 || !d.mail || !d.ctl || 7 * d.world > 64 || bNp.count != 1)) return -(int)hipErrorInvalidValue;
-    if (!rows_ok(H, row0, row1) || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if ((!(mode & 1) && !Ap_in) || d.world < 1 || d.world > THALLO_DIST_MAX_WORLD) return -(int)hipErrorInvalidValue;
-    const Geo g = make_geo(W, H, row0, row1);
-    const int grid = grid_for(g, g_iter_per_cu);
-    // two register budgets of the same kernel: up to one workgroup per CU (every image the plugin sends here by default: < 0.4 Mpixel) the
-    // 139 registers it wants, no scratch; beyond that the 128-register build -- two workgroups per CU, 28 B/lane of scratch -- is 30 % faster
-    // (2048^2 with an irregular UrShape: 9.0 vs 11.8 ms per GN step)
-    if (grid <= thallo_hip_device_cu_count())
-        hipLaunchKernelGGL((k_iter<3, 512, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, d, fin_tickets, aD_word, bN_word, slot0, PrevSums{ nullptr, nullptr, 0, nullptr, nullptr });
-    else
-        hipLaunchKernelGGL((k_iter<4, 512, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, g, (const float2*)cs, (const float2*)urshape, flags, pre,
-                       w_fit * w_fit, w_reg * w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp,
-                       aD_out, s12_out, g_iter_nt, g_no_grid ? nullptr : irregular, d, fin_tickets, aD_word, bN_word, slot0, PrevSums{ nullptr, nullptr, 0, nullptr, nullptr });
-    int e = check_launch(); return e ? e : grid;
+    if (!a) return -(int)hipErrorInvalidValue;
+    if (int e = iw_iter_check(*a)) return e;
+    if (kernel == THALLO_IW_ITER_TILE) return launch_iter(*a, (hipStream_t)stream);
+    if (kernel == THALLO_IW_ITER_MARCH) return launch_march(*a, (hipStream_t)stream);
+    if (kernel == THALLO_IW_ITER_MARCH_RC) return launch_march_rc(*a, (hipStream_t)stream);
+    return -(int)hipErrorInvalidValue;
 }
 
 int thallo_hip_iw_pcg_iter_finish(const float* aD_partials, const double* s12_partials, int count, thallo_sum_t alphaN,

@@ -429,26 +429,25 @@ struct LaunchEvents { hipEvent_t start = nullptr, stop = nullptr; int armed = 0,
 thread_local LaunchEvents g_launch_ev;
 
 template <int SLAB>
-int launch_march_rc(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                    const float* r_in, float* r_out, const float* A_in, float* A_out, const float* p_in, float* p_out, float* delta, int mode,
-                    thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp, const int* irregular, thallo_dist_t d,
-                    float* aD_out, double* s12_out, unsigned* fin_tickets, float* aD_word, float* bN_word, int xslot, hipStream_t stream, PrevSums prev)
+int launch_march_rc_as(const thallo_iw_iter_t& a, hipStream_t stream)
 {
-    const int R = march_pick_rows(W, row1 - row0);
+    const IterForm f(a);
+    const float *A_in = SLAB ? a.Ap_in : nullptr; float* A_out = SLAB ? a.Ap_out : nullptr;      // (whole images: the A p planes are not touched)
+    const int R = march_pick_rows(a.W, a.row1 - a.row0);
     if (R <= 0) return -(int)hipErrorNotSupported;
-    const MarchGeo g = make_march_geo(W, H, row0, row1, R);
-    const int grid = (g.total + 7) / 8 * 8 + ((SLAB == 2 && prev.gs != nullptr) ? 8 : 0);      // (deferred cross-rank finish: eight workgroups without rows; wave 0 of the last one is the exchange)
+    const MarchGeo g = make_march_geo(a.W, a.H, a.row0, a.row1, R);
+    const int grid = (g.total + 7) / 8 * 8 + ((SLAB == 2 && f.prev.gs != nullptr) ? 8 : 0);      // (deferred cross-rank finish: eight workgroups without rows; wave 0 of the last one is the exchange)
     if (grid > THALLO_MAX_PARTIALS) return -(int)hipErrorInvalidValue;
-    const int dmode = (mode >> 1) & 3;
-    const float wf2 = w_fit * w_fit, wr2 = w_reg * w_reg;
+    const int dmode = (a.mode >> 1) & 3;
+    const float wf2 = a.w_fit * a.w_fit, wr2 = a.w_reg * a.w_reg;
     // (g_launch_ev armed -- the library's kernel timer sampling this launch, bench.py's roofline figure -- : the launch carries two events that take the kernel's OWN
     //  begin / end timestamps, what rocprofv3 reports as its duration; events recorded around the launch also contain the dispatch gap in front of it)
     const bool ev_on = g_launch_ev.armed != 0;
     if (ev_on) g_launch_ev.used = 1;
-#define RC_LAUNCH(DM, DP, OCC, NTM) do { if (ev_on) hipExtLaunchKernelGGL((k_iter_march_rc<DM, DP, NTM, OCC, SLAB>), dim3(grid), dim3(MARCH_NT), 0, stream, g_launch_ev.start, g_launch_ev.stop, 0, g, cs, flags, wf2, wr2, \
-        r_in, r_out, A_in, A_out, p_in, p_out, delta, aNp, aDp, bNp, aNpp, aDpp, aD_out, s12_out, irregular, d, fin_tickets, aD_word, bN_word, xslot, prev); \
-    else hipLaunchKernelGGL((k_iter_march_rc<DM, DP, NTM, OCC, SLAB>), dim3(grid), dim3(MARCH_NT), 0, stream, g, cs, flags, wf2, wr2, \
-        r_in, r_out, A_in, A_out, p_in, p_out, delta, aNp, aDp, bNp, aNpp, aDpp, aD_out, s12_out, irregular, d, fin_tickets, aD_word, bN_word, xslot, prev); } while (0)
+#define RC_ARGS g, a.cs, a.flags, wf2, wr2, a.r_in, a.r_out, A_in, A_out, a.p_in, a.p_out, a.delta, a.alphaN_prev, f.aDp, f.bNp, a.alphaN_prev2, a.alphaD_prev2, \
+        a.alphaD_out, a.s12_out, a.irregular, f.d, f.tickets, f.aD_word, f.bN_word, f.xslot, f.prev
+#define RC_LAUNCH(DM, DP, OCC, NTM) do { if (ev_on) hipExtLaunchKernelGGL((k_iter_march_rc<DM, DP, NTM, OCC, SLAB>), dim3(grid), dim3(MARCH_NT), 0, stream, g_launch_ev.start, g_launch_ev.stop, 0, RC_ARGS); \
+    else hipLaunchKernelGGL((k_iter_march_rc<DM, DP, NTM, OCC, SLAB>), dim3(grid), dim3(MARCH_NT), 0, stream, RC_ARGS); } while (0)
 #ifdef THALLO_MARCH_SWEEP      // tools/rc_probe.py: prefetch depth x register budget at the product's cache policy, and the cache-policy masks at the product's depth / budget
 #define RC_BY_DEPTH(DM) do { if constexpr (SLAB != 0) RC_LAUNCH(DM, MARCH_RC_DEPTH, MARCH_RC_OCC, MARCH_NTM); else { const int dp = g_march_rc_depth, oc = g_march_rc_occ, nt = g_march_rc_nt; \
         if (nt != MARCH_NTM) { if (nt == 0) RC_LAUNCH(DM, MARCH_RC_DEPTH, 2, 0); else if (nt == 1) RC_LAUNCH(DM, MARCH_RC_DEPTH, 2, 1); else if (nt == 4) RC_LAUNCH(DM, MARCH_RC_DEPTH, 2, 4); else if (nt == 7) RC_LAUNCH(DM, MARCH_RC_DEPTH, 2, 7); \
@@ -462,78 +461,34 @@ int launch_march_rc(int W, int H, int row0, int row1, const float* cs, const uns
     if (dmode == 1) RC_BY_DEPTH(1); else if (dmode == 2) RC_BY_DEPTH(2); else RC_BY_DEPTH(0);
 #undef RC_BY_DEPTH
 #undef RC_LAUNCH
+#undef RC_ARGS
     int e = check_launch(); return e ? e : grid;
 }
 
-// what every entry checks: the shape (a whole image, or a slab with at most one ghost row towards each neighbour), the planes, the sums this iteration starts from
-int rc_check(int W, int H, int row0, int row1, const void* cs, const void* flags, const void* r_in, const void* r_out, const void* A_in, const void* A_out,
-             const void* p_in, const void* p_out, const void* delta, int mode, thallo_sum_t aNp, thallo_sum_t aNpp, thallo_sum_t aDpp, const void* aD_out, const void* s12_out)
-{
-    if ((W & 1) || W < 2 || H < 1 || row0 < 0 || row1 > H || row0 >= row1 || row0 > 1 || H - row1 > 1) return -(int)hipErrorInvalidValue;
-    if (mode & 1) return -(int)hipErrorInvalidValue;          // (the first iteration of a GN step has no A p_{k-1}: the stored-plane kernel runs it)
-    if (!cs || !flags || !r_in || !r_out || !p_in || !p_out || !delta || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if ((row0 > 0 || row1 < H) && (!A_in || !A_out)) return -(int)hipErrorInvalidValue;          // slabs: the exchanged rows of A p
-    if (aNp.count < 1 || !aNp.partials) return -(int)hipErrorInvalidValue;
-    if (((mode >> 1) & 3) == 2 && (aNpp.count < 1 || aDpp.count < 1 || !aNpp.partials || !aDpp.partials)) return -(int)hipErrorInvalidValue;
-    if (12.0 * (double)W * (double)H >= 4294967296.0) return -(int)hipErrorNotSupported;       // a vector must fit one buffer descriptor
-    return 0;
-}
 }  // namespace
+
+// the recomputing kernel's own conditions on a block: an even width, a whole image or a slab with at most one ghost row towards each neighbour, never a GN step's
+// first iteration, the exchanged rows of A p on a slab, the sums the iteration starts from, a vector within one buffer descriptor
+int thallo::launch_march_rc(const thallo_iw_iter_t& a, hipStream_t stream)
+{
+    const bool whole = a.row0 == 0 && a.row1 == a.H;
+    const int dmode = (a.mode >> 1) & 3;
+    const auto given = [](const thallo_sum_t& s) { return s.count >= 1 && s.partials; };
+    if ((a.W & 1) || a.W < 2 || a.row0 > 1 || a.H - a.row1 > 1) return -(int)hipErrorInvalidValue;
+    if (a.mode & 1) return -(int)hipErrorInvalidValue;          // (the first iteration of a GN step has no A p_{k-1}: the stored-plane kernel runs it)
+    if ((!whole || a.dist) && (!a.Ap_in || !a.Ap_out)) return -(int)hipErrorInvalidValue;          // slabs: the exchanged rows of A p
+    if (!given(a.alphaN_prev) || (!a.prev && (!given(a.alphaD_prev) || !given(a.betaN_prev)))) return -(int)hipErrorInvalidValue;
+    if (dmode == 2 && (!given(a.alphaN_prev2) || !given(a.alphaD_prev2))) return -(int)hipErrorInvalidValue;
+    if (12.0 * (double)a.W * (double)a.H >= 4294967296.0) return -(int)hipErrorNotSupported;       // a vector must fit one buffer descriptor
+    if (a.dist && a.gs && !thallo_hip_iw_march_rc_deferred_fits(a.W, a.row1 - a.row0)) return -(int)hipErrorNotSupported;      // (its waits need every workgroup resident)
+    return !a.dist ? (whole ? launch_march_rc_as<0>(a, stream) : launch_march_rc_as<1>(a, stream)) : launch_march_rc_as<2>(a, stream);
+}
 
 extern "C" {
 
-int thallo_hip_iw_pcg_iter_march_rc(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                    const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                    thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                                    const int* irregular, float* aD_out, double* s12_out,
-                                    unsigned* fin_tickets, float* aD_word, float* bN_word, thallo_stream_t stream)
-{
-    if (int e = rc_check(W, H, row0, row1, cs, flags, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aNpp, aDpp, aD_out, s12_out)) return e;
-    if (aDp.count < 1 || bNp.count < 1 || !aDp.partials || !bNp.partials) return -(int)hipErrorInvalidValue;
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    const PrevSums none = { nullptr, nullptr, 0, nullptr, nullptr };
-    if (row0 == 0 && row1 == H)
-        return launch_march_rc<0>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, nullptr, nullptr, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp, irregular, thallo_dist_t{},
-                                  aD_out, s12_out, fin_tickets, aD_word, bN_word, 0, (hipStream_t)stream, none);
-    return launch_march_rc<1>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp, irregular, thallo_dist_t{},
-                              aD_out, s12_out, fin_tickets, aD_word, bN_word, 0, (hipStream_t)stream, none);
-}
-
-int thallo_hip_iw_pcg_iter_march_rc_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                             const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                             thallo_sum_t aNp, thallo_sum_t aNpp, thallo_sum_t aDpp, thallo_prev_t prev,
-                                             const int* irregular, float* aD_out, double* s12_out, thallo_stream_t stream)
-{
-    if (int e = rc_check(W, H, row0, row1, cs, flags, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aNpp, aDpp, aD_out, s12_out)) return e;
-    if (prev.count < 1 || prev.count > THALLO_MAX_PARTIALS || !prev.alphaD_partials || !prev.s12_partials || !prev.alphaD_word || !prev.betaN_word ||
-        prev.s12_partials == s12_out) return -(int)hipErrorInvalidValue;
-    const thallo_sum_t none = { nullptr, 0 };
-    const PrevSums ps = { prev.alphaD_partials, prev.s12_partials, prev.count, prev.alphaD_word, prev.betaN_word };
-    if (row0 == 0 && row1 == H)
-        return launch_march_rc<0>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, nullptr, nullptr, p_in, p_out, delta, mode, aNp, none, none, aNpp, aDpp, irregular, thallo_dist_t{},
-                                  aD_out, s12_out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, ps);
-    return launch_march_rc<1>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, none, none, aNpp, aDpp, irregular, thallo_dist_t{},
-                              aD_out, s12_out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, ps);
-}
-
-int thallo_hip_iw_pcg_iter_march_rc_dist(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                         const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                         thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                                         const int* irregular, thallo_dist_t d, float* aD_out, double* s12_out,
-                                         unsigned* fin_tickets, int slot0, float* aD_word, float* bN_word, thallo_stream_t stream)
-{
-    if (int e = rc_check(W, H, row0, row1, cs, flags, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aNpp, aDpp, aD_out, s12_out)) return e;
-    if (!Ap_in || !Ap_out || aDp.count < 1 || bNp.count < 1 || !aDp.partials || !bNp.partials || d.world < 1 || d.world > THALLO_DIST_MAX_WORLD) return -(int)hipErrorInvalidValue;
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    if (fin_tickets && (slot0 < 0 || !d.mail || !d.ctl || 7 * d.world > 64 || bNp.count != 1)) return -(int)hipErrorInvalidValue;
-    for (int k = 0; k < 2; ++k) if (d.peer_r[k] && ((d.peer_off_o[k] | d.peer_off_a[k]) & 1)) return -(int)hipErrorInvalidValue;
-    return launch_march_rc<2>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aDp, bNp, aNpp, aDpp, irregular, d,
-                              aD_out, s12_out, fin_tickets, aD_word, bN_word, slot0, (hipStream_t)stream, PrevSums{ nullptr, nullptr, 0, nullptr, nullptr });
-}
-
 /* The deferred cross-rank finish makes every working wave wait for granules that wave 0 of the launch's LAST workgroup publishes: the whole grid (its eight extra
  * workgroups included) must be resident at once -- the kernel is built for MARCH_RC_OCC workgroups per CU, while march_pick_rows may size a wide slab's grid for up to
- * four.  1: it is; 0: run the launch-end exchange (thallo_hip_iw_pcg_iter_march_rc_dist), which has no such requirement. */
+ * four.  1: it is; 0: run the launch-end exchange (the block's gs left NULL), which has no such requirement. */
 int thallo_hip_iw_march_rc_deferred_fits(int W, int rows)
 {
     if (W < 2 || (W & 1) || rows < 1) return 0;
@@ -544,23 +499,6 @@ int thallo_hip_iw_march_rc_deferred_fits(int W, int rows)
     return grid <= march_cap(MARCH_RC_OCC) && grid <= THALLO_MAX_PARTIALS ? 1 : 0;
 }
 
-/* ... with the deferred cross-rank finish (thallo_hip.h): `prev` = iteration k-1's partials of THIS rank, its two words, and where the exchange happens */
-int thallo_hip_iw_pcg_iter_march_rc_dist_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                                                  const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                                                  thallo_sum_t aNp, thallo_sum_t aNpp, thallo_sum_t aDpp, thallo_prev_t prev, int prev_slot0, unsigned long long* gs,
-                                                  const int* irregular, thallo_dist_t d, float* aD_out, double* s12_out, thallo_stream_t stream)
-{
-    if (int e = rc_check(W, H, row0, row1, cs, flags, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, aNpp, aDpp, aD_out, s12_out)) return e;
-    if (!Ap_in || !Ap_out || d.world < 1 || d.world > THALLO_DIST_MAX_WORLD || !d.mail || !d.ctl || 7 * d.world > 64 || prev_slot0 < 0 || !gs || aNp.count != 1) return -(int)hipErrorInvalidValue;
-    if (!thallo_hip_iw_march_rc_deferred_fits(W, row1 - row0)) return -(int)hipErrorNotSupported;      // (its waits need every workgroup resident)
-    if (prev.count < 1 || prev.count > THALLO_MAX_PARTIALS || !prev.alphaD_partials || !prev.s12_partials || !prev.alphaD_word || !prev.betaN_word ||
-        prev.s12_partials == s12_out) return -(int)hipErrorInvalidValue;
-    for (int k = 0; k < 2; ++k) if (d.peer_r[k] && ((d.peer_off_o[k] | d.peer_off_a[k]) & 1)) return -(int)hipErrorInvalidValue;
-    const thallo_sum_t none = { nullptr, 0 };
-    const PrevSums ps = { prev.alphaD_partials, prev.s12_partials, prev.count, prev.alphaD_word, prev.betaN_word, gs, prev_slot0 };
-    return launch_march_rc<2>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode, aNp, none, none, aNpp, aDpp, irregular, d,
-                              aD_out, s12_out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, ps);
-}
 int thallo_hip_iw_dist_finish_deferred(thallo_prev_t prev, int prev_slot0, thallo_sum_t aNp, thallo_dist_t d, unsigned long long* gs, thallo_stream_t stream)
 {
     if (prev.count < 1 || prev.count > THALLO_MAX_PARTIALS || !prev.alphaD_partials || !prev.s12_partials || !prev.alphaD_word || !prev.betaN_word || prev_slot0 < 0 || !gs ||

@@ -774,7 +774,7 @@ long thallo_hip_iw_resident_bytes(int W, int rows)
 long thallo_hip_iw_resident_ghost_bytes(int W) { return W < 2 ? 0 : 2L * ((W + RES_USE - 1) / RES_USE) * 2 * 64 * 48; }
 
 /* The PCG loop of one Gauss-Newton step in one launch: L iterations from what thallo_hip_iw_pcg_init left (r_0 in r_in, zeros in p_in and delta, cs / flags,
- * alphaN_0), leaving what L launches of thallo_hip_iw_pcg_iter_march leave: r_{L-1}, A p_{L-1}, p_{L-1} in the *_out planes, delta without its last term, and
+ * alphaN_0), leaving what L launches of the marching kernel (THALLO_IW_ITER_MARCH) leave: r_{L-1}, A p_{L-1}, p_{L-1} in the *_out planes, delta without its last term, and
  * words[2k] = alphaD_k, words[2k + 1] = betaN_k; with X_offset / X_angle (round 6) PCGLinearUpdate rides along: X += delta + alpha_{L-1} p_{L-1}, thallo_hip_linear_update's
  * bits.  The *_out planes may be the *_in planes (every workgroup has read its rows and halo before any workgroup can
  * be through its L iterations: each iteration needs every workgroup's sums).  xbuf: thallo_hip_iw_resident_bytes() bytes, zeroed once by the caller, private to the plan.
@@ -801,7 +801,7 @@ int thallo_hip_iw_pcg_resident(int W, int H, int row0, int row1, const float* cs
 /* The same for ONE RANK's row slab of a multi-GPU run (local image W x H with its ghost rows, owned rows [row0, row1)): the first / last owned row of A p_k
  * goes straight into the neighbouring ranks' ghost areas (d.peer_mail[rank -+ 1] + ghost_off bytes: thallo_hip_iw_resident_ghost_bytes() bytes behind the scalar
  * granules of every rank's mailbox block), workgroup 0 adds this rank's sums up, exchanges them with the other ranks through the mailbox slots slot0 + 7 k ..
- * (the granules, slots and rank order of thallo_hip_iw_pcg_iter_march_dist: same bits) and publishes alphaD_k / betaN_k for the rest of the chip.  alphaN0: the
+ * (the granules, slots and rank order of the marching kernel's slab form: same bits) and publishes alphaD_k / betaN_k for the rest of the chip.  alphaN0: the
  * global alphaN_0 (one word).  L <= 4095.  The caller has advanced the GN step counter (thallo_hip_dist_begin_step). */
 int thallo_hip_iw_pcg_resident_dist(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
                                     const float* r_in, const float* p_in, float* r_out, float* Ap_out, float* p_out, float* delta,

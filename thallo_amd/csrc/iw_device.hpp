@@ -148,4 +148,55 @@ __device__ __forceinline__ void iter_tail(float acc, double s0, double s1, doubl
     }
 }
 
+// ---- host side of the one-kernel PCG iteration: thallo_hip_iw_pcg_iter (energy_image_warping.hip) checks the block once and hands it to the kernel's launch
+
+// What every kernel and form asks of a block: owned rows inside the image, the planes every kernel touches, delta unless the launch is a GN step's first, a
+// well-formed `prev`, a world within bounds and -- where a wave of the launch exchanges scalars -- its mailbox, even peer offsets, and a form that exists.
+// Tickets: all three or none (IterForm below).  Each launch function adds its kernel's own conditions.
+inline int iw_iter_check(const thallo_iw_iter_t& a)
+{
+    const int bad = -(int)hipErrorInvalidValue;
+    if (a.row0 < 0 || a.row1 > a.H || a.row0 >= a.row1) return bad;
+    if (!a.cs || !a.flags || !a.r_in || !a.r_out || !a.p_in || !a.p_out || !a.alphaD_out || !a.s12_out) return bad;
+    if (!(a.mode & 1) && !a.delta) return bad;
+    if (a.prev && !(a.mode & 1)) {
+        const thallo_prev_t& p = *a.prev;
+        if (p.count < 1 || p.count > THALLO_MAX_PARTIALS || !p.alphaD_partials || !p.s12_partials || !p.alphaD_word || !p.betaN_word || p.s12_partials == a.s12_out) return bad;
+    }
+    if (a.dist) {
+        const thallo_dist_t& d = *a.dist;
+        const bool fin = !a.prev && a.fin_tickets && a.alphaD_word && a.betaN_word;
+        if (d.world < 1 || d.world > THALLO_DIST_MAX_WORLD) return bad;
+        if ((fin || a.gs) && (!d.mail || !d.ctl || 7 * d.world > 64)) return bad;
+        if (fin && (a.slot0 < 0 || a.betaN_prev.count != 1)) return bad;
+        if (a.gs && (!a.prev || a.prev_slot0 < 0 || a.alphaN_prev.count != 1)) return bad;
+        for (int k = 0; k < 2; ++k) if (d.peer_r[k] && ((d.peer_off_o[k] | d.peer_off_a[k]) & 1)) return bad;
+        if (a.prev && !a.gs) return -(int)hipErrorNotSupported;      // (no kernel finishes a rank's own sums ahead of a launch-end exchange)
+    }
+    return 0;
+}
+
+// What a k_iter* launch hands its kernel behind the planes, derived from the block's form in one place: the deferred forms start from `prev` instead of the
+// two finished words and carry no tickets; only a slab launch has a peer block and mailbox slots.
+struct IterForm {
+    thallo_sum_t aDp, bNp; thallo_dist_t d; unsigned* tickets; float *aD_word, *bN_word; int xslot; PrevSums prev;
+    explicit IterForm(const thallo_iw_iter_t& a)
+    {
+        const thallo_sum_t none = { nullptr, 0 };
+        const bool fin = !a.prev && a.fin_tickets && a.alphaD_word && a.betaN_word;
+        aDp = a.prev ? none : a.alphaD_prev; bNp = a.prev ? none : a.betaN_prev;
+        d = a.dist ? *a.dist : thallo_dist_t{};
+        tickets = fin ? a.fin_tickets : nullptr; aD_word = fin ? a.alphaD_word : nullptr; bN_word = fin ? a.betaN_word : nullptr;
+        xslot = a.dist && !a.prev ? a.slot0 : 0;
+        prev = PrevSums{ nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0 };
+        if (a.prev && !(a.mode & 1)) prev = PrevSums{ a.prev->alphaD_partials, a.prev->s12_partials, a.prev->count, a.prev->alphaD_word, a.prev->betaN_word,
+                                                      a.dist ? a.gs : nullptr, a.dist ? a.prev_slot0 : 0 };
+    }
+};
+
+// one per kernel file (the sweep build's probe/march_probe_kernels.hip defines launch_march in the product file's place); the block has passed iw_iter_check
+int launch_iter(const thallo_iw_iter_t& a, hipStream_t stream);
+int launch_march(const thallo_iw_iter_t& a, hipStream_t stream);
+int launch_march_rc(const thallo_iw_iter_t& a, hipStream_t stream);
+
 }  // namespace thallo

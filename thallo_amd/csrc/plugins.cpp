@@ -192,7 +192,7 @@ public:
     }
     int prepare(LaunchCtx& c) override
     {   // UrShape is a constant input: establish once per Init, on the host, whether it is the unit pixel grid (what the reference's
-        // harness passes, CombinedSolver.h:158-176) -- that selects thallo_hip_iw_pcg_iter_march; pcg_init still re-verifies on the device
+        // harness passes, CombinedSolver.h:158-176) -- that selects the marching kernels of thallo_hip_iw_pcg_iter; pcg_init still re-verifies on the device
         march_ = grid_ = march_rc_ = false;
         const char* e = env_switch("THALLO_MARCH");
         int* word = (int*)irregular.ptr + 8;
@@ -243,34 +243,44 @@ public:
     int slab_width() const override { return W; }
     bool slab_grid_ok() const override { return grid_; }
     unsigned char* slab_flags() override { return (unsigned char*)flags.ptr; }
+private:
+    // The one-kernel PCG iteration (thallo_hip_iw_pcg_iter): the block every form starts from -- this plan's planes and weights, the ping-pong planes of `cur`,
+    // the sums and where the partials go -- and the kernel that runs it.  The callers below add their form's fields.
+    thallo_iw_iter_t iter_block(SolverVectors& v, int cur, int mode, thallo_sum_t aN, thallo_sum_t aD, thallo_sum_t bN, thallo_sum_t aN2, thallo_sum_t aD2, float* out, double* s12_out) const
+    {
+        thallo_iw_iter_t a = {};
+        a.W = W; a.H = H; a.row0 = row0_; a.row1 = row1_;
+        a.cs = (const float*)cs.ptr; a.urshape = urshape; a.flags = (const unsigned char*)flags.ptr; a.pre = v.pre; a.irregular = (const int*)irregular.ptr;
+        a.w_fit = w_fit; a.w_reg = w_reg;
+        a.r_in = v.rbuf(cur); a.r_out = v.rbuf(cur ^ 1); a.Ap_in = v.Abuf(cur); a.Ap_out = v.Abuf(cur ^ 1); a.p_in = v.p[cur]; a.p_out = v.p[cur ^ 1]; a.delta = v.delta; a.mode = mode;
+        a.alphaN_prev = aN; a.alphaD_prev = aD; a.betaN_prev = bN; a.alphaN_prev2 = aN2; a.alphaD_prev2 = aD2;
+        a.alphaD_out = out; a.s12_out = s12_out;
+        return a;
+    }
+    int run_iter(LaunchCtx& c, const thallo_iw_iter_t& a)
+    {
+        TimedLaunch t(c, "PCGIteration");
+        // the recomputing kernel has no A p_{k-1} to start a GN step from: the stored-plane kernel runs every first iteration
+        const int kernel = march_rc_ && !(a.mode & 1) ? THALLO_IW_ITER_MARCH_RC : march_ ? THALLO_IW_ITER_MARCH : THALLO_IW_ITER_TILE;
+        return thallo_hip_iw_pcg_iter(kernel, &a, c.stream);
+    }
+public:
     int pcg_iter_dist(LaunchCtx& c, SolverVectors& v, int cur, int mode, thallo_sum_t aN, thallo_sum_t aD, thallo_sum_t bN, thallo_sum_t aN2, thallo_sum_t aD2,
                       const thallo_dist_t& d, float* out, int slot0, float* aD_word, float* bN_word) override
     {
-        TimedLaunch t(c, "PCGIteration");
-        if (march_rc_ && !(mode & 1))
-            return thallo_hip_iw_pcg_iter_march_rc_dist(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                        v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                        aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, d, out, v.s12, v.fin_tickets, slot0, aD_word, bN_word, c.stream);
-        if (march_)
-            return thallo_hip_iw_pcg_iter_march_dist(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                     v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                     aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, d, out, v.s12, v.fin_tickets, slot0, aD_word, bN_word, c.stream);
-        return thallo_hip_iw_pcg_iter_dist(W, H, row0_, row1_, (const float*)cs.ptr, urshape, (const unsigned char*)flags.ptr, v.pre, w_fit, w_reg,
-                                           v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                           aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, d, out, v.s12, v.fin_tickets, slot0, aD_word, bN_word, c.stream);
+        thallo_iw_iter_t a = iter_block(v, cur, mode, aN, aD, bN, aN2, aD2, out, v.s12);
+        a.dist = &d; a.fin_tickets = v.fin_tickets; a.slot0 = slot0; a.alphaD_word = aD_word; a.betaN_word = bN_word;
+        return run_iter(c, a);
     }
     bool dist_defers_finish() const override { return march_rc_ && march_ && thallo_hip_iw_march_rc_deferred_fits(W, row1_ - row0_) != 0; }      // (every workgroup of the launch resident)
     int pcg_iter_dist_deferred(LaunchCtx& c, SolverVectors& v, int cur, int mode, thallo_sum_t aN, thallo_sum_t aD, thallo_sum_t bN, thallo_sum_t aN2, thallo_sum_t aD2,
                                const thallo_prev_t& prev, int prev_slot0, unsigned long long* gs, const thallo_dist_t& d, float* out, double* s12_out) override
     {
-        TimedLaunch t(c, "PCGIteration");
-        if (mode & 1)       // a GN step's first iteration: the stored-plane kernel, partials only (no tickets: nothing is exchanged at its end)
-            return thallo_hip_iw_pcg_iter_march_dist(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                     v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                     aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, d, out, s12_out, nullptr, 0, nullptr, nullptr, c.stream);
-        return thallo_hip_iw_pcg_iter_march_rc_dist_deferred(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                             v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                             aN, aN2, aD2, prev, prev_slot0, gs, (const int*)irregular.ptr, d, out, s12_out, c.stream);
+        thallo_iw_iter_t a = iter_block(v, cur, mode, aN, aD, bN, aN2, aD2, out, s12_out);
+        a.dist = &d;
+        // (a GN step's first iteration: the stored-plane kernel, partials only -- no tickets: nothing is exchanged at its end)
+        if (!(mode & 1)) { a.prev = &prev; a.prev_slot0 = prev_slot0; a.gs = gs; }
+        return run_iter(c, a);
     }
     int pcg_iter_dist_finish(LaunchCtx& c, const thallo_prev_t& prev, int prev_slot0, thallo_sum_t aN, const thallo_dist_t& d, unsigned long long* gs) override
     { TimedLaunch t(c, "PCGScalars"); return thallo_hip_iw_dist_finish_deferred(prev, prev_slot0, aN, d, gs, c.stream); }
@@ -312,21 +322,9 @@ public:
     int pcg_iter(LaunchCtx& c, SolverVectors& v, int cur, int mode, thallo_sum_t aN, thallo_sum_t aD, thallo_sum_t bN, thallo_sum_t aN2, thallo_sum_t aD2, float* out,
                  float* aD_word, float* bN_word) override
     {
-        TimedLaunch t(c, "PCGIteration");
-        if (march_rc_ && !(mode & 1))
-            return thallo_hip_iw_pcg_iter_march_rc(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                   v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                   aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, out, v.s12,
-                                                   aD_word ? v.fin_tickets : nullptr, aD_word, bN_word, c.stream);
-        if (march_)
-            return thallo_hip_iw_pcg_iter_march(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, out, v.s12,
-                                                aD_word ? v.fin_tickets : nullptr, aD_word, bN_word, c.stream);
-        return thallo_hip_iw_pcg_iter(W, H, row0_, row1_, (const float*)cs.ptr, urshape, (const unsigned char*)flags.ptr, v.pre, w_fit, w_reg,
-                                      v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                      aN, aD, bN, aN2, aD2, (const int*)irregular.ptr, out, v.s12,
-                                      aD_word ? v.fin_tickets : nullptr, aD_word, bN_word, c.stream);
+        thallo_iw_iter_t a = iter_block(v, cur, mode, aN, aD, bN, aN2, aD2, out, v.s12);
+        a.fin_tickets = aD_word ? v.fin_tickets : nullptr; a.alphaD_word = aD_word; a.betaN_word = bN_word;
+        return run_iter(c, a);
     }
     int pcg_iter_finish(LaunchCtx& c, SolverVectors& v, const float* part, int count, thallo_sum_t aN, float* aD_word, float* bN_word) override
     {
@@ -365,18 +363,10 @@ public:
     int pcg_iter_deferred(LaunchCtx& c, SolverVectors& v, int cur, int mode, thallo_sum_t aN, thallo_sum_t aN2, thallo_sum_t aD2, const thallo_prev_t& prev,
                           float* out, double* s12_out) override
     {
-        TimedLaunch t(c, "PCGIteration");
-        if (march_rc_ && !(mode & 1))
-            return thallo_hip_iw_pcg_iter_march_rc_deferred(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                            v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                            aN, aN2, aD2, prev, (const int*)irregular.ptr, out, s12_out, c.stream);
-        if (march_)
-            return thallo_hip_iw_pcg_iter_march_deferred(W, H, row0_, row1_, (const float*)cs.ptr, (const unsigned char*)flags.ptr, w_fit, w_reg,
-                                                         v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                                         aN, aN2, aD2, prev, (const int*)irregular.ptr, out, s12_out, c.stream);
-        return thallo_hip_iw_pcg_iter_deferred(W, H, row0_, row1_, (const float*)cs.ptr, urshape, (const unsigned char*)flags.ptr, v.pre, w_fit, w_reg,
-                                               v.rbuf(cur), v.rbuf(cur ^ 1), v.Abuf(cur), v.Abuf(cur ^ 1), v.p[cur], v.p[cur ^ 1], v.delta, mode,
-                                               aN, aN2, aD2, prev, (const int*)irregular.ptr, out, s12_out, c.stream);
+        const thallo_sum_t none = { nullptr, 0 };
+        thallo_iw_iter_t a = iter_block(v, cur, mode, aN, none, none, aN2, aD2, out, s12_out);
+        a.prev = &prev;
+        return run_iter(c, a);
     }
     int pcg_iter_finish_from(LaunchCtx& c, const float* part, const double* s12p, int count, thallo_sum_t aN, float* aD_word, float* bN_word) override
     {

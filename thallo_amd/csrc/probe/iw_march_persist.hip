@@ -511,7 +511,7 @@ int thallo_hip_debug_stamps_persist(unsigned long long* buf) { return hipMemcpyT
 #endif
 
 /* Iterations k0 .. k1-1 (1 <= k0 < k1) of the PCG loop of a GN step in ONE launch; whole images on the unit pixel grid.  What a launch per iteration
- * (thallo_hip_iw_pcg_iter_march_rc_deferred, delta mode "none") reads and leaves behind, in the plan's own layout:
+ * (thallo_hip_iw_pcg_iter: THALLO_IW_ITER_MARCH_RC with `prev`, delta mode "none") reads and leaves behind, in the plan's own layout:
  *   r[k & 1] -> r[(k + 1) & 1];  p_{k-1} in planes[(k - 1) % n_planes] -> p_k in planes[k % n_planes]  (n_planes >= k1 - k0 + 1, so that no plane of the launch is written twice or read after its overwrite);
  *   reduction slots at parts + j * THALLO_HIP_MAX_PARTIALS with their words at parts + slots * THALLO_HIP_MAX_PARTIALS + j, alphaN_k = slot B + 2k, alphaD_k = B + 2k + 1, betaN_k = B + 2k + 2:
  *   read  alphaN_{k0-1} (alphaN_prev: partials or one word), the nb_prev alphaD partials of iteration k0 - 1 and its double sums in s12[(k0 - 1) & 1];

@@ -583,21 +583,20 @@ constexpr int MARCH_WG_PER_CU = 1;                                // grid sizing
     X(2, 1, 2, 1) X(2, 1, 2, 2) X(1, 1, 2, 0) X(3, 1, 2, 0) X(2, 5, 2, 1) X(2, 11, 2, 1) X(2, 0, 2, 1) X(2, 1, 2, 3) X(2, 5, 2, 3) X(2, 11, 2, 3) X(2, 0, 2, 3)
 
 template <bool DIST>
-int launch_march(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags, float w_fit, float w_reg,
-                 const float* r_in, float* r_out, const float* Ap_in, float* Ap_out, const float* p_in, float* p_out, float* delta, int mode,
-                 thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp, const int* irregular, thallo_dist_t d,
-                 float* aD_out, double* s12_out, unsigned* fin_tickets, float* aD_word, float* bN_word, int xslot, hipStream_t stream, PrevSums prev = PrevSums{ nullptr, nullptr, 0, nullptr, nullptr })
+int launch_march_as(const thallo_iw_iter_t& a, hipStream_t stream)
 {
-    const int R = pick_rows(W, row1 - row0, MARCH_WG_PER_CU);
+    const IterForm f(a);
+    const int R = pick_rows(a.W, a.row1 - a.row0, MARCH_WG_PER_CU);
     if (R <= 0) return -(int)hipErrorNotSupported;                          // wider than the workgroup budget: thallo_hip_iw_march_fits() said so
-    const MarchGeo g = make_march_geo(W, H, row0, row1, R);
+    const MarchGeo g = make_march_geo(a.W, a.H, a.row0, a.row1, R);
     const int grid = (g.total + 7) / 8 * 8;
     if (grid > THALLO_MAX_PARTIALS) return -(int)hipErrorInvalidValue;      // (only reachable through the tools' forced rows-per-segment)
-    const bool first = mode & 1;
-    const int dmode = first ? 1 : (mode >> 1) & 3;
-    const float wf2 = w_fit * w_fit, wr2 = w_reg * w_reg;
-#define MARCH_LAUNCH(F, DM, DP, NTM, OCC, DBG) hipLaunchKernelGGL((k_iter_march<F, DM, DP, NTM, DIST, OCC, DBG>), dim3(grid), dim3(MARCH_NT), 0, stream, g, cs, flags, wf2, wr2, \
-        r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, aNp, aDp, bNp, aNpp, aDpp, aD_out, s12_out, irregular, d, fin_tickets, aD_word, bN_word, xslot, prev)
+    const bool first = a.mode & 1;
+    const int dmode = first ? 1 : (a.mode >> 1) & 3;
+    const float wf2 = a.w_fit * a.w_fit, wr2 = a.w_reg * a.w_reg;
+#define MARCH_LAUNCH(F, DM, DP, NTM, OCC, DBG) hipLaunchKernelGGL((k_iter_march<F, DM, DP, NTM, DIST, OCC, DBG>), dim3(grid), dim3(MARCH_NT), 0, stream, g, a.cs, a.flags, wf2, wr2, \
+        a.r_in, a.r_out, a.Ap_in, a.Ap_out, a.p_in, a.p_out, a.delta, a.alphaN_prev, f.aDp, f.bNp, a.alphaN_prev2, a.alphaD_prev2, a.alphaD_out, a.s12_out, a.irregular, f.d, \
+        f.tickets, f.aD_word, f.bN_word, f.xslot, f.prev)
     // (the multi-GPU variant has no "apply two delta updates" form: peer stores on top of that variant's 256 registers spill, and at slab sizes the
     //  6 B/pixel it saves do not matter -- solver_dist.cpp updates delta every iteration on the device-side transport)
     if (DIST && dmode == 2) return -(int)hipErrorInvalidValue;
@@ -620,58 +619,18 @@ int launch_march(int W, int H, int row0, int row1, const float* cs, const unsign
 
 }  // namespace
 
+// the stored-plane kernel's own conditions on a block: an even width, both A p planes (A p_{k-1} unless the launch is a GN step's first)
+int thallo::launch_march(const thallo_iw_iter_t& a, hipStream_t stream)
+{
+    if ((a.W & 1) || a.W < 2 || !a.Ap_out || (!(a.mode & 1) && !a.Ap_in)) return -(int)hipErrorInvalidValue;
+    if (a.dist && a.gs) return -(int)hipErrorNotSupported;      // (the deferred cross-rank finish: the recomputing kernel only)
+    return !a.dist ? launch_march_as<false>(a, stream) : launch_march_as<true>(a, stream);
+}
+
 extern "C" {
 #ifdef THALLO_MARCH_SWEEP
 int thallo_hip_debug_stamps_march(unsigned long long* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_m), &buf, sizeof buf) == hipSuccess ? 0 : -1; }
 #endif
-
-int thallo_hip_iw_pcg_iter_march(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                 float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                 const float* p_in, float* p_out, float* delta, int mode,
-                                 thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                                 const int* irregular, float* aD_out, double* s12_out,
-                                 unsigned* fin_tickets, float* aD_word, float* bN_word, thallo_stream_t stream)
-{
-    if (row0 < 0 || row1 > H || row0 >= row1 || (W & 1) || W < 2) return -(int)hipErrorInvalidValue;
-    if (!cs || !flags || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if (!(mode & 1) && (!Ap_in || !delta)) return -(int)hipErrorInvalidValue;
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    return launch_march<false>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode,
-                               aNp, aDp, bNp, aNpp, aDpp, irregular, thallo_dist_t{}, aD_out, s12_out, fin_tickets, aD_word, bN_word, 0, (hipStream_t)stream);
-}
-
-int thallo_hip_iw_pcg_iter_march_deferred(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                          float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                          const float* p_in, float* p_out, float* delta, int mode,
-                                          thallo_sum_t aNp, thallo_sum_t aNpp, thallo_sum_t aDpp, thallo_prev_t prev,
-                                          const int* irregular, float* aD_out, double* s12_out, thallo_stream_t stream)
-{
-    if (row0 < 0 || row1 > H || row0 >= row1 || (W & 1) || W < 2) return -(int)hipErrorInvalidValue;
-    if (!cs || !flags || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if (!(mode & 1) && (!Ap_in || !delta || prev.count < 1 || prev.count > THALLO_MAX_PARTIALS || !prev.alphaD_partials || !prev.s12_partials || !prev.alphaD_word ||
-                        !prev.betaN_word || prev.s12_partials == s12_out)) return -(int)hipErrorInvalidValue;
-    const thallo_sum_t none = { nullptr, 0 };
-    return launch_march<false>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode,
-                               aNp, none, none, aNpp, aDpp, irregular, thallo_dist_t{}, aD_out, s12_out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream,
-                               (mode & 1) ? PrevSums{ nullptr, nullptr, 0, nullptr, nullptr } : PrevSums{ prev.alphaD_partials, prev.s12_partials, prev.count, prev.alphaD_word, prev.betaN_word });
-}
-
-int thallo_hip_iw_pcg_iter_march_dist(int W, int H, int row0, int row1, const float* cs, const unsigned char* flags,
-                                      float w_fit, float w_reg, const float* r_in, float* r_out, const float* Ap_in, float* Ap_out,
-                                      const float* p_in, float* p_out, float* delta, int mode,
-                                      thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, thallo_sum_t aNpp, thallo_sum_t aDpp,
-                                      const int* irregular, thallo_dist_t d, float* aD_out, double* s12_out,
-                                      unsigned* fin_tickets, int slot0, float* aD_word, float* bN_word, thallo_stream_t stream)
-{
-    if (row0 < 0 || row1 > H || row0 >= row1 || (W & 1) || W < 2) return -(int)hipErrorInvalidValue;
-    if (!cs || !flags || !r_in || !r_out || !Ap_out || !p_in || !p_out || !aD_out || !s12_out) return -(int)hipErrorInvalidValue;
-    if ((!(mode & 1) && (!Ap_in || !delta)) || d.world < 1 || d.world > THALLO_DIST_MAX_WORLD) return -(int)hipErrorInvalidValue;
-    if (!fin_tickets || !aD_word || !bN_word) { fin_tickets = nullptr; aD_word = nullptr; bN_word = nullptr; }
-    if (fin_tickets && (slot0 < 0 || !d.mail || !d.ctl || 7 * d.world > 64 || bNp.count != 1)) return -(int)hipErrorInvalidValue;
-    for (int k = 0; k < 2; ++k) if (d.peer_r[k] && ((d.peer_off_o[k] | d.peer_off_a[k]) & 1)) return -(int)hipErrorInvalidValue;
-    return launch_march<true>(W, H, row0, row1, cs, flags, w_fit, w_reg, r_in, r_out, Ap_in, Ap_out, p_in, p_out, delta, mode,
-                              aNp, aDp, bNp, aNpp, aDpp, irregular, d, aD_out, s12_out, fin_tickets, aD_word, bN_word, slot0, (hipStream_t)stream);
-}
 
 int thallo_hip_iw_urshape_irregular(int W, int H, const float* urshape, int* count_out, thallo_stream_t stream)
 {

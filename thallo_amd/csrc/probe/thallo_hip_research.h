@@ -10,7 +10,7 @@ extern "C" {
 /* ---- the marching PCG iteration as a PERSISTENT loop (probe/iw_march_persist.hip): iterations k0 .. k1-1 of a GN step in ONE launch, for whole images on
  * the unit pixel grid whose solver state does not fit the chip's registers (2048^2: 35 rows per wave).  The launch-per-iteration grid stays on the chip; the
  * iteration's sums (a tagged record per workgroup) are its one synchronisation point, r_k / p_k are stored write-through.  What a launch per iteration
- * (thallo_hip_iw_pcg_iter_march_rc_deferred, delta mode "none") reads and leaves behind, in the plan's own layout:
+ * (thallo_hip_iw_pcg_iter: THALLO_IW_ITER_MARCH_RC with `prev`, delta mode "none") reads and leaves behind, in the plan's own layout:
  *   r[k & 1] -> r[(k + 1) & 1];  p_{k-1} in planes[(k - 1) % n_planes] -> p_k in planes[k % n_planes]   (n_planes >= k1 - k0 + 1);
  *   reduction slots at parts + j * THALLO_HIP_MAX_PARTIALS, their words at parts + slots * THALLO_HIP_MAX_PARTIALS + j; alphaN_k = slot B + 2k, alphaD_k = B + 2k + 1, betaN_k = B + 2k + 2:
  *   read  alphaN_{k0-1} (alphaN_prev: partials or one word), the nb_prev alphaD partials of iteration k0 - 1 and its double sums in s12[(k0 - 1) & 1];

@@ -1,4 +1,4 @@
-"""GPU probe (run through gpurun): the marching one-kernel PCG iteration (thallo_hip_iw_pcg_iter_march) against the LDS-tiled
+"""GPU probe: the marching one-kernel PCG iteration (thallo_hip_iw_pcg_iter, THALLO_IW_ITER_MARCH) against the LDS-tiled
 k_iter on the same inputs -- bitwise comparison of every output plane, then a timing sweep over rows-per-segment / prefetch depth /
 non-temporal mask.  Needs the sweep build for the knobs to take effect:  make -C thallo_amd/csrc SWEEP=1 -B
 Not part of the product or the tests."""
@@ -41,21 +41,24 @@ torch.cuda.synchronize()
 assert int(irregular[0].item()) == 0
 
 
+def launch(kind, mode, r_in, r_out, A_in, A_out, p_in, p_out, d, fin):
+    """one launch of the tile or the stored-plane marching kernel on a whole image (urshape / pre: the tile kernel only reads them)"""
+    a = api.IwIterT(W=W, H=H, row0=0, row1=H, cs=cs.data_ptr(), urshape=dev[2].data_ptr(), flags=flags.data_ptr(), pre=pre.data_ptr(), irregular=irregular.data_ptr(),
+                    w_fit=float(p[5]), w_reg=float(p[6]), r_in=r_in.data_ptr(), r_out=r_out.data_ptr(), Ap_in=A_in.data_ptr(), Ap_out=A_out.data_ptr(),
+                    p_in=p_in.data_ptr(), p_out=p_out.data_ptr(), delta=d.data_ptr(), mode=mode,
+                    alphaN_prev=S(0), alphaD_prev=S(1), betaN_prev=S(2), alphaN_prev2=S(3), alphaD_prev2=S(4),
+                    alphaD_out=parts.data_ptr() + 4096, s12_out=s12.data_ptr())
+    if fin:
+        a.fin_tickets, a.alphaD_word, a.betaN_word = tickets.data_ptr(), words.data_ptr(), words.data_ptr() + 4
+    return L.thallo_hip_iw_pcg_iter(api.IW_ITER_TILE if kind == "tile" else api.IW_ITER_MARCH, C.byref(a), None)
+
+
 def run(kind, mode, r_in, A_in, p_in, dl, fin=True):
     r_out, A_out, p_out = f(), f(), f()
     d = dl.clone()
     if ((mode >> 1) & 3) == 2:           # p_out holds p_{k-2} before it is overwritten
         p_out.copy_(pk2)
-    args_tail = (S(0), S(1), S(2), S(3), S(4), vp(irregular.data_ptr()), vp(parts.data_ptr() + 4096), vp(s12.data_ptr()),
-                 vp(tickets.data_ptr()) if fin else None, vp(words.data_ptr()) if fin else None, vp(words.data_ptr() + 4) if fin else None, None)
-    if kind == "tile":
-        nb = L.thallo_hip_iw_pcg_iter(W, H, 0, H, vp(cs.data_ptr()), vp(dev[2].data_ptr()), vp(flags.data_ptr()), vp(pre.data_ptr()), fl(p[5]), fl(p[6]),
-                                      vp(r_in.data_ptr()), vp(r_out.data_ptr()), vp(A_in.data_ptr()), vp(A_out.data_ptr()), vp(p_in.data_ptr()), vp(p_out.data_ptr()),
-                                      vp(d.data_ptr()), mode, *args_tail)
-    else:
-        nb = L.thallo_hip_iw_pcg_iter_march(W, H, 0, H, vp(cs.data_ptr()), vp(flags.data_ptr()), fl(p[5]), fl(p[6]),
-                                            vp(r_in.data_ptr()), vp(r_out.data_ptr()), vp(A_in.data_ptr()), vp(A_out.data_ptr()), vp(p_in.data_ptr()), vp(p_out.data_ptr()),
-                                            vp(d.data_ptr()), mode, *args_tail)
+    nb = launch(kind, mode, r_in, r_out, A_in, A_out, p_in, p_out, d, fin)
     assert nb > 0, nb
     torch.cuda.synchronize()
     aD = float(parts[1024:1024 + nb].double().sum().item())
@@ -92,20 +95,12 @@ def timeit(kind, reps=REPS, modes=(4, 2), pingpong=True, hook=None):
     """alternate modes 4 / 2 like the PCG loop does, ping-ponging the buffers (pingpong=False: always a -> b, so no launch reads what the previous one wrote)"""
     bufs = [[it0["r"].clone(), it0["A"].clone(), it0["p"].clone()], [f(), f(), f()]]
     d = delta0.clone()
-    fn = L.thallo_hip_iw_pcg_iter if kind == "tile" else L.thallo_hip_iw_pcg_iter_march
 
     def one(k):
         if hook is not None:
             hook(k)
         a, b = (bufs[k & 1], bufs[(k & 1) ^ 1]) if pingpong else (bufs[0], bufs[1])
-        mode = modes[k % len(modes)]
-        tail = (vp(a[0].data_ptr()), vp(b[0].data_ptr()), vp(a[1].data_ptr()), vp(b[1].data_ptr()), vp(a[2].data_ptr()), vp(b[2].data_ptr()), vp(d.data_ptr()), mode,
-                S(0), S(1), S(2), S(3), S(4), vp(irregular.data_ptr()), vp(parts.data_ptr() + 4096), vp(s12.data_ptr()),
-                vp(tickets.data_ptr()) if FIN else None, vp(words.data_ptr()) if FIN else None, vp(words.data_ptr() + 4) if FIN else None, None)
-        if kind == "tile":
-            rc = fn(W, H, 0, H, vp(cs.data_ptr()), vp(dev[2].data_ptr()), vp(flags.data_ptr()), vp(pre.data_ptr()), fl(p[5]), fl(p[6]), *tail)
-        else:
-            rc = fn(W, H, 0, H, vp(cs.data_ptr()), vp(flags.data_ptr()), fl(p[5]), fl(p[6]), *tail)
+        rc = launch(kind, modes[k % len(modes)], a[0], b[0], a[1], b[1], a[2], b[2], d, FIN)
         assert rc > 0, rc
     for k in range(4):
         one(k)
