@@ -200,6 +200,36 @@ int ThalloX_PlanSetRobustLoss(Thallo_Plan* plan, int kind, float scale);
  * the inliers off.  Returns the number of observations, or -1 when no loss is in force since the last Init or n is not that number.  Synchronises the plan's stream. */
 long ThalloX_PlanRobustWeights(Thallo_Plan* plan, float* host_out, long n);
 
+/* How well the cameras and points are determined: marginal blocks of the covariance at the plan's current unknowns.  With A = J_s^T J_s there (J_s carries the robust
+ * weights when a loss is in force; NO LM diagonal is added, on a ThalloX_EnableLM plan too) and F the scalars the caller does not hold (ThalloX_PlanSetHeldUnknowns),
+ * Sigma = (A_FF)^-1 bordered by exact zero rows and columns at the held scalars.  input 0: the 9 x 9 block of every camera ids[i] into host_out[81 i ..]; input 1: the
+ * 3 x 3 block of every point ids[i] into host_out[9 i ..]; row-major, symmetric bit for bit, the caller's ids.  The blocks are UNSCALED, as the common packages return them:
+ * multiply by your sigma^2.  FIXING THE GAUGE IS THE CALLER'S JOB, through ThalloX_PlanSetHeldUnknowns (a camera and one more scalar, or two cameras): without it A is
+ * singular and the columns do not converge.  A point that the elimination's factor rule holds (observed once or never, or a squared pivot below 2^-16; see
+ * ThalloX_PlanSchurHeldPoints) has no finite covariance: its block is filled with quiet NaNs and counted; a point the caller holds entirely returns zeros; the columns
+ * of a camera nothing observes do not converge and its block stays zero.
+ * Computed through the Schur complement on the cameras, S^-1 and Cp^-1 + V^T S^-1 V, by a float32 PCG on the assembled S, 64 columns at a time: the plan's last
+ * Thallo_ProblemInit must have run THALLOX_SOLVER_SCHUR_EXPLICIT_PCG.  A column ends when sqrt(r . z / r0 . z0) <= rel_tol or after max_iterations; opt == NULL: 1e-6 and
+ * 500 (from a CPU study in float32: the error against float64 levels off at 3e-6 ... 2e-5 of sqrt(Sigma_aa Sigma_bb) from there on).  The call re-linearises at the
+ * current unknowns and leaves the solve as it was: unknowns, the LM radius, costs and the kernel statistics of the steps are untouched, and a plan that never makes
+ * the call launches what it launched before.  Its work vectors are allocated at the first call and freed with the plan.  Synchronises the plan's stream.
+ * Returns 0; or the number of columns that did not converge (> 0; host_out is written all the same); or a negative number with ThalloX_LastError naming the energy
+ * and the reason: wherever THALLOX_SOLVER_SCHUR_EXPLICIT_PCG is refused, a plan whose last Init ran another linear solver, a call before Thallo_ProblemInit, an input
+ * that is not an Unknown, n <= 0, an id out of range or repeated, a rel_tol that is not finite and positive, max_iterations < 1. */
+typedef struct ThalloX_CovarianceOptions {
+    float rel_tol;               /* default 1e-6 */
+    int   max_iterations;        /* default 500 */
+} ThalloX_CovarianceOptions;
+typedef struct ThalloX_CovarianceInfo {
+    long  iterations;            /* PCG iterations run, added over the batches of 64 columns */
+    long  columns;               /* columns solved (a held scalar's unit column and a held point's columns are zero and need no solve) */
+    long  not_converged;         /* ... of them not converged */
+    long  nan_blocks;            /* blocks filled with NaN */
+    float worst_residual;        /* the largest sqrt(r . z / r0 . z0) a column ended with */
+} ThalloX_CovarianceInfo;
+long ThalloX_PlanCovariance(Thallo_Plan* plan, void** problem_params, int input, const int* ids, long n, float* host_out, const ThalloX_CovarianceOptions* opt,
+                            ThalloX_CovarianceInfo* info);
+
 /* 1 if the most recent Thallo_ProblemInit on this plan succeeded (parameters bound, plugin prepared), else 0: Init itself returns void. */
 int ThalloX_PlanReady(Thallo_Plan* plan);
 

@@ -835,6 +835,53 @@ int thallo_hip_ba_schur_assemble(int C, int nlower, long nblk, const int* lower,
 int thallo_hip_ba_schur_apply_s(int C, long nblk, const int* row_ptr, const int* col, const float* S, const float* x, float* Sx, float* xSx_out, const unsigned* gate,
                                 thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- marginal covariances (ba_covariance.hip; DESIGN.md "Marginal covariances")
+ * Columns of S^-1 (a camera's nine unit columns) or of S^-1 V (a point's three, V = W_q G_p at the rows of camera c(q)) by PCG on the assembled S with the camera blocks'
+ * G^T G as preconditioner, THALLO_HIP_COV_K columns at a time, ONE LANE PER COLUMN.  A panel is [9 C][THALLO_HIP_COV_K] floats, a scalar's columns consecutive; a batch
+ * holds up to 7 cameras (column 9 j + a) or 21 points (column 3 j + m), its unused columns have a zero right-hand side and stay zero.  Every sum, scalar, freeze decision
+ * and update of a column is its lane's alone: a column's result does not depend on its companions in the batch.  Partials: one per workgroup and column,
+ * min(C, 1024) of them whatever the batch holds, added in a fixed order; no float atomics: bitwise reproducible. */
+#define THALLO_HIP_COV_K 64
+#define THALLO_HIP_COV_CHUNK 8            /* iterations enqueued between two looks at the frozen count */
+typedef struct thallo_cov_sys_t {
+    int C, P;
+    long nblk;                            /* the assembled S as thallo_hip_ba_schur_assemble left it ... */
+    const int *row_ptr, *col;
+    const float* S;
+    const float* Gc;                      /* ... the camera blocks' factor, 45 planes of C floats (thallo_hip_block_factor, held rows and columns zero) ... */
+    const float* Ge;                      /* ... and for points: the elimination factor (6 planes of P floats), W (thallo_hip_ba_schur_w) and the point lists */
+    const float* W;
+    const int *pt_ptr, *pt_pos, *q_cam;
+    const unsigned char* hold;            /* the mask of held unknowns over the flat vector, or NULL: tells a point the caller holds (zeros) from one the factor rule held (NaN) */
+} thallo_cov_sys_t;
+typedef struct thallo_cov_info_t {
+    int iterations;                       /* PCG iterations this batch ran */
+    int columns;                          /* columns with a nonzero right-hand side */
+    int not_converged;                    /* ... of them not frozen when the batch ended */
+    int nan_blocks;                       /* point blocks filled with NaN */
+    float worst;                          /* the largest sqrt(r . z / r0 . z0) over those columns */
+} thallo_cov_info_t;
+long thallo_hip_ba_cov_work_bytes(int C);      /* device bytes a batch works in (five panels, two slots of partials, the per-column scalars) */
+/* The right-hand sides of a batch into the panel R (zeroed first).  mode 0: ids = nreq <= 7 cameras, unit columns; mode 1: nreq <= 21 points (the plan's internal ids),
+ * W_q G_p into the rows of c(q) over the point's list in list order.  ids: a DEVICE array. */
+int thallo_hip_ba_cov_rhs(const thallo_cov_sys_t* sys, int mode, const int* ids, int nreq, float* R, thallo_stream_t stream);
+/* Y = S X for a panel and, per column, the partials of x . S x at xSx_out[w * THALLO_HIP_COV_K + column] (returns their number per column, min(C, 1024)): one wave per
+ * camera row, the row's blocks staged through LDS 32 at a time, every lane its column's nine sums over the row's blocks in ascending order. */
+int thallo_hip_ba_schur_apply_s_cols(int C, long nblk, const int* row_ptr, const int* col, const float* S, const float* X, float* Y, float* xSx_out, thallo_stream_t stream);
+/* Z = G^T G R on the camera region for a panel, and the partials of r . z per column (returns their number per column). */
+int thallo_hip_ba_cov_precond_cols(int C, const float* Gc, const float* R, float* Z, float* rz_out, thallo_stream_t stream);
+/* The output blocks of a batch from its solved panel X into out (DEVICE; nreq x 81 or nreq x 9 floats), each symmetric bit for bit: a camera's 0.5 (X_ii + X_ii^T); a point's
+ * G^T G + sum_q (W_q G)^T X_c(q), symmetrised the same way.  A point whose elimination factor is zero gets zeros where sys->hold holds all of it and quiet NaNs otherwise
+ * (nan_count[0] += 1, a device word). */
+int thallo_hip_ba_cov_out(const thallo_cov_sys_t* sys, int mode, const int* ids, int nreq, const float* X, float* out, unsigned* nan_count, thallo_stream_t stream);
+/* One batch: right-hand sides, PCG with per-column scalars that stay on the device (alpha = alphaN / alphaD, 0 where alphaD <= 0; beta = betaN / alphaN, 0 where
+ * alphaN <= 0; a column whose r . z <= rel_tol^2 r0 . z0 is frozen at that iteration and its X never changes again), the output blocks.  Five launches per iteration
+ * (P = Z + beta P; Y = S P; alpha; X, R, Z; beta and the freeze), no host round trip inside one; every THALLO_HIP_COV_CHUNK iterations the frozen count is copied to
+ * pinned[0 / 1] (two pinned host words, or NULL: a blocking read) and the batch ends early once every column is frozen.  work: thallo_hip_ba_cov_work_bytes(C) device bytes.
+ * Synchronises the stream.  Returns 0 or a negative code. */
+int thallo_hip_ba_cov_solve(const thallo_cov_sys_t* sys, int mode, const int* ids, int nreq, float rel_tol, int max_iterations, void* work, unsigned* pinned, float* out,
+                            thallo_cov_info_t* info, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

@@ -81,6 +81,14 @@ class DistributedT(C.Structure):
                 ("global_row0", C.c_uint), ("global_rows", C.c_uint), ("allreduce", AllReduceFn)]
 
 
+class CovarianceOptions(C.Structure):      # ThalloX_CovarianceOptions of include/Thallo.h
+    _fields_ = [("rel_tol", C.c_float), ("max_iterations", C.c_int)]
+
+
+class CovarianceInfo(C.Structure):         # ThalloX_CovarianceInfo
+    _fields_ = [("iterations", C.c_long), ("columns", C.c_long), ("not_converged", C.c_long), ("nan_blocks", C.c_long), ("worst_residual", C.c_float)]
+
+
 def lib():
     """Load libThallo.so; raises (never falls back) if it has not been built."""
     global _lib
@@ -127,6 +135,9 @@ def lib():
     if hasattr(L, "ThalloX_PlanSetRobustLoss"):      # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_robust_bench.py --ab)
         L.ThalloX_PlanSetRobustLoss.argtypes = [vp, C.c_int, C.c_float]; L.ThalloX_PlanSetRobustLoss.restype = C.c_int
         L.ThalloX_PlanRobustWeights.argtypes = [vp, vp, C.c_long]; L.ThalloX_PlanRobustWeights.restype = C.c_long
+    if hasattr(L, "ThalloX_PlanCovariance"):         # (likewise: an A/B build from before the call existed)
+        L.ThalloX_PlanCovariance.argtypes = [vp, vpp, C.c_int, vp, C.c_long, vp, C.POINTER(CovarianceOptions), C.POINTER(CovarianceInfo)]
+        L.ThalloX_PlanCovariance.restype = C.c_long
     L.ThalloX_PlanSetDistributed.argtypes = [vp, C.POINTER(DistributedT)]; L.ThalloX_PlanSetDistributed.restype = C.c_int
     L.ThalloX_PlanDistributedInfo.argtypes = [vp]; L.ThalloX_PlanDistributedInfo.restype = C.c_char_p
     L.ThalloX_DistributedControl.argtypes = [vp, C.c_int, C.c_int]; L.ThalloX_DistributedControl.restype = C.c_int
@@ -466,6 +477,31 @@ class ThalloSolver:
         out = np.empty(int(self._dims[2]), np.float32)      # (bundle_adjustment: dims = (cameras, points, observations); any other plan answers -1 below)
         if self._L.ThalloX_PlanRobustWeights(self.plan, out.ctypes.data_as(C.c_void_p), int(out.size)) != out.size:
             raise RuntimeError("ThalloX_PlanRobustWeights: no robust loss in force on this plan (or it has another number of observations)")
+        return out
+
+    def covariance(self, params, cameras=None, points=None, rel_tol=1e-6, max_iterations=500):
+        """Marginal covariance blocks at the plan's current unknowns (include/Thallo.h ThalloX_PlanCovariance): `cameras` and `points` are sequences of the caller's ids
+        (None: that kind is not asked for).  Returns {"cameras": float32 [n, 9, 9], "points": float32 [m, 3, 3], "info": {...}}: the blocks of (A_FF)^-1, A = J^T J without
+        the LM diagonal, unscaled, zero rows and columns at held scalars, NaN blocks for points the elimination holds; info adds up iterations, columns, not_converged and
+        nan_blocks over both kinds and keeps the largest worst_residual.  The gauge is the caller's to fix, with hold().  The plan's last init() must have run
+        set_linear_solver("schur_explicit_pcg"); raises, with the library's reason, where the call is refused."""
+        import numpy as np
+        out = {"cameras": np.zeros((0, 9, 9), np.float32), "points": np.zeros((0, 3, 3), np.float32),
+               "info": {"iterations": 0, "columns": 0, "not_converged": 0, "nan_blocks": 0, "worst_residual": 0.0}}
+        opt = CovarianceOptions(float(rel_tol), int(max_iterations))
+        for key, input, ids, d in (("cameras", 0, cameras, 9), ("points", 1, points, 3)):
+            if ids is None:
+                continue
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
+            blocks = np.zeros((len(ids), d, d), np.float32)
+            info = CovarianceInfo()
+            rc = self._L.ThalloX_PlanCovariance(self.plan, params, input, ids.ctypes.data_as(C.c_void_p), len(ids), blocks.ctypes.data_as(C.c_void_p), C.byref(opt), C.byref(info))
+            if rc < 0:
+                raise RuntimeError("ThalloX_PlanCovariance failed: " + last_error())
+            out[key] = blocks
+            for k in ("iterations", "columns", "not_converged", "nan_blocks"):
+                out["info"][k] += int(getattr(info, k))
+            out["info"]["worst_residual"] = max(out["info"]["worst_residual"], float(info.worst_residual))
         return out
 
     def set_kernel_sampling(self, period):

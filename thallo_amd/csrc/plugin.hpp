@@ -247,6 +247,13 @@ public:
     virtual bool robust_ok() const { return false; }
     virtual int robust_prepare(int /*kind*/, float /*scale*/) { return 0; }
     virtual long robust_weights(LaunchCtx&, float* /*host_out*/, long /*n*/) { return -1; }
+    // ---- marginal covariances (ThalloX_PlanCovariance; ba_covariance.hip): plugins with an assembled Schur complement.  cov_elements: the elements of Unknown `input`
+    // (-1: not one of this energy's).  covariance, behind the GN set-up of the assembled form at the current unknowns (Plan::covariance): the blocks of the n elements
+    // ids (the caller's ids, checked) into host_out from Gc, the kept region's block factor, Ge, the elimination factor, and hold, the plan's mask or NULL; batches of
+    // thallo_hip_ba_cov_solve, whose infos are added up.  Its work buffers are the plugin's: allocated at the first call, kept, freed with it.  -> 0, or -1 with the reason set
+    virtual long cov_elements(int /*input*/) const { return -1; }
+    virtual int covariance(LaunchCtx&, int /*input*/, const int* /*ids*/, long /*n*/, const float* /*Gc*/, const float* /*Ge*/, const unsigned char* /*hold*/, float /*rel_tol*/,
+                           int /*max_iterations*/, float* /*host_out*/, thallo_cov_info_t* /*info*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale

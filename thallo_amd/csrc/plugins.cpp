@@ -1102,6 +1102,46 @@ public:
         for (int q = 0; q < O; ++q) host_out[co[(size_t)q]] = w[(size_t)q] * w[(size_t)q];
         return O;
     }
+    // ---- marginal covariances (ThalloX_PlanCovariance; ba_covariance.hip, DESIGN.md "Marginal covariances"): batches of 7 cameras or 21 points through
+    // thallo_hip_ba_cov_solve on the assembled S, W and the lists of this step's set-up.  The caller's point ids become the plan's as hold_to_internal maps a mask
+    DeviceBuffer cov_work_, cov_ids_, cov_out_;
+    unsigned* cov_pinned_ = nullptr;      // two pinned host words: the frozen counts of the two chunks in flight
+    long cov_elements(int input) const override { return input == 0 ? C : input == 1 ? P : -1; }
+    int covariance(LaunchCtx& c, int input, const int* ids, long n, const float* Gc, const float* Ge, const unsigned char* hold, float rel_tol, int max_iterations, float* host_out,
+                   thallo_cov_info_t* info) override
+    {
+        if (!sx_on_) { set_error("bundle_adjustment: a covariance needs the assembled reduced camera matrix"); return -1; }
+        const int per = input == 0 ? THALLO_HIP_COV_K / 9 : THALLO_HIP_COV_K / 3, fl = input == 0 ? 81 : 9;
+        if (!cov_work_.ptr && (cov_work_.alloc((size_t)thallo_hip_ba_cov_work_bytes(C)) || cov_ids_.alloc(sizeof(int) * THALLO_HIP_COV_K) ||
+                               cov_out_.alloc(sizeof(float) * 81 * (THALLO_HIP_COV_K / 9) + 64))) {
+            for (DeviceBuffer* b : { &cov_work_, &cov_ids_, &cov_out_ }) b->release();
+            set_error("bundle_adjustment: out of device memory for the covariance's work vectors (%ld bytes)", thallo_hip_ba_cov_work_bytes(C)); return -1;
+        }
+        if (!cov_pinned_ && hipHostMalloc((void**)&cov_pinned_, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { cov_pinned_ = nullptr; (void)hipGetLastError(); }      // (without them: a blocking read per chunk)
+        std::vector<int> in(ids, ids + n);
+        if (input == 1 && perm_) {
+            std::vector<int> old2new((size_t)P);
+            for (int j = 0; j < P; ++j) old2new[(size_t)h_new2old_[(size_t)j]] = j;
+            for (long i = 0; i < n; ++i) in[(size_t)i] = old2new[(size_t)ids[i]];
+        }
+        thallo_cov_sys_t sys;
+        sys.C = C; sys.P = P; sys.nblk = sx_nblk_; sys.row_ptr = (const int*)sx_row_ptr_.ptr; sys.col = (const int*)sx_col_.ptr; sys.S = (const float*)sx_S_.ptr;
+        sys.Gc = Gc; sys.Ge = Ge; sys.W = (const float*)sx_W_.ptr; sys.pt_ptr = (const int*)pt_ptr.ptr; sys.pt_pos = (const int*)pt_pos.ptr; sys.q_cam = (const int*)q_cam.ptr; sys.hold = hold;
+        *info = thallo_cov_info_t{ 0, 0, 0, 0, 0.0f };
+        for (long b0 = 0; b0 < n; b0 += per) {
+            const int nreq = (int)(n - b0 < per ? n - b0 : per);
+            thallo_cov_info_t bi;
+            if (hipMemcpyAsync(cov_ids_.ptr, in.data() + b0, sizeof(int) * (size_t)nreq, hipMemcpyHostToDevice, c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot upload the covariance's ids"); return -1; }
+            const int rc = thallo_hip_ba_cov_solve(&sys, input, (const int*)cov_ids_.ptr, nreq, rel_tol, max_iterations, cov_work_.ptr, cov_pinned_, (float*)cov_out_.ptr, &bi, c.stream);
+            if (rc < 0) { set_error("bundle_adjustment: the covariance's column solve failed (%d)", rc); return -1; }
+            if (hipMemcpyAsync(host_out + (size_t)fl * (size_t)b0, cov_out_.ptr, sizeof(float) * (size_t)fl * (size_t)nreq, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+                hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance blocks"); return -1; }
+            info->iterations += bi.iterations; info->columns += bi.columns; info->not_converged += bi.not_converged; info->nan_blocks += bi.nan_blocks;
+            if (!(bi.worst <= info->worst)) info->worst = bi.worst;
+        }
+        return 0;
+    }
+    ~BundleAdjustmentPlugin() override { if (cov_pinned_) (void)hipHostFree(cov_pinned_); }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }
     int shared_split_slots() const override { return thallo_hip_ba_apply2_camera_slots(C, P); }

@@ -164,6 +164,8 @@ public:
     // ThalloX_PlanSetRobustLoss: kind THALLOX_LOSS_*, scale in residual units; takes effect at the next Init.  0 = ok
     int  set_robust_loss(int kind, float scale);
     long robust_weights(float* host_out, long n);      // rho'(s) per observation of the last linearisation, the caller's ids -> O, or -1 (no loss in force, n != O)
+    // ThalloX_PlanCovariance (solver_forms.cpp): marginal covariance blocks at the current unknowns -> 0, the columns that did not converge, or < 0 (refused)
+    long covariance(void** params, int input, const int* ids, long n, float* host_out, const ThalloX_CovarianceOptions* opt, ThalloX_CovarianceInfo* info);
     // collective over the ranks; before Thallo_ProblemInit.  0 on success (every rank returns the same value)
     int  set_distributed(const ThalloX_Distributed& cfg);
     int  set_ghost_exchange(int n_boundary, const int* boundary_units, int n_ghost, const int* ghost_units, const int* ghost_src_rank, const int* ghost_src_pos);

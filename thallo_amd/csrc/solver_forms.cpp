@@ -321,4 +321,48 @@ int Plan::schur_prepare()
 
 int Plan::schur_held_points() { return schur_on_ && schur_held_ ? read_word(schur_held_) : -1; }
 
+// ------------------------------------------------------------------ marginal covariances (ba_covariance.hip, DESIGN.md "Marginal covariances")
+// Sigma = (A_FF)^-1 with A = J_s^T J_s at the current unknowns, no CtC, on an LM plan too: the call re-linearises with the launches of a GN step's head -- PCGInit1
+// (precomputeJ, `pre`) and forms_setup with shift = NULL: the mask, the block diagonal, both factors, W and the assembly -- and hands the step's S, both factors and the
+// mask to the plugin's column solve.  Everything those launches write, every step rewrites before use (r, pre, z, p, delta, diag; H, G, the status words, y, g, W, S;
+// slot 2); the LM state -- the radius and its decrease factor, SSq, CtC, b, the previous cost, prevX -- and the unknowns are not touched, no partial count is recorded, and
+// the launches are kept out of the kernel statistics, which stay the steps'.
+long Plan::covariance(void** params, int input, const int* ids, long n, float* host_out, const ThalloX_CovarianceOptions* opt, ThalloX_CovarianceInfo* info)
+{
+    if (!ok_) return -1;
+    const char* e = plugin->name();
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no assembled Schur complement to take a covariance from", e); return -1; }
+    if (!plugin->schur_ok() || plugin->cov_elements(0) < 0) { set_error("%s: no covariance for this energy (its plugin eliminates nothing and assembles no reduced matrix; bundle_adjustment does)", e); return -1; }
+    if (dist_) { set_error("%s: the covariance runs on one GPU (this plan is distributed)", e); return -1; }
+    if (!ready_) { set_error("%s: ThalloX_PlanCovariance before Thallo_ProblemInit: the covariance is taken at the unknowns of an initialised plan", e); return -1; }
+    if (!schur_on_ || !schur_explicit_) {
+        set_error("%s: the plan's last Init did not run the assembled Schur-complement solve: set ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) before Thallo_ProblemInit", e);
+        return -1;
+    }
+    const long elems = plugin->cov_elements(input);
+    if (elems < 0) { set_error("%s: input %d is not an Unknown of this energy", e, input); return -1; }
+    if (n <= 0 || !ids || !host_out) { set_error("%s: a covariance needs n > 0 ids and an output array (n = %ld)", e, n); return -1; }
+    const float rel_tol = opt ? opt->rel_tol : 1e-6f;
+    const int max_it = opt ? opt->max_iterations : 500;
+    if (!(rel_tol > 0.0f) || !std::isfinite(rel_tol)) { set_error("%s: the covariance's rel_tol must be finite and positive (got %g)", e, (double)rel_tol); return -1; }
+    if (max_it < 1) { set_error("%s: the covariance's max_iterations must be at least 1 (got %d)", e, max_it); return -1; }
+    {   std::vector<char> seen((size_t)elems, 0);
+        for (long i = 0; i < n; ++i) {
+            if (ids[i] < 0 || ids[i] >= elems) { set_error("%s: covariance id %d (at %ld) is out of range: input %d has %ld elements", e, ids[i], i, input, elems); return -1; }
+            if (seen[(size_t)ids[i]]++) { set_error("%s: covariance id %d is repeated (at %ld)", e, ids[i], i); return -1; }
+        }
+    }
+    if (params && plugin->bind(params)) { set_error("%s: parameter binding failed", e); return -1; }
+    if (!lm_) plugin->unknowns_changed();      // (as a GN step: everything is derived from the unknowns as they are now)
+    struct NoStats { LaunchCtx& c; KernelTimer* t; NoStats(LaunchCtx& ctx) : c(ctx), t(ctx.timer) { c.timer = nullptr; } ~NoStats() { c.timer = t; } } no_stats(ctx);
+    int nb = plugin->pcg_init(ctx, v_, 0, slot(2));
+    if (nb < 0) { set_error("%s: covariance: PCGInit1 launch failed (%d)", e, nb); return -1; }
+    const char* what = nullptr;
+    if ((nb = forms_setup(nullptr, v_.r, slot(2), nb, what)) < 0) { set_error("%s: covariance: %s failed (%d)", e, what, nb); return -1; }
+    thallo_cov_info_t ci;
+    if (plugin->covariance(ctx, input, ids, n, block_G_, schur_Ge_, held_on() ? held_mask_ : nullptr, rel_tol, max_it, host_out, &ci)) return -1;
+    if (info) { info->iterations = ci.iterations; info->columns = ci.columns; info->not_converged = ci.not_converged; info->nan_blocks = ci.nan_blocks; info->worst_residual = ci.worst; }
+    return ci.not_converged;
+}
+
 }  // namespace thallo
