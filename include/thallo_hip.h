@@ -401,6 +401,11 @@ void thallo_hip_resident_debug_set(int what, int value);    /* tools / tests onl
 /* rows per wave segment the marching kernels use on `rows` owned rows of a W-wide image; 0 = more column strips than the device has workgroup
  * slots: the marching kernels return -hipErrorNotSupported, the caller stays on THALLO_IW_ITER_TILE (host logic, no launch) */
 int thallo_hip_iw_march_rows(int W, int rows);
+/* where the marching kernels put every wave of a launch of `grid` workgroups (4 waves each) over the owned rows [row0, row1) of a W-wide image at R rows per
+ * wave segment -- the kernels' own placement code compiled for the host: place[3 (4 b + w) + 0 .. 2] = column strip, first row, end row of wave w of workgroup b
+ * (first == end: the wave has no rows).  0, or -hipErrorInvalidValue for what no launcher runs: a grid that is not a multiple of 8 or exceeds 1024 workgroups, more
+ * (strip, band of 4 segments) ids than 1024.  Host logic, no launch: tests/test_march_place.py */
+int thallo_hip_iw_march_place(int W, int row0, int row1, int R, int grid, int* place);
 int thallo_hip_iw_pcg_iter_finish(const float* alphaD_partials, const double* s12_partials, int count, thallo_sum_t alphaN,
                                   float* alphaD_word, float* betaN_word, thallo_stream_t stream);
 

@@ -69,16 +69,12 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
     __shared__ float red[16];
     __shared__ double redd[48];
     constexpr bool nt_delta = NTM & 1, nt_ra = NTM & 2, nt_out = NTM & 4, nt_pin = NTM & 8, nt_pout = NTM & 16, nt_const = NTM & 32;
-    // this kernel is the unit-pixel-grid form only; the caller checked that at Init.  Should the word pcg_init wrote this GN step say
-    // otherwise, poison the scalars (NaN cost downstream) instead of computing with the wrong Jacobian.
-    if (irregular != nullptr && __builtin_amdgcn_readfirstlane(irregular[0]) != 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0 && aD_word) { aD_word[0] = __builtin_nanf(""); bN_word[0] = __builtin_nanf(""); }
-        if (blockIdx.x == 0 && threadIdx.x == 0 && prev.count > 0) { prev.aD_word[0] = __builtin_nanf(""); prev.bN_word[0] = __builtin_nanf(""); }
-        if (threadIdx.x == 0) { aD_out[blockIdx.x] = __builtin_nanf(""); }
-        return;
-    }
-    if (threadIdx.x < 32) { float mo, ma; pre_from_flags((unsigned char)threadIdx.x, wf2, wr2, mo, ma); lut[threadIdx.x] = make_float2(mo, ma); }
-    __syncthreads();
+    // The head of the launch: the word pcg_init wrote this GN step is REQUESTED first (a round trip right behind the launch boundary); the placement and the
+    // address set-up run while it is on its way, and it is looked at in front of the M^-1 table.  (The recomputing kernel also has its first rows' loads in
+    // front of the table; here they stay the loop's first refills: see the loop.)
+    int irregular_word = 0;
+    if (irregular != nullptr) irregular_word = irregular[0];
+    fence_order();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long N = (long)g.W * g.H;
@@ -99,6 +95,18 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
     float4* __restrict__ Ao4 = reinterpret_cast<float4*>(A_out);  float2* __restrict__ Aa2 = reinterpret_cast<float2*>(A_out + 2 * N);
     float4* __restrict__ qo4 = reinterpret_cast<float4*>(p_out);  float2* __restrict__ qa2 = reinterpret_cast<float2*>(p_out + 2 * N);
     float4* __restrict__ dl4 = reinterpret_cast<float4*>(delta);  float2* __restrict__ dl2 = reinterpret_cast<float2*>(delta + 2 * N);
+
+    // This kernel is the unit-pixel-grid form only; the caller checked that at Init.  Should the word pcg_init wrote this GN step say otherwise, poison the
+    // scalars (NaN cost downstream) instead of computing with the wrong Jacobian.
+    fence_order();
+    if (__builtin_amdgcn_readfirstlane(irregular_word) != 0) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && aD_word) { aD_word[0] = __builtin_nanf(""); bN_word[0] = __builtin_nanf(""); }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && prev.count > 0) { prev.aD_word[0] = __builtin_nanf(""); prev.bN_word[0] = __builtin_nanf(""); }
+        if (threadIdx.x == 0) { aD_out[blockIdx.x] = __builtin_nanf(""); }
+        return;
+    }
+    if (threadIdx.x < 32) { float mo, ma; pre_from_flags((unsigned char)threadIdx.x, wf2, wr2, mo, ma); lut[threadIdx.x] = make_float2(mo, ma); }
+    __syncthreads();
 
     float alpha = 0.0f, beta = 0.0f, alpha2 = 0.0f;
     // alpha, beta are added up inside the row loop, behind the first three rows' loads (see there) -- except in the "apply two delta updates" variant,
@@ -223,7 +231,9 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
         // t_last are clamped re-reads of the last row (cache hits) whose publish / stencil are predicated off.
         // There is no prologue either: the loop starts three rows early with empty slots (publish predicated off) and its refills are
         // the first loads.  A separate prologue is a second path into the loop header with its own (compiler-scheduled) issue order,
-        // and the wait at the header is the conservative merge of both paths -- in practice vmcnt(0).
+        // and the wait at the header is the conservative merge of both paths -- in practice vmcnt(0).  (Tried again when the recomputing kernel's
+        // first rows went in front of its table: with the three rows requested ahead of the table and the barrier, the slots' registers no longer
+        // coalesce with the loop's and two of them are copied at the loop latch behind an s_waitcnt vmcnt(1) -- every trip then waits for all its rows.)
         // Entering an iteration at row t0: win[0] = row t0-2, win[1] = row t0-1.
 #pragma unroll
         for (int j = 0; j < 3; ++j) { slot[j] = RawT{}; dsl[j] = RawD{}; }

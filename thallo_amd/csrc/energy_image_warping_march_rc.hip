@@ -42,6 +42,10 @@ template <bool NT> __device__ __forceinline__ void bst2(rsrc_t r, unsigned vo, u
 { u32x2 v; v.x = __float_as_uint(a); v.y = __float_as_uint(b); __builtin_amdgcn_raw_buffer_store_b64(v, r, vo, so, NT ? 2 : 0); }
 __device__ __forceinline__ float uf(unsigned u) { return __uint_as_float(u); }
 __device__ __forceinline__ float to_sgpr(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+// (pairs move as pairs: one v_mov_b64 per two words, and {x, y} / {c, s} stay in an aligned register pair for the packed arithmetic)
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void take4u(u32x4& d, const u32x4& s) { const u64x2 sv = __builtin_bit_cast(u64x2, s); unsigned long long a, b; take_pair(a, sv.x); take_pair(b, sv.y); u64x2 dv; dv.x = a; dv.y = b; d = __builtin_bit_cast(u32x4, dv); }
+__device__ __forceinline__ void take2u(u32x2& d, const u32x2& s) { unsigned long long a; take_pair(a, __builtin_bit_cast(unsigned long long, s)); d = __builtin_bit_cast(u32x2, a); }
 
 // iteration_scalars (iw_device.hpp) in a lean form: sums are added up by a ROLLED loop with one load in flight (the same additions in the same order as
 // sum_partials / k_iter_finish; finished sums are one word; alphaN_0 and iteration k-1's raw partials are at most a few per lane).  The general routine keeps 16
@@ -53,15 +57,67 @@ __device__ __forceinline__ float rc_sum(thallo_sum_t s)
     for (int i = threadIdx.x & (THALLO_WAVE - 1); i < s.count; i += THALLO_WAVE) t += s.partials[i];
     return wave_sum_all(t);
 }
-__device__ __forceinline__ void rc_iteration_scalars(thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, const PrevSums& prev, float& alpha, float& beta, bool writer)
+// The raw partials of iteration k-1 (prev.count > 0), REQUESTED right behind the first rows' loads: the first RC_AHEAD slots of every lane -- all of them on grids of
+// up to 64 RC_AHEAD workgroups -- and the lane's alphaN_{k-1} slot.  A lane without a slot re-reads slot 0 (unconditional loads, as the rows'); rc_iteration_scalars
+// adds the values up where and in the order it always did, so they have the two entering row steps to arrive in instead of one round trip after the other behind them.
+constexpr int RC_AHEAD = 4;
+#ifdef THALLO_RC_SUMS_LATE
+constexpr bool RC_SUMS_AHEAD = false;
+#else
+constexpr bool RC_SUMS_AHEAD = true;
+#endif
+// (raw words, as the rows' slots: a value the optimiser can read it starts to add to -- 0 + slot 0 -- inside the requesting block, i.e. it waits for the loads
+//  where they were issued; rc_prev_arrive moves a slot into fresh registers with real v_mov instructions, and only those copies are arithmetic operands)
+struct PrevAhead { unsigned an, ad[RC_AHEAD]; unsigned long long s[RC_AHEAD][3]; };      // alphaN slot; per slot alphaD and the words of N, S1, S2
+__device__ __forceinline__ void rc_prev_request(thallo_sum_t aNp, const PrevSums& prev, PrevAhead& a)
 {
-    const float an = rc_sum(aNp);
-    float ad, bn;
+    const int lane = threadIdx.x & (THALLO_WAVE - 1), nb = prev.count;
+    a.an = __float_as_uint(aNp.partials[lane < aNp.count ? lane : 0]);
+#pragma unroll
+    for (int u = 0; u < RC_AHEAD; ++u) {
+        const int i = lane + u * THALLO_WAVE, ic = i < nb ? i : 0;
+        a.ad[u] = __float_as_uint(prev.aD_part[ic]);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a.s[u][q] = __builtin_bit_cast(unsigned long long, prev.s12_part[3 * ic + q]);
+    }
+}
+__device__ __forceinline__ float rc_sum_ahead(thallo_sum_t s, float first)      // rc_sum with the lane's first slot already loaded
+{
+    if (s.count == 1) return first;
+    const int lane = threadIdx.x & (THALLO_WAVE - 1);
+    float t = 0.0f;
+    if (lane < s.count) t += first;
+    for (int i = lane + THALLO_WAVE; i < s.count; i += THALLO_WAVE) t += s.partials[i];
+    return wave_sum_all(t);
+}
+__device__ __forceinline__ void rc_prev_arrive(const PrevAhead& a, int u, float& ad, double& n, double& s1, double& s2)
+{
+    unsigned w; unsigned long long d[3];
+    take1(w, a.ad[u]); take_pair(d[0], a.s[u][0]); take_pair(d[1], a.s[u][1]); take_pair(d[2], a.s[u][2]);
+    ad = uf(w); n = __builtin_bit_cast(double, d[0]); s1 = __builtin_bit_cast(double, d[1]); s2 = __builtin_bit_cast(double, d[2]);
+}
+template <bool AHEAD>
+__device__ __forceinline__ void rc_iteration_scalars(thallo_sum_t aNp, thallo_sum_t aDp, thallo_sum_t bNp, const PrevSums& prev, const PrevAhead& ah, float& alpha, float& beta, bool writer)
+{
+    float an, ad, bn;
     if (prev.count > 0) {
         const int lane = threadIdx.x & (THALLO_WAVE - 1), nb = prev.count;
         float t = 0.0f; double n = 0.0, a1 = 0.0, b1 = 0.0;
-        for (int i = lane; i < nb; i += THALLO_WAVE) { t += prev.aD_part[i]; n += prev.s12_part[3 * i]; a1 += prev.s12_part[3 * i + 1]; b1 += prev.s12_part[3 * i + 2]; }
-        ad = nb == 1 ? prev.aD_part[0] : wave_sum_all(t);
+        int i = lane;
+        float ad0 = 0.0f;                                   // slot 0 (a lane without one re-read it: the launch's alphaD where there is one workgroup)
+        if (AHEAD) {
+            unsigned wn; take1(wn, ah.an);
+            an = rc_sum_ahead(aNp, uf(wn));
+#pragma unroll
+            for (int u = 0; u < RC_AHEAD; ++u, i += THALLO_WAVE) {
+                float vd; double v0, v1, v2;
+                rc_prev_arrive(ah, u, vd, v0, v1, v2);
+                if (u == 0) ad0 = vd;
+                if (i < nb) { t += vd; n += v0; a1 += v1; b1 += v2; }
+            }
+        } else an = rc_sum(aNp);
+        for (; i < nb; i += THALLO_WAVE) { t += prev.aD_part[i]; n += prev.s12_part[3 * i]; a1 += prev.s12_part[3 * i + 1]; b1 += prev.s12_part[3 * i + 2]; }
+        ad = nb == 1 ? (AHEAD ? ad0 : prev.aD_part[0]) : wave_sum_all(t);
         n = wave_sum_all_d(n); a1 = wave_sum_all_d(a1); b1 = wave_sum_all_d(b1);
         alpha = safe_div<false>(an, ad);
         double bd = n - 2.0 * (double)alpha * a1 + (double)alpha * (double)alpha * b1;
@@ -69,7 +125,7 @@ __device__ __forceinline__ void rc_iteration_scalars(thallo_sum_t aNp, thallo_su
         bn = (float)bd;
         if (writer) { prev.aD_word[0] = ad; prev.bN_word[0] = bn; }      // writer: exactly ONE thread of the launch, one that certainly gets here
     } else {
-        ad = rc_sum(aDp); bn = rc_sum(bNp);
+        an = rc_sum(aNp); ad = rc_sum(aDp); bn = rc_sum(bNp);
         alpha = safe_div<false>(an, ad);
     }
     beta = safe_div<false>(bn, an);
@@ -129,10 +185,6 @@ struct RawRc {                              // what one step takes, for one lane
     u32x4 ro; u32x2 ra;                     // row t-1: r_{k-1}
     u32x4 dlo, ppo; u32x2 dla, ppa;         // row t-1: delta (DMODE 0, 2) and p_{k-2} (DMODE 2)
 };
-// (pairs move as pairs: one v_mov_b64 per two words, and {x, y} / {c, s} stay in an aligned register pair for the packed arithmetic)
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void take4u(u32x4& d, const u32x4& s) { const u64x2 sv = __builtin_bit_cast(u64x2, s); unsigned long long a, b; take_pair(a, sv.x); take_pair(b, sv.y); u64x2 dv; dv.x = a; dv.y = b; d = __builtin_bit_cast(u32x4, dv); }
-__device__ __forceinline__ void take2u(u32x2& d, const u32x2& s) { unsigned long long a; take_pair(a, __builtin_bit_cast(unsigned long long, s)); d = __builtin_bit_cast(u32x2, a); }
 template <int DMODE>
 __device__ __forceinline__ void take(RawRc<DMODE>& d, const RawRc<DMODE>& s)
 {
@@ -171,15 +223,12 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
     __shared__ float red[16];
     __shared__ double redd[48];
     constexpr bool nt_delta = NTM & 1, nt_ra = NTM & 2, nt_out = NTM & 4, nt_pin = NTM & 8, nt_pout = NTM & 16, nt_const = NTM & 32;
-    // unit-pixel-grid form only; should the word pcg_init wrote this GN step say otherwise, poison the scalars (NaN cost downstream)
-    if (irregular != nullptr && __builtin_amdgcn_readfirstlane(irregular[0]) != 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0 && aD_word) { aD_word[0] = __builtin_nanf(""); bN_word[0] = __builtin_nanf(""); }
-        if (blockIdx.x == 0 && threadIdx.x == 0 && prev.count > 0) { prev.aD_word[0] = __builtin_nanf(""); prev.bN_word[0] = __builtin_nanf(""); }
-        if (threadIdx.x == 0) { aD_out[blockIdx.x] = __builtin_nanf(""); }
-        return;
-    }
-    if (threadIdx.x < 32) { float mo, ma; pre_from_flags((unsigned char)threadIdx.x, wf2, wr2, mo, ma); lut[threadIdx.x] = make_float4(mo, ma, (threadIdx.x & 2) ? wf2 : 0.f, 0.f); }
-    __syncthreads();
+    // The head of the launch -- every wave of the grid is here at the same time with nothing in flight -- is ordered by what it waits for: the word pcg_init wrote
+    // this GN step is REQUESTED first (a cold round trip right behind the launch boundary), then come the placement and the loads of the wave's first DEPTH rows, and
+    // only behind those the word is looked at, the M^-1 table is built and the workgroup meets at its barrier.  None of the row loads depends on the three.
+    int irregular_word = 0;
+    if (irregular != nullptr) irregular_word = irregular[0];
+    fence_order();
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned N = (unsigned)g.W * (unsigned)g.H;         // (12 N < 2^32: host-checked)
@@ -230,6 +279,27 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
             if (DMODE == 2) { s.ppo = bld4<false>(RS_Q, vo16, drow * 16u); s.ppa = bld2<false>(RS_Q, vo8, angle0 + drow * 8u); }
         }
     };
+
+    // head: the loads of the first DEPTH rows, nothing else (a wave without rows loads nothing)
+    PrevAhead ahead;                                           // (read only where it was requested)
+    if (work) {
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) issue(slot[i], t_first + i, IC<1>{});
+        fence_order();                                         // (the rows need the first round of kernel arguments only: nothing of the second in front of them)
+        if (RC_SUMS_AHEAD && prev.count > 0 && !(SLAB == 2 && prev.gs != nullptr)) rc_prev_request(aNp, prev, ahead);
+    }
+    fence_order();
+    // ... and, while they are in flight, what the launch's head used to start with.
+    // Unit-pixel-grid form only; should the word pcg_init wrote this GN step say otherwise, poison the scalars (NaN cost downstream).  Nothing was stored yet
+    // and nothing is: the rows in flight land in registers nobody reads.
+    if (__builtin_amdgcn_readfirstlane(irregular_word) != 0) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && aD_word) { aD_word[0] = __builtin_nanf(""); bN_word[0] = __builtin_nanf(""); }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && prev.count > 0) { prev.aD_word[0] = __builtin_nanf(""); prev.bN_word[0] = __builtin_nanf(""); }
+        if (threadIdx.x == 0) { aD_out[blockIdx.x] = __builtin_nanf(""); }
+        return;
+    }
+    if (threadIdx.x < 32) { float mo, ma; pre_from_flags((unsigned char)threadIdx.x, wf2, wr2, mo, ma); lut[threadIdx.x] = make_float4(mo, ma, (threadIdx.x & 2) ? wf2 : 0.f, 0.f); }
+    lds_barrier();      // (LDS only: __syncthreads() would also wait for the rows in flight)
 
     // rings of four rows, indexed by the row's position inside a trip of four (compile-time)
     PRow pp[4], pk[4]; GRow gg[4]; RRow rr[2];
@@ -368,15 +438,13 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march_rc(MarchGeo g, con
     if (SLAB == 2 && prev.gs != nullptr && prev.count > 0 && blockIdx.x == gridDim.x - 1 && wave == 0 && !work) rc_exchange_prev(aNp, prev, dd);
 
     if (work) {
-        // head: the loads of the first DEPTH rows, nothing else; rows ya-2, ya-1 enter the rings
-#pragma unroll
-        for (int i = 0; i < DEPTH; ++i) issue(slot[i], t_first + i, IC<1>{});
+        // rows ya-2, ya-1 (requested at the launch's head) enter the rings
         step(t_first, IC<0>{}, IC<PH_ENTER>{}, IC<1>{});
         step(t_first + 1, IC<1>{}, IC<PH_ENTER>{}, IC<1>{});
         // The iteration's scalars, behind the loads of the first rows: rows ya-2, ya-1 need neither alpha nor beta; the partial loads queue up behind those
         // row loads and the additions run while the rows arrive.  Wave-uniform: kept in SGPRs.
         if (SLAB == 2 && prev.gs != nullptr && prev.count > 0) rc_iteration_scalars_x(aNp, prev, dd, alpha, beta);
-        else rc_iteration_scalars(aNp, aDp, bNp, prev, alpha, beta, scal_writer);
+        else rc_iteration_scalars<RC_SUMS_AHEAD>(aNp, aDp, bNp, prev, ahead, alpha, beta, scal_writer);
         alpha = to_sgpr(alpha); beta = to_sgpr(beta);
         if (DMODE == 2) alpha2 = to_sgpr(safe_div<false>(rc_sum(aNpp), rc_sum(aDpp)));
         step(ya, IC<2>{}, IC<PH_S1>{}, IC<1>{});
@@ -497,6 +565,20 @@ int thallo_hip_iw_march_rc_deferred_fits(int W, int rows)
     const MarchGeo g = make_march_geo(W, rows, 0, rows, R);
     const long grid = (g.total + 7) / 8 * 8 + 8;
     return grid <= march_cap(MARCH_RC_OCC) && grid <= THALLO_MAX_PARTIALS ? 1 : 0;
+}
+
+/* The placement the marching kernels run (march_place_at: the same body, compiled for the host), for every wave of a launch of `grid` workgroups over the owned rows
+ * [row0, row1) of a W-wide image at R rows per wave segment: place[3 (4 b + w) + 0 .. 2] = strip, ya, yb of wave w of workgroup b (ya == yb: no rows).  Refuses what no
+ * launcher runs: a grid that is not a multiple of 8 or has more than THALLO_MAX_PARTIALS workgroups, more (strip, band of segments) ids than that.  Host logic, no launch. */
+int thallo_hip_iw_march_place(int W, int row0, int row1, int R, int grid, int* place)
+{
+    if (W < 2 || (W & 1) || row0 < 0 || row1 <= row0 || R < 1 || grid < 8 || (grid & 7) || grid > THALLO_MAX_PARTIALS || !place) return -(int)hipErrorInvalidValue;
+    const long nstrips = (W + MARCH_USE - 1) / MARCH_USE, nseg = ((long)row1 - row0 + R - 1) / R;
+    if (nstrips * ((nseg + MARCH_NT / 64 - 1) / (MARCH_NT / 64)) > THALLO_MAX_PARTIALS) return -(int)hipErrorInvalidValue;
+    const MarchGeo g = make_march_geo(W, row1, row0, row1, R);
+    for (int b = 0; b < grid; ++b)
+        for (int w = 0; w < MARCH_NT / 64; ++w) { int* o = place + 3 * ((MARCH_NT / 64) * b + w); march_place_at(g, (unsigned)b, w, o[0], o[1], o[2]); }
+    return 0;
 }
 
 int thallo_hip_iw_dist_finish_deferred(thallo_prev_t prev, int prev_slot0, thallo_sum_t aNp, thallo_dist_t d, unsigned long long* gs, thallo_stream_t stream)

@@ -162,25 +162,40 @@ __device__ __forceinline__ void iter_sums_pixel_masked(float msum, float pxi, fl
     s2 = __builtin_fma(dmo, __builtin_fma(day, day, dax * dax), __builtin_fma(dma, daa * daa, s2));
 }
 
-struct MarchGeo { int W, H, row0, row1, R, nstrips, nwgrow, total; };
+struct MarchGeo { int W, H, row0, row1, R, nstrips, nwgrow, total; unsigned strip_magic; };
 
 // XCD-aware placement: workgroups b and b+8 share an XCD (MI355X_MICROARCH.md), group b%8 owns a contiguous range of (band of 4 segments, strip) ids,
 // x-adjacent strips first: x-halo columns and y-halo rows are re-read from the same L2.  Returns the wave's strip and its rows [ya, yb) (empty: no work).
-__device__ __forceinline__ void march_place(const MarchGeo& g, int wave, int& strip, int& ya, int& yb)
+// Every launcher rounds its grid up to a multiple of 8 workgroups, so there are always eight groups (a grid that is not one has no launcher: the host
+// mirror refuses it) and group grp owns the ids [total grp / 8, total (grp + 1) / 8).
+// The placement sits in front of a launch's first load, so it is 32-bit arithmetic without a division: total <= THALLO_MAX_PARTIALS = 2^10 (the launchers
+// refuse larger grids), hence id < 2^10 and nstrips <= 2^10, and id / nstrips = (id * strip_magic) >> 20 with the host's strip_magic = 2^20 / nstrips + 1:
+// strip_magic * nstrips = 2^20 + e with 0 < e <= nstrips, so id * strip_magic / 2^20 = id / nstrips + id e / (2^20 nstrips); id / nstrips lies at least
+// 1 / nstrips below the next integer and id e < 2^20, so the floor is the quotient (id * strip_magic < 2^31; tests/test_march_place.py walks every grid).
+// One body for the kernels and for the host mirror thallo_hip_iw_march_place.
+constexpr int MARCH_PLACE_SHIFT = 20;
+// workgroup `block`'s (band, strip) id; false: its group's range is used up, the workgroup has no rows
+__host__ __device__ __forceinline__ bool march_block_id(const MarchGeo& g, unsigned block, unsigned& id)
+{
+    const unsigned grp = block & 7u, l = block >> 3;
+    const unsigned total = (unsigned)g.total, lo = (total * grp) >> 3, hi = (total * (grp + 1u)) >> 3;
+    id = lo + l;
+    return id < hi;
+}
+__host__ __device__ __forceinline__ void march_place_at(const MarchGeo& g, unsigned block, int wave, int& strip, int& ya, int& yb)
 {
     strip = 0; ya = 0; yb = 0;
-    const int G = (gridDim.x % 8) == 0 ? 8 : 1;
-    const int grp = blockIdx.x % G, l = blockIdx.x / G;
-    const long lo = (long)g.total * grp / G, hi = (long)g.total * (grp + 1) / G;
-    const long id = lo + l;
-    if (id < hi) {
-        strip = (int)(id % g.nstrips);
-        const int seg = (int)(id / g.nstrips) * (MARCH_NT / 64) + wave;
+    unsigned id;
+    if (march_block_id(g, block, id)) {
+        const unsigned band = (id * g.strip_magic) >> MARCH_PLACE_SHIFT;
+        strip = (int)(id - band * (unsigned)g.nstrips);
+        const int seg = (int)band * (MARCH_NT / 64) + wave;
         ya = g.row0 + seg * g.R; yb = ya + g.R;
         if (yb > g.row1) yb = g.row1;
         if (ya > g.row1) ya = g.row1;
     }
 }
+__device__ __forceinline__ void march_place(const MarchGeo& g, int wave, int& strip, int& ya, int& yb) { march_place_at(g, blockIdx.x, wave, strip, ya, yb); }
 
 inline MarchGeo make_march_geo(int W, int H, int row0, int row1, int R)
 {
@@ -189,6 +204,7 @@ inline MarchGeo make_march_geo(int W, int H, int row0, int row1, int R)
     const int nseg = (row1 - row0 + R - 1) / R;
     g.nwgrow = (nseg + MARCH_NT / 64 - 1) / (MARCH_NT / 64);
     g.total = g.nstrips * g.nwgrow;
+    g.strip_magic = (1u << MARCH_PLACE_SHIFT) / (unsigned)g.nstrips + 1u;
     return g;
 }
 

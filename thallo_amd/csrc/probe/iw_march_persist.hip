@@ -157,8 +157,7 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_march_persist(PersistArgs a)
     // which workgroup slots carry rows (march_place: slot b -> id).  A slot without rows never publishes -- the sweeps of the others know, its sums are zeros --
     // and leaves the zeros of the launch's last iteration where a launch per iteration would
     const int grid = (int)gridDim.x;
-    const int G = (grid % 8) == 0 ? 8 : 1;
-    auto slot_has_rows = [&](int b) { const int grp = b % G, l = b / G; const long lo = (long)g.total * grp / G, hi = (long)g.total * (grp + 1) / G; return lo + l < hi; };
+    auto slot_has_rows = [&](int b) { unsigned id; return march_block_id(g, (unsigned)b, id); };
     if (!slot_has_rows((int)blockIdx.x)) {
         if (threadIdx.x == 0) {
             float* aD_out = a.parts + (size_t)(a.B + 2 * (a.k1 - 1) + 1) * THALLO_MAX_PARTIALS; double* s12_out = a.s12[(a.k1 - 1) & 1];
