@@ -666,8 +666,8 @@ int thallo_hip_pcg_update_fin(float* r, const float* Ap, const float* pre, const
                               const float* alphaD_partials, const double* s3_partials, int count, float* alphaD_word, float* betaN_word, thallo_stream_t stream);
 /* the applyJTJ entry points of E2 / E3 / E4 (argument meaning as in the plain forms below) that also return the three sums */
 /* Round 3: applyJTJ with the per-edge G block RECOMPUTED from the source vertex's sines / cosines (SC: [sin a, sin b, sin g] per vertex, then the cosines; written by
- * thallo_hip_arap_precompute2) and dv = Original differences, instead of 2 x 36 streamed bytes per edge; ELL layout with at most 8 edge slots per vertex
- * (thallo_hip_arap_recompute_supported).  s3_out == NULL: alphaD partials only; else the three sums of the single-reduction form and, with fin.tickets, the scalars.
+ * thallo_hip_arap_precompute2) and dv = Original differences, instead of 2 x 36 streamed bytes per edge; ELL layout with at most 8 OUT-edge slots per vertex
+ * (ell_stride / N; thallo_hip_arap_recompute_supported) -- the in-lists of a directed graph may have more, any number.  s3_out == NULL: alphaD partials only; else the three sums of the single-reduction form and, with fin.tickets, the scalars.
  * Same terms in the same order as thallo_hip_arap_apply_jtj(_sums_fin) (thallo.t:3536-3569's sums, gathered per vertex). */
 int thallo_hip_arap_precompute2(int N, const int* out_ptr, const int* out_v1, const float* position, const float* angle,
                                 const float* original, float w_reg, float* F, float* G, float* SC, long ell_stride, thallo_stream_t stream);

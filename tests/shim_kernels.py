@@ -1,4 +1,5 @@
-"""Shared helper of the per-kernel tests (test_gpu_pcg_chain.py, test_gpu_transport_kernels.py, test_gpu_sparse_kernels.py, test_shim_references.py).
+"""Shared helper of the per-kernel tests (test_gpu_pcg_chain.py, test_gpu_transport_kernels.py, test_gpu_sparse_kernels.py, test_gpu_graph_kernels.py,
+test_shim_references.py).
 
 Four things live here:
   * shim(): the library with argtypes / restype declared once for every thallo_hip.h entry point those files call;
@@ -36,6 +37,13 @@ class UnitsT(C.Structure):       # thallo_units_t
 class UpdateTermsT(C.Structure):     # thallo_update_terms_t
     _fields_ = [("p", C.c_void_p * MAX_UPDATE_TERMS), ("alphaN", api.SumT * MAX_UPDATE_TERMS), ("alphaD", api.SumT * MAX_UPDATE_TERMS), ("count", C.c_int)]
 
+
+class FinT(C.Structure):             # thallo_fin_t
+    _fields_ = [("alphaN", api.SumT), ("tickets", C.c_void_p), ("alphaD_word", C.c_void_p), ("betaN_word", C.c_void_p)]
+
+
+NO_FIN = FinT(api.SumT(None, 0), None, None, None)
+FIN_TICKET_WORDS = 528           # THALLO_HIP_FIN_TICKET_WORDS
 
 _SHIM = None
 
@@ -91,16 +99,33 @@ def shim():
         "jtj_scatter": [lg, it, vp, vp, vp, vp],
         "incidence_count": [vp, lg, it, C.POINTER(C.c_long), C.POINTER(C.c_int), lg, vp, vp, vp],      # slot_base / slot_ch: HOST arrays
         "incidence_fill": [vp, lg, it, C.POINTER(C.c_long), C.POINTER(C.c_int), lg, vp, vp, vp, vp],
+        # the graph-edge domains (csrc/energy_graph.hip; test_gpu_graph_kernels.py)
+        "lapgraph_cost": [it] + [vp] * 4 + [fl, vp, vp],
+        "lapgraph_pcg_init": [it] + [vp] * 6 + [fl] + [vp] * 7,
+        "lapgraph_apply_jtj": [it] + [vp] * 4 + [fl] + [vp] * 4,
+        "arap_cost": [it] * 3 + [vp] * 6 + [fl, fl, vp, lg, vp],
+        "arap_precompute": [it] + [vp] * 5 + [fl, vp, vp, lg, vp],
+        "arap_precompute2": [it] + [vp] * 5 + [fl, vp, vp, vp, lg, vp],
+        "arap_recompute_supported": [it, lg],
+        "arap_pcg_init": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 7 + [lg, vp],
+        "arap_apply_jtj": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 3 + [lg, vp],
+        "arap_apply_jtj_sums": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 3 + [lg] + [vp] * 4,
+        "arap_apply_jtj_sums_fin": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 3 + [lg] + [vp] * 3 + [FinT, vp],
+        "arap_apply_jtj_rc": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 3 + [lg] + [vp] * 3 + [FinT, vp],
+        "arap_debug_set": [it, it],
+        "permute3": [it, vp, vp, vp, it, vp],
+        "checksum_i32": [lg, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, "thallo_hip_" + name)
         f.argtypes = args
-        f.restype = None if name == "lm_set_gate" else lg if name == "vector_elems" else it
+        f.restype = None if name in ("lm_set_gate", "arap_debug_set") else lg if name == "vector_elems" else it
     _SHIM = L
     return L
 
 
 INVALID = -1          # -hipErrorInvalidValue
+NOT_SUPPORTED = -801  # -hipErrorNotSupported
 
 
 def sumt(t, count=None):

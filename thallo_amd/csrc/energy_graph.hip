@@ -318,8 +318,8 @@ __global__ __launch_bounds__(BLOCK) void k_arap_apply(int N, int n0, int n1, con
     else block_store_partial(acc, aD_out, red);
 }
 
-// The same J^T J p for the ELL layout with at most MD edge slots per vertex (S = maxdeg * N, maxdeg <= MD): both edge loops fully unrolled with
-// the slots beyond a vertex's degree predicated off, so that every index load of a vertex is issued first, then every gather that depends on
+// The same J^T J p for the ELL layout with at most MD OUT-edge slots per vertex (S = maxdeg * N, maxdeg <= MD): both edge loops fully unrolled over MD slots with
+// the slots beyond a vertex's degree predicated off (incoming edges beyond MD -- the in-lists are sized by the max in-degree -- follow in a plain loop), so that every index load of a vertex is issued first, then every gather that depends on
 // them, then the arithmetic -- two dependent memory round trips per vertex instead of one pair per group of four edges (the kernel is latency-bound:
 // 13 MB working set, 1.6 waves per SIMD).  Same terms in the same order: bitwise the loop form's output.
 template <int MD>
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(BLOCK) void k_arap_apply_ell(int N, int n0, int n1,
         f3 ap = { 0.f, 0.f, 0.f }, aa = { 0.f, 0.f, 0.f };
 #pragma unroll
         for (int j = 0; j < MD; ++j) {
-            const long k = (long)j * L.N + n;
+            const long k = j < deg ? (long)j * L.N + n : n;       // (a slot beyond the degree reads the vertex's first one: with fewer than MD out-slots, j*N + n lies behind the planes)
             const f3 pm = pmo[j];
             const f3 g0 = ldG(G, L, k, 0), g1 = ldG(G, L, k, 1), g2 = ldG(G, L, k, 2);
             const float jx = (pp.x - pm.x) - (g0.x * pa.x + g1.x * pa.y + g2.x * pa.z);
@@ -371,6 +371,15 @@ __global__ __launch_bounds__(BLOCK) void k_arap_apply_ell(int N, int n0, int n1,
                 ap.y -= (pm.y - pp.y) - (g0.y * am.x + g1.y * am.y + g2.y * am.z);
                 ap.z -= (pm.z - pp.z) - (g0.z * am.x + g1.z * am.y + g2.z * am.z);
             }
+        }
+        for (int j = MD; j < ideg; ++j) {      // a directed graph: the in-lists have slots of their own (max in-degree), which may be more than MD -- the rest of them, as the loop form
+            const long k = (long)j * L.N + n;
+            const int e = in_edge[k], m = in_src[k];
+            const f3 pm = ld3(p, m), am = ld3(p, (long)N + m);
+            const f3 g0 = ldG(G, L, e, 0), g1 = ldG(G, L, e, 1), g2 = ldG(G, L, e, 2);
+            ap.x -= (pm.x - pp.x) - (g0.x * am.x + g1.x * am.y + g2.x * am.z);
+            ap.y -= (pm.y - pp.y) - (g0.y * am.x + g1.y * am.y + g2.y * am.z);
+            ap.z -= (pm.z - pp.z) - (g0.z * am.x + g1.z * am.y + g2.z * am.z);
         }
         ap.x *= wr2; ap.y *= wr2; ap.z *= wr2; aa.x *= wr2; aa.y *= wr2; aa.z *= wr2;
         if (Cn[3 * n] >= -999999.9f) { ap.x += wf * wf * pp.x; ap.y += wf * wf * pp.y; ap.z += wf * wf * pp.z; }
@@ -466,6 +475,16 @@ __global__ __launch_bounds__(BLOCK) void k_arap_apply_rc(int N, int n0, int n1, 
                 ap.y -= (pm.y - pp.y) - (g0.y * am.x + g1.y * am.y + g2.y * am.z);
                 ap.z -= (pm.z - pp.z) - (g0.z * am.x + g1.z * am.y + g2.z * am.z);
             }
+        }
+        for (int j = MD; j < ideg; ++j) {      // in-slots beyond MD (a directed graph, as in k_arap_apply_ell): same expressions
+            const int m = in_src[(long)j * L.N + n];
+            const f3 pm = ld3(p, m), am = ld3(p, (long)N + m), om = ld3(O, m);
+            const DRot dm = drot(ld3(SC, m), ld3(SC, (long)N + m));
+            f3 dv; dv.x = om.x - on.x; dv.y = om.y - on.y; dv.z = om.z - on.z;
+            f3 g0, g1, g2; gcols(dm, dv, g0, g1, g2);
+            ap.x -= (pm.x - pp.x) - (g0.x * am.x + g1.x * am.y + g2.x * am.z);
+            ap.y -= (pm.y - pp.y) - (g0.y * am.x + g1.y * am.y + g2.y * am.z);
+            ap.z -= (pm.z - pp.z) - (g0.z * am.x + g1.z * am.y + g2.z * am.z);
         }
         ap.x *= wr2; ap.y *= wr2; ap.z *= wr2; aa.x *= wr2; aa.y *= wr2; aa.z *= wr2;
         if (Cn[3 * n] >= -999999.9f) { ap.x += wf * wf * pp.x; ap.y += wf * wf * pp.y; ap.z += wf * wf * pp.z; }
