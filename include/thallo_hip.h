@@ -583,7 +583,9 @@ int thallo_hip_sfs_apply_jtj_lm_pupdate(int W, int H, int row0, int row1, int yo
                                         thallo_sum_t alphaN_prev, thallo_sum_t betaN_prev, const unsigned* gate, thallo_stream_t stream);
 void thallo_hip_arap_debug_set(int what, int value);     /* tools / tests only: 0 = the unrolled ELL form of the ARAP applyJTJ on (1, default) / off */
 /* tools / tests only: 0 = rows per wave segment of the marching J^T(J v) kernel, 1 = workgroups per CU its grid is sized for (0 = automatic),
- * 2 = kernel choice (1 marching, 0 LDS-tiled, -1 the environment's THALLO_SFS_MARCH; default marching) */
+ * 2 = kernel choice (1 marching, 0 LDS-tiled, -1 the environment's THALLO_SFS_MARCH; default marching), 3 = the raw LM diagonal of thallo_hip_sfs_pcg_init by the marching
+ * J^T F kernel (1, default) or by k_diag in a launch of its own (0), 4 = thallo_hip_sfs_precompute by the marching kernel (1, default) or by k_precompute (0; float4 planes
+ * only), 5 = the workgroup budget the marching grids are sized for (0 = CUs x workgroups per CU of the device); 6, 7: the plane layout and the pair kernels' prefetch, below */
 void thallo_hip_sfs_march_debug_set(int what, int value);
 /* Round 6 -- the layout of the precomputed planes every thallo_hip_sfs_* entry point reads / writes for a W x H (local) image: 0 = G float4 / Wt float2 / fl byte per pixel
  * as described above; 1 = PACKED (images of even width; csrc/sfs_pair.hpp): the G buffer holds four planes of N floats Gx | Gy | Gz | BI, the first 4 N bytes of the Wt
@@ -621,8 +623,9 @@ int thallo_hip_sfs_resident_status(void* xbuf, int clear, int spin_ms, unsigned*
 void thallo_hip_sfs_resident_debug_set(int what, int value);
 /* Packed planes only (-hipErrorNotSupported elsewhere: the caller runs the launches they replace).
  * thallo_hip_sfs_pcg_init_lm: PCGInit1's J^T F pass with PCGFinalizeDiagonal (gauss_newton.t:936-969) riding along: r = -J^T F, delta = 0, p_prev = 0 and, from the raw diagonal
- * of J^T J formed in the same pass, CtC, pre = M^-1, b = r, z = M^-1 r, SSq (written when save_ssq, else read), partials of r . z -- thallo_hip_sfs_pcg_init +
- * thallo_hip_lm_finalize_diagonal in one launch.
+ * of J^T J formed in the same pass, CtC, pre = M^-1, b = r, z = M^-1 r, partials of r . z -- thallo_hip_sfs_pcg_init + thallo_hip_lm_finalize_diagonal in one launch.
+ * SSq: this energy has no preconditioner, so the plane holds ones: with save_ssq the launch writes them; without, it neither reads nor writes the plane and computes with 1
+ * (what the launch with save_ssq left -- a caller that keeps anything else there gets thallo_hip_lm_finalize_diagonal's result only from that entry point).
  * thallo_hip_sfs_lm_model_cost: delta_out = delta + alpha_kl p_kl (the update the one-launch LM loop owes: thallo_hip_lm_owed_delta's rule; delta_out != delta) and the partials of
  * delta_out . (J^T J delta_out) and delta_out . b -- thallo_hip_lm_owed_delta + thallo_hip_sfs_apply_jtj + thallo_hip_dot in one launch (whole image on one GPU); with X and
  * prevX (both or neither) also savePreviousUnknowns and PCGLinearUpdate of the step: prevX = X, X = X + delta_out (gauss_newton.t:901-906,915-920).  Returns the number of

@@ -1,5 +1,5 @@
 """Shared helper of the per-kernel tests (test_gpu_pcg_chain.py, test_gpu_transport_kernels.py, test_gpu_sparse_kernels.py, test_gpu_graph_kernels.py,
-test_shim_references.py).
+test_gpu_sfs_kernels.py, test_shim_references.py).
 
 Four things live here:
   * shim(): the library with argtypes / restype declared once for every thallo_hip.h entry point those files call;
@@ -36,6 +36,10 @@ class UnitsT(C.Structure):       # thallo_units_t
 
 class UpdateTermsT(C.Structure):     # thallo_update_terms_t
     _fields_ = [("p", C.c_void_p * MAX_UPDATE_TERMS), ("alphaN", api.SumT * MAX_UPDATE_TERMS), ("alphaD", api.SumT * MAX_UPDATE_TERMS), ("count", C.c_int)]
+
+
+class PrevT(C.Structure):            # thallo_prev_t
+    _fields_ = [("alphaD_partials", C.c_void_p), ("s12_partials", C.c_void_p), ("count", C.c_int), ("alphaD_word", C.c_void_p), ("betaN_word", C.c_void_p)]
 
 
 class FinT(C.Structure):             # thallo_fin_t
@@ -114,12 +118,29 @@ def shim():
         "arap_apply_jtj_rc": [it] * 3 + [vp] * 7 + [fl, fl] + [vp] * 3 + [lg] + [vp] * 3 + [FinT, vp],
         "arap_debug_set": [it, it],
         "permute3": [it, vp, vp, vp, it, vp],
+        # shape_from_shading (csrc/energy_sfs.hip, energy_sfs_pair.hip; test_gpu_sfs_kernels.py): W, H, row0 / ra, row1 / rb, yoff, Hg, host_params first
+        "sfs_precompute": [it] * 6 + [vp] * 10,
+        "sfs_precompute_cost": [it] * 6 + [vp] * 9 + [it, it, vp, vp],
+        "sfs_cost": [it] * 6 + [vp] * 8,
+        "sfs_pcg_init": [it] * 6 + [vp] * 15,
+        "sfs_pcg_init_lm": [it] * 6 + [vp] * 14 + [fl, fl, fl, it, vp, vp],
+        "sfs_apply_jtj": [it] * 6 + [vp] * 10,
+        "sfs_apply_jtj_gated": [it] * 6 + [vp] * 11,
+        "sfs_apply_jtj_lm": [it] * 6 + [vp] * 12,
+        "sfs_apply_jtj_sums": [it] * 6 + [vp] * 12,
+        "sfs_apply_jtj_sums_fin": [it] * 6 + [vp] * 11 + [FinT, vp],
+        "sfs_apply_jtj_lm_pupdate": [it] * 6 + [vp] * 10 + [it, S, S, vp, vp],
+        "sfs_pcg_iter": [it] * 6 + [vp] * 11 + [it, S, S, S, vp, vp, FinT, vp],
+        "sfs_pcg_iter_deferred": [it] * 6 + [vp] * 11 + [it, S, PrevT, vp, vp, vp],
+        "sfs_pcg_iter_lm": [it] * 6 + [vp] * 14 + [it, S, S, S, vp, vp, vp, FinT, vp, it, fl, vp],
+        "sfs_lm_model_cost": [it] * 6 + [vp] * 11 + [it, vp, it, vp, vp, vp, vp, vp],
+        "sfs_march_debug_set": [it, it], "sfs_planes_layout": [it, it], "sfs_march_fits": [it], "sfs_lm_pupdate_supported": [],
         "checksum_i32": [lg, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, "thallo_hip_" + name)
         f.argtypes = args
-        f.restype = None if name in ("lm_set_gate", "arap_debug_set") else lg if name == "vector_elems" else it
+        f.restype = None if name in ("lm_set_gate", "arap_debug_set", "sfs_march_debug_set") else lg if name == "vector_elems" else it
     _SHIM = L
     return L
 

@@ -164,6 +164,8 @@ __global__ __launch_bounds__(BLOCK) void k_rows(Geo g, Cam cm, const float* __re
                                                 const float2* __restrict__ Wt, const unsigned char* __restrict__ fl,
                                                 float2* __restrict__ U, float* __restrict__ R)
 {
+    // contraction per source expression, so that dB and its differences round as in k_fused<1>, which rounds dB into LDS first (held bitwise by tests/test_gpu_sfs_kernels.py)
+#pragma clang fp contract(on)
     const long N = (long)g.W * g.H;
     FOR_EACH_PIXEL(g) {
         const long i = (long)y * g.W + x;
@@ -251,6 +253,7 @@ __global__ __launch_bounds__(BLOCK) void k_gather(Geo g, Cam cm, const float* __
 // the tile +- 1 halo (66x18 over 64x16 = 16 %) and the stencil neighbourhoods are re-read through L1 / L2.
 // MODE 0 is the J^T F pass of PCGInit1: dB := BI (G.w), v := X, the fit term uses X - D, and the outputs are r = -J^T F, z = r,
 // p_prev = 0, delta = 0, alphaN partials.  Same expressions in the same order as k_rows / k_gather: bit-identical outputs.
+// (tests/test_gpu_sfs_kernels.py holds this for both modes.)
 // `gate` (may be NULL): a device word; non-zero = skip this launch (LM: the PCG loop ended early on the device, solver.cpp).
 // MODE 1 with D != NULL: D is the LM diagonal CtC and the output is (J^T J + CtC) v -- PCGStep1_Finish (gauss_newton.t:774-787) folded into the apply.
 constexpr int FW = 64, FH = 16;
@@ -1009,7 +1012,7 @@ int thallo_hip_sfs_march_fits(int W) { return sfs_fused() && sfs_march() && sfs_
 
 /* Round 6 (packed planes only; -hipErrorNotSupported elsewhere: the caller runs the launches they replace).
  * thallo_hip_sfs_pcg_init_lm: PCGInit1's J^T F pass with PCGFinalizeDiagonal riding along (gauss_newton.t:936-969): r = -J^T F, delta = 0, p_prev = 0 and, from the raw
- * diagonal of J^T J formed in the same pass, CtC, M^-1 (pre), b = r, z = M^-1 r, SSq (written when save_ssq, else read), partials of r . z.
+ * diagonal of J^T J formed in the same pass, CtC, M^-1 (pre), b = r, z = M^-1 r, SSq (ones: written when save_ssq, never read), partials of r . z.
  * thallo_hip_sfs_lm_model_cost: delta_out = delta + alpha_kl p_kl (the update the one-launch LM loop owes, thallo_hip_lm_owed_delta's rule) and the partials of
  * delta_out . J^T J delta_out and delta_out . b in ONE launch -- the model cost of an LM step (thallo.t:3845-3865, expanded: solver.cpp step_lm); with X / prevX also
  * savePreviousUnknowns and PCGLinearUpdate (prevX = X, X = X + delta_out; gauss_newton.t:901-906,915-920). */
