@@ -154,16 +154,30 @@ int ThalloX_PlanPreconditionerFallbacks(Thallo_Plan* plan);
  * block-sparse mat-vec instead of three passes over the observations (ThalloX_PlanScheduleName: "Schur complement on the cameras, assembled (N blocks); block-Jacobi on
  * S").  Its structure (blocks, term lists, one 9 x 3 block per observation) is built at Init and must fit a quarter of the free device memory and int32 indices: otherwise Init
  * fails with ThalloX_LastError naming the bytes wanted and allowed -- the term count grows with the square of a point's track length; there is no silent fall-back to
- * THALLOX_SOLVER_SCHUR_PCG.  Refused where THALLOX_SOLVER_SCHUR_PCG is. */
+ * THALLOX_SOLVER_SCHUR_PCG.  Refused where THALLOX_SOLVER_SCHUR_PCG is.
+ * THALLOX_SOLVER_SCHUR_DENSE: the exact solve for small and medium problems (up to a few hundred cameras).  Elimination, right-hand side and assembly are
+ * THALLOX_SOLVER_SCHUR_EXPLICIT_PCG's (its structure and budget are implied); then S is expanded to a dense lower triangle, Jacobi-scaled to a unit diagonal, factored by a
+ * float32 Cholesky on the device and delta_c = S^-1 g follows by two triangular sweeps -- no PCG loop on S: lIterations, q_tolerance and ThalloX_PlanSetPreconditioner are
+ * ignored, the step reports 0 linear iterations.  In LM every step factors anew (S carries the step's diagonal).  ThalloX_PlanScheduleName: "... assembled (N blocks);
+ * dense Cholesky of S (n = 9 C)".  A scalar the caller holds, and a scalar whose diagonal of S is not positive (a camera nothing observes; counted by
+ * ThalloX_PlanSchurDenseNonPositive), gets the identity's row and column: delta is exactly 0 there.  A FACTOR THAT MEETS A PIVOT THAT IS NOT POSITIVE FAILS THE STEP:
+ * Thallo_ProblemStep returns 0, the unknowns are unchanged, and ThalloX_LastError names the camera and scalar of the pivot.  Gauss-Newton without a fixed gauge is such a
+ * system (singular but consistent: PCG tolerates it, a factorisation does not): hold a camera and one more scalar (ThalloX_PlanSetHeldUnknowns) or use ThalloX_EnableLM.
+ * One blocking 4-byte read-back per step reports it.  The dense matrix takes 4 ld n bytes (n = 9 C, ld = n rounded up to 32), added to the structure's bytes before
+ * anything is allocated: Init fails, naming the bytes wanted and allowed, above a quarter of the free device memory.  Refused where THALLOX_SOLVER_SCHUR_PCG is. */
 #define THALLOX_SOLVER_PCG                0   /* default */
 #define THALLOX_SOLVER_SCHUR_PCG          1
 #define THALLOX_SOLVER_SCHUR_EXPLICIT_PCG 2
+#define THALLOX_SOLVER_SCHUR_DENSE        3
 int ThalloX_PlanSetLinearSolver(Thallo_Plan* plan, int kind);
 /* The stored 9 x 9 blocks of the assembled S (both triangles) after Thallo_ProblemInit; -1 when the assembled form does not run. */
 int ThalloX_PlanSchurBlocks(Thallo_Plan* plan);
 /* Points that the last step's elimination held fixed (delta = 0 for the step: their 3 x 3 block did not factor, or has a squared pivot of the Jacobi-scaled block below 2^-16);
  * -1 when the Schur form does not run.  ThalloX_PlanPreconditionerFallbacks then reports the camera blocks' fallbacks.  Synchronises the plan's stream. */
 int ThalloX_PlanSchurHeldPoints(Thallo_Plan* plan);
+/* Scalars of the last dense factor (a step's, or a ThalloX_PlanCovariance call's) whose diagonal of S was not positive and that were given the identity's row and column;
+ * -1 when THALLOX_SOLVER_SCHUR_DENSE does not run.  Synchronises the plan's stream. */
+int ThalloX_PlanSchurDenseNonPositive(Thallo_Plan* plan);
 
 /* Unknowns that are not to move: gauge fixing (one or two cameras), fixed intrinsics (components 6..8 of every camera), motion-only or structure-only bundle adjustment,
  * known control points.  `input` is the Inputs{} index of an Unknown (bundle_adjustment: 0 cameras, 1 points); held is a HOST array of n = elements x components bytes in
@@ -215,7 +229,11 @@ long ThalloX_PlanRobustWeights(Thallo_Plan* plan, float* host_out, long n);
  * the call launches what it launched before.  Its work vectors are allocated at the first call and freed with the plan.  Synchronises the plan's stream.
  * Returns 0; or the number of columns that did not converge (> 0; host_out is written all the same); or a negative number with ThalloX_LastError naming the energy
  * and the reason: wherever THALLOX_SOLVER_SCHUR_EXPLICIT_PCG is refused, a plan whose last Init ran another linear solver, a call before Thallo_ProblemInit, an input
- * that is not an Unknown, n <= 0, an id out of range or repeated, a rel_tol that is not finite and positive, max_iterations < 1. */
+ * that is not an Unknown, n <= 0, an id out of range or repeated, a rel_tol that is not finite and positive, max_iterations < 1.
+ * On a plan whose last Thallo_ProblemInit ran THALLOX_SOLVER_SCHUR_DENSE the columns come from a dense Cholesky factor of S instead (expanded and factored once per call,
+ * two triangular sweeps per batch, whatever the length of the camera chain): rel_tol and max_iterations are accepted and ignored; info reports 0 iterations and a worst
+ * residual of 0; not_converged -- and the return value -- count the requested camera columns at scalars whose diagonal of S is not positive (their blocks stay zero); a
+ * factor that meets a pivot that is not positive returns a negative number, ThalloX_LastError naming the camera and scalar. */
 typedef struct ThalloX_CovarianceOptions {
     float rel_tol;               /* default 1e-6 */
     int   max_iterations;        /* default 500 */

@@ -890,6 +890,32 @@ int thallo_hip_ba_cov_out(const thallo_cov_sys_t* sys, int mode, const int* ids,
 int thallo_hip_ba_cov_solve(const thallo_cov_sys_t* sys, int mode, const int* ids, int nreq, float rel_tol, int max_iterations, void* work, unsigned* pinned, float* out,
                             thallo_cov_info_t* info, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- dense Cholesky of the reduced camera matrix (ba_schur_dense.hip; DESIGN.md "Dense Cholesky Schur solve")
+ * A dense n x n lower triangle, row-major with leading dimension ld = thallo_hip_dense_ld(n) (n rounded up to the panel width THALLO_HIP_DENSE_NB; the base 16-byte
+ * aligned).  None of the calls below reads or writes the upper triangle or the padding columns [n, ld).  No float atomics, one fixed summation order per n: two runs give
+ * equal bits. */
+#define THALLO_HIP_DENSE_NB 32
+#define THALLO_HIP_DENSE_MAX_N (1L << 20)
+long thallo_hip_dense_ld(long n);
+/* T = D S D for the assembled S of thallo_hip_ba_schur_assemble (n = 9 C), D = diag(S_ii)^-1/2: d[i] = 1 / sqrt(S_ii) and T_ij = float(float(d_i S_ij) d_j) for j <= i.  A
+ * scalar with hold[i] != 0 (hold: 9 C bytes or NULL) and one whose S_ii is not positive get d[i] = 0 and the identity's row and column; nonpos[0] (a device word) = the
+ * number of the latter.  The whole buffer T (ld x n floats) is zeroed first. */
+int thallo_hip_ba_schur_dense_expand(int C, long nblk, const int* row_ptr, const int* col, const float* S, const unsigned char* hold, long ld, float* T, float* d, unsigned* nonpos,
+                                     thallo_stream_t stream);
+/* T = L L^T in place (lower triangle), blocked right-looking: per panel of 32 columns the diagonal block by one wave, the rows below spread over workgroups, the trailing
+ * update on the matrix cores (v_mfma_f32_32x32x2_f32).  info[0] (a device word, zeroed first) = 1 + the index of the first pivot that was not positive, where the factor
+ * went on with 1.0; 0: none. */
+int thallo_hip_dense_potrf(long n, long ld, float* T, int* info, thallo_stream_t stream);
+/* X = D L^-T L^-1 D B in place for ngroups panels of THALLO_HIP_COV_K right-hand sides, B[g][n][THALLO_HIP_COV_K] (the covariance's layout), d = NULL: D = I.  One launch,
+ * one workgroup per panel, one lane per column: a column's result does not depend on its companions, a zero column stays zero.  sweeps: THALLO_HIP_DENSE_BOTH, or one
+ * sweep alone -- _FORWARD: Y = L^-1 D B; _BACKWARD: X = D L^-T B (the two in a row give the bits of _BOTH). */
+#define THALLO_HIP_DENSE_BOTH     0
+#define THALLO_HIP_DENSE_FORWARD  1
+#define THALLO_HIP_DENSE_BACKWARD 2
+int thallo_hip_dense_potrs_cols(long n, long ld, const float* L, const float* d, float* B, int ngroups, int sweeps, thallo_stream_t stream);
+/* x = D L^-T L^-1 D b for one right-hand side (x != b; d = NULL: D = I; sweeps as above): one launch, one workgroup. */
+int thallo_hip_dense_potrs_vec(long n, long ld, const float* L, const float* d, const float* b, float* x, int sweeps, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

@@ -130,6 +130,8 @@ def lib():
     L.ThalloX_PlanSetLinearSolver.argtypes = [vp, C.c_int]; L.ThalloX_PlanSetLinearSolver.restype = C.c_int
     L.ThalloX_PlanSchurHeldPoints.argtypes = [vp]; L.ThalloX_PlanSchurHeldPoints.restype = C.c_int
     L.ThalloX_PlanSchurBlocks.argtypes = [vp]; L.ThalloX_PlanSchurBlocks.restype = C.c_int
+    if hasattr(L, "ThalloX_PlanSchurDenseNonPositive"):      # (THALLO_LIB may name an A/B build from before the call existed)
+        L.ThalloX_PlanSchurDenseNonPositive.argtypes = [vp]; L.ThalloX_PlanSchurDenseNonPositive.restype = C.c_int
     L.ThalloX_PlanSetHeldUnknowns.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetHeldUnknowns.restype = C.c_int
     L.ThalloX_PlanHeldUnknowns.argtypes = [vp]; L.ThalloX_PlanHeldUnknowns.restype = C.c_long
     if hasattr(L, "ThalloX_PlanSetRobustLoss"):      # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_robust_bench.py --ab)
@@ -422,13 +424,16 @@ class ThalloSolver:
         """Blocks of the last step that fell back to their diagonal (-1: the block form does not run)."""
         return self._L.ThalloX_PlanPreconditionerFallbacks(self.plan)
 
-    LINEAR_SOLVERS = {"pcg": 0, "schur_pcg": 1, "schur_explicit_pcg": 2}      # THALLOX_SOLVER_* of include/Thallo.h
+    LINEAR_SOLVERS = {"pcg": 0, "schur_pcg": 1, "schur_explicit_pcg": 2, "schur_dense": 3}      # THALLOX_SOLVER_* of include/Thallo.h
 
     def set_linear_solver(self, kind):
         """"pcg" (the full system, default), "schur_pcg" (bundle_adjustment: the points eliminated through their 3 x 3 blocks, PCG on the cameras, preconditioned by the
         camera blocks whatever set_preconditioner was given; S x applied matrix-free) or "schur_explicit_pcg" (the same solve with the reduced camera matrix S assembled
         once per step as a block-sparse matrix: one mat-vec per iteration; init() fails, naming the bytes, where its structure does not fit a quarter of the free device
-        memory); before init().  Raises, with the library's reason, where the plan has no Schur form (include/Thallo.h ThalloX_PlanSetLinearSolver)."""
+        memory) or "schur_dense" (that assembly, then a dense float32 Cholesky factor of S on the device instead of a PCG loop: the exact solve for up to a few hundred
+        cameras; lIterations, q_tolerance and the preconditioner are ignored; a step whose factor meets a pivot that is not positive returns 0 with the unknowns unchanged
+        and last_error() naming the camera and scalar -- fix the gauge with hold() or use LM); before init().  Raises, with the library's reason, where the plan has no
+        Schur form (include/Thallo.h ThalloX_PlanSetLinearSolver)."""
         if kind not in self.LINEAR_SOLVERS:
             raise ValueError(f"linear solver {kind!r}: expected one of {sorted(self.LINEAR_SOLVERS)}")
         if self._L.ThalloX_PlanSetLinearSolver(self.plan, self.LINEAR_SOLVERS[kind]) != 0:
@@ -441,6 +446,10 @@ class ThalloSolver:
     def schur_blocks(self):
         """Stored 9 x 9 blocks of the assembled reduced camera matrix after init() (-1: the assembled form does not run)."""
         return self._L.ThalloX_PlanSchurBlocks(self.plan)
+
+    def schur_dense_nonpositive(self):
+        """Scalars of the last dense factor whose diagonal of S was not positive and that got the identity's row and column (-1: "schur_dense" does not run)."""
+        return self._L.ThalloX_PlanSchurDenseNonPositive(self.plan)
 
     def hold(self, input, mask):
         """Unknowns that are not to move (include/Thallo.h ThalloX_PlanSetHeldUnknowns): `input` is the Inputs{} index of an Unknown (bundle_adjustment: 0 cameras,
@@ -484,7 +493,9 @@ class ThalloSolver:
         (None: that kind is not asked for).  Returns {"cameras": float32 [n, 9, 9], "points": float32 [m, 3, 3], "info": {...}}: the blocks of (A_FF)^-1, A = J^T J without
         the LM diagonal, unscaled, zero rows and columns at held scalars, NaN blocks for points the elimination holds; info adds up iterations, columns, not_converged and
         nan_blocks over both kinds and keeps the largest worst_residual.  The gauge is the caller's to fix, with hold().  The plan's last init() must have run
-        set_linear_solver("schur_explicit_pcg"); raises, with the library's reason, where the call is refused."""
+        set_linear_solver("schur_explicit_pcg") (columns by PCG) or "schur_dense" (columns through the dense Cholesky factor: rel_tol and max_iterations are ignored,
+        iterations and worst_residual are 0, not_converged counts the requested columns at scalars whose diagonal of S is not positive); raises, with the library's
+        reason, where the call is refused."""
         import numpy as np
         out = {"cameras": np.zeros((0, 9, 9), np.float32), "points": np.zeros((0, 3, 3), np.float32),
                "info": {"iterations": 0, "columns": 0, "not_converged": 0, "nan_blocks": 0, "worst_residual": 0.0}}

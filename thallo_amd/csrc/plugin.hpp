@@ -236,6 +236,16 @@ public:
     virtual long schur_explicit(bool /*on*/) { return -1; }
     virtual int schur_assemble(LaunchCtx&, const float* /*H*/, const float* /*Ge*/, const float* /*ctc*/) { return -1; }
     virtual int schur_back(LaunchCtx&, const float* /*Ge*/, const float* /*b*/, float* /*delta*/, const float* /*p*/, thallo_sum_t /*aN*/, thallo_sum_t /*aD*/) { return -1; }
+    // the dense form (ThalloX_PlanSetLinearSolver kind 3; ba_schur_dense.hip): the assembled form plus a dense Cholesky factor of S in place of the reduced PCG loop.
+    // schur_dense_want(on), before schur_explicit(true): the dense lower triangle is part of the structure -- its bytes are added to the budget before anything is
+    // allocated, it is allocated behind the structure and freed with it, or by the next schur_explicit that does not want it.  schur_dense_n: the order of the matrix
+    // (-1: the dense form does not run).  schur_dense_solve, every step behind schur_assemble: T = D S D with the identity at the scalars `hold` holds (the plan's mask over
+    // the flat vector or NULL) and at non-positive diagonals, T = L L^T, delta_c = D L^-T L^-1 D g -> 0 or a negative launch code.  schur_dense_words: two device words
+    // of the last factor, [0] 1 + the index of the first pivot that was not positive (0: none), [1] the non-positive diagonals
+    virtual void schur_dense_want(bool /*on*/) {}
+    virtual long schur_dense_n() const { return -1; }
+    virtual int schur_dense_solve(LaunchCtx&, const unsigned char* /*hold*/, const float* /*g*/, float* /*delta_c*/) { return -1; }
+    virtual const unsigned* schur_dense_words() const { return nullptr; }
     // ---- held unknowns (opt-in: ThalloX_PlanSetHeldUnknowns; held.hip): plugins all of whose PCG routes form M^-1 from the stored SolverVectors::pre.  hold_to_internal,
     // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
     virtual bool hold_ok() const { return false; }
@@ -254,6 +264,10 @@ public:
     virtual long cov_elements(int /*input*/) const { return -1; }
     virtual int covariance(LaunchCtx&, int /*input*/, const int* /*ids*/, long /*n*/, const float* /*Gc*/, const float* /*Ge*/, const unsigned char* /*hold*/, float /*rel_tol*/,
                            int /*max_iterations*/, float* /*host_out*/, thallo_cov_info_t* /*info*/) { return -1; }
+    // ... on a plan of the dense form: the columns through the factor (expanded and factored once per call) -> 0, -1 with the reason set, or -2 with *pivot = the index
+    // of the pivot that was not positive
+    virtual int covariance_dense(LaunchCtx&, int /*input*/, const int* /*ids*/, long /*n*/, const float* /*Gc*/, const float* /*Ge*/, const unsigned char* /*hold*/, float* /*host_out*/,
+                                 thallo_cov_info_t* /*info*/, int* /*pivot*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale

@@ -962,9 +962,18 @@ public:
     bool sx_on_ = false;
     long sx_nblk_ = 0; int sx_nlower_ = 0;
     DeviceBuffer sx_row_ptr_, sx_col_, sx_lower_, sx_term_ptr_, sx_terms_, sx_W_, sx_S_;
+    // the dense form (kind 3; ba_schur_dense.hip): the lower triangle T of D S D (ld x 9 C floats, factored in place every step), d, and two words -- the factor's info and the
+    // count of non-positive diagonals.  Part of the assembled structure: counted in its budget, allocated behind it, freed with it or by the next Init that does not want it
+    bool sd_want_ = false, sd_on_ = false;
+    long sd_ld_ = 0;
+    DeviceBuffer sd_T_, sd_d_, sd_words_;
+    void schur_dense_want(bool on) override { sd_want_ = on; }
+    long schur_dense_n() const override { return sd_on_ ? 9L * C : -1; }
+    const unsigned* schur_dense_words() const override { return sd_on_ ? (const unsigned*)sd_words_.ptr : nullptr; }
     long schur_explicit(bool on) override
     {
-        sx_on_ = false;
+        sx_on_ = false; sd_on_ = false;
+        if (!on || !sd_want_) for (DeviceBuffer* b : { &sd_T_, &sd_d_, &sd_words_ }) b->release();
         if (!on) { for (DeviceBuffer* b : { &sx_row_ptr_, &sx_col_, &sx_lower_, &sx_term_ptr_, &sx_terms_, &sx_W_, &sx_S_ }) b->release(); return 0; }
         if (C < 1) { set_error("bundle_adjustment: the assembled Schur-complement solve needs at least one camera"); return -1; }
         std::vector<int> pp((size_t)P + 1), ppos((size_t)O), qc((size_t)O), qp((size_t)O), cp((size_t)C + 1);
@@ -981,6 +990,22 @@ public:
             const unsigned long long cap = strtoull(e, nullptr, 10) << 20;
             if (cap < allowed) { allowed = cap; why = "THALLO_AB schur_s_max_mb"; }
         }
+        // the dense form's bytes: known from C alone, refused first
+        const long sd_n = 9L * C, sd_ld = thallo_hip_dense_ld(sd_n);
+        const unsigned long long dense_bytes = sd_want_ ? 4ULL * (unsigned long long)sd_ld * (unsigned long long)sd_n + 4ULL * (unsigned long long)sd_n + 128 : 0;
+        if (sd_want_) {
+            if (sd_n > THALLO_HIP_DENSE_MAX_N) { set_error("bundle_adjustment: the dense reduced camera matrix has n = %ld, more than the dense kernels take (%ld)", sd_n, (long)THALLO_HIP_DENSE_MAX_N); return -1; }
+            unsigned long long dense_allowed = allowed; const char* dwhy = why;
+            if (const char* e = env_switch("THALLO_SCHUR_DENSE_MAX_MB")) {
+                const unsigned long long cap = strtoull(e, nullptr, 10) << 20;
+                if (cap < dense_allowed) { dense_allowed = cap; dwhy = "THALLO_AB schur_dense_max_mb"; }
+            }
+            if (dense_bytes > dense_allowed) {
+                set_error("bundle_adjustment: the dense reduced camera matrix wants %llu bytes of device memory (n = %ld scalars, leading dimension %ld), the budget allows %llu (%s): "
+                          "THALLOX_SOLVER_SCHUR_EXPLICIT_PCG solves on the block-sparse S without it", dense_bytes, sd_n, sd_ld, dense_allowed, dwhy);
+                return -1;
+            }
+        }
         // the terms, counted before anything is built: an observation pairs with every observation of its point whose camera is not above its own
         unsigned long long nterms = 0;
         for (int j = 0; j < P; ++j)
@@ -990,13 +1015,17 @@ public:
             }
         const unsigned long long w_bytes = sizeof(float) * THALLO_HIP_SCHUR_W_STRIDE * (unsigned long long)O + 64;
         auto over = [&](unsigned long long bytes, unsigned long long blocks, const char* least) {
+            if (sd_want_)
+                set_error("bundle_adjustment: the assembled reduced camera matrix and its dense lower triangle want %s%llu bytes of device memory (%s%llu blocks of 9 x 9, %llu terms, %d observations; "
+                          "%llu bytes dense, n = %ld), the budget allows %llu (%s): THALLOX_SOLVER_SCHUR_PCG applies S without assembling it", least, bytes, least, blocks, nterms, O, dense_bytes, sd_n, allowed, why);
+            else
             set_error("bundle_adjustment: the assembled reduced camera matrix wants %s%llu bytes of device memory (%s%llu blocks of 9 x 9, %llu terms, %d observations), the budget allows %llu (%s): "
                       "points seen by many cameras make the term count grow with the square of the track length; THALLOX_SOLVER_SCHUR_PCG applies S without assembling it",
                       least, bytes, least, blocks, nterms, O, allowed, why);
             return -1L;
         };
         if (nterms > 0x7fffffffULL) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu terms, more than its int32 indices hold", nterms); return -1; }
-        if (w_bytes + 8ULL * nterms > allowed) return over(w_bytes + 8ULL * nterms + 81ULL * 4 * (unsigned long long)C, (unsigned long long)C, "at least ");      // (the blocks are not counted yet)
+        if (w_bytes + 8ULL * nterms + dense_bytes > allowed) return over(w_bytes + 8ULL * nterms + 81ULL * 4 * (unsigned long long)C + dense_bytes, (unsigned long long)C, "at least ");      // (the blocks are not counted yet)
         // row by row, without a comparison sort of the terms: a row's observations ascend, a counting pass sizes its blocks, a second pass places the terms -- (q, q')
         // ascending within every block.  Every diagonal block is present, with or without terms
         std::vector<int> lower, term_ptr, tq(2 * (size_t)nterms + 2), cnt((size_t)C, 0), touched;
@@ -1017,7 +1046,7 @@ public:
         tq.resize(2 * (size_t)nterms);
         const unsigned long long nlower = keys.size(), nblk = 2 * nlower - (unsigned long long)C;
         if (nblk > 0x7fffffffULL / 3) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu blocks, more than its int32 indices hold", nblk); return -1; }
-        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5);
+        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5) + dense_bytes;
         if (bytes > allowed) return over(bytes, nblk, "");
         std::vector<int> row_ptr((size_t)C + 1, 0);
         for (long key : keys) { const int i = (int)(key / C), j = (int)(key % C); row_ptr[i + 1]++; if (i != j) row_ptr[j + 1]++; }
@@ -1042,8 +1071,33 @@ public:
             set_error("bundle_adjustment: out of device memory for the assembled reduced camera matrix (%llu bytes): %s", bytes, whyn.c_str());
             return -1;
         }
-        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true;
+        if (sd_want_ && (sd_T_.alloc(4 * (size_t)sd_ld * (size_t)sd_n + 64) || sd_d_.alloc(4 * (size_t)sd_n + 64) || sd_words_.alloc(64))) {
+            const std::string whyn = last_error();
+            for (DeviceBuffer* b : { &sd_T_, &sd_d_, &sd_words_ }) b->release();
+            set_error("bundle_adjustment: out of device memory for the dense reduced camera matrix (%llu bytes): %s", dense_bytes, whyn.c_str());
+            return -1;
+        }
+        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true; sd_on_ = sd_want_; sd_ld_ = sd_ld;
         return sx_nblk_;
+    }
+    // expand + factor of the step's (or the covariance call's) assembled S; hold: the plan's mask over the flat vector (its first 9 C bytes are the cameras') or NULL
+    int schur_dense_factor(LaunchCtx& c, const unsigned char* hold)
+    {
+        if (!sd_on_) return -1;
+        unsigned* words = (unsigned*)sd_words_.ptr;
+        {   TimedLaunch t(c, "SchurDenseExpand");
+            const int rc = thallo_hip_ba_schur_dense_expand(C, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, hold, sd_ld_, (float*)sd_T_.ptr, (float*)sd_d_.ptr,
+                                                            words + 1, c.stream);
+            if (rc < 0) return rc; }
+        TimedLaunch t(c, "SchurDenseFactor");
+        return thallo_hip_dense_potrf(9L * C, sd_ld_, (float*)sd_T_.ptr, (int*)words, c.stream);
+    }
+    int schur_dense_solve(LaunchCtx& c, const unsigned char* hold, const float* g, float* delta_c) override
+    {
+        const int rc = schur_dense_factor(c, hold);
+        if (rc < 0) return rc;
+        TimedLaunch t(c, "SchurDenseSolve");
+        return thallo_hip_dense_potrs_vec(9L * C, sd_ld_, (const float*)sd_T_.ptr, (const float*)sd_d_.ptr, g, delta_c, THALLO_HIP_DENSE_BOTH, c.stream);
     }
     int schur_assemble(LaunchCtx& c, const float* H, const float* Ge, const float* ctc) override
     {
@@ -1139,6 +1193,76 @@ public:
             info->iterations += bi.iterations; info->columns += bi.columns; info->not_converged += bi.not_converged; info->nan_blocks += bi.nan_blocks;
             if (!(bi.worst <= info->worst)) info->worst = bi.worst;
         }
+        return 0;
+    }
+    // ... and on a plan of the dense form (kind 3): S is expanded and factored once per call, then per group of up to SD_GROUPS batches thallo_hip_ba_cov_rhs per batch, ONE
+    // thallo_hip_dense_potrs_cols launch (a workgroup per batch) and thallo_hip_ba_cov_out per batch.  -> 0; -1 with the reason set; -2: the factor met a pivot that is
+    // not positive (words[0]; the plan words the message).  info->not_converged: the requested camera columns at scalars whose diagonal is not positive
+    static constexpr int SD_GROUPS = 8;
+    DeviceBuffer sdc_panels_, sdc_ids_, sdc_out_;
+    int covariance_dense(LaunchCtx& c, int input, const int* ids, long n, const float* Gc, const float* Ge, const unsigned char* hold, float* host_out, thallo_cov_info_t* info,
+                         int* pivot) override
+    {
+        if (!sd_on_) { set_error("bundle_adjustment: the dense covariance needs the dense reduced camera matrix"); return -1; }
+        const int K = THALLO_HIP_COV_K, per = input == 0 ? K / 9 : K / 3, fl = input == 0 ? 81 : 9;
+        const long sd_n = 9L * C, pn = sd_n * K;
+        const long nbatch = (n + per - 1) / per;
+        const int groups = (int)(nbatch < SD_GROUPS ? nbatch : SD_GROUPS);
+        if (sdc_panels_.bytes < sizeof(float) * (size_t)pn * (size_t)groups + 64 &&
+            (sdc_panels_.alloc(sizeof(float) * (size_t)pn * (size_t)groups + 64) || sdc_ids_.alloc(sizeof(int) * K * SD_GROUPS) || sdc_out_.alloc(sizeof(float) * 81 * (K / 9) * SD_GROUPS + 64))) {
+            for (DeviceBuffer* b : { &sdc_panels_, &sdc_ids_, &sdc_out_ }) b->release();
+            set_error("bundle_adjustment: out of device memory for the dense covariance's panels (%zu bytes)", sizeof(float) * (size_t)pn * (size_t)groups); return -1;
+        }
+        int rc = schur_dense_factor(c, hold);
+        if (rc < 0) { set_error("bundle_adjustment: the dense covariance's expansion or factor failed to launch (%d)", rc); return -1; }
+        unsigned words[2] = { 0, 0 };
+        std::vector<float> dh((size_t)sd_n);
+        std::vector<unsigned char> hh(hold ? (size_t)sd_n : 0);
+        if (hipMemcpyAsync(words, sd_words_.ptr, sizeof(words), hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            hipMemcpyAsync(dh.data(), sd_d_.ptr, sizeof(float) * (size_t)sd_n, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            (hold && hipMemcpyAsync(hh.data(), hold, (size_t)sd_n, hipMemcpyDeviceToHost, c.stream) != hipSuccess) ||
+            hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the dense factor's status"); return -1; }
+        if (words[0]) { *pivot = (int)words[0] - 1; return -2; }
+        std::vector<int> in(ids, ids + n);
+        if (input == 1 && perm_) {
+            std::vector<int> old2new((size_t)P);
+            for (int j = 0; j < P; ++j) old2new[(size_t)h_new2old_[(size_t)j]] = j;
+            for (long i = 0; i < n; ++i) in[(size_t)i] = old2new[(size_t)ids[i]];
+        }
+        thallo_cov_sys_t sys;
+        sys.C = C; sys.P = P; sys.nblk = sx_nblk_; sys.row_ptr = (const int*)sx_row_ptr_.ptr; sys.col = (const int*)sx_col_.ptr; sys.S = (const float*)sx_S_.ptr;
+        sys.Gc = Gc; sys.Ge = Ge; sys.W = (const float*)sx_W_.ptr; sys.pt_ptr = (const int*)pt_ptr.ptr; sys.pt_pos = (const int*)pt_pos.ptr; sys.q_cam = (const int*)q_cam.ptr; sys.hold = hold;
+        *info = thallo_cov_info_t{ 0, 0, 0, 0, 0.0f };
+        unsigned* nan_word = (unsigned*)sd_words_.ptr + 2;
+        if (hipMemsetAsync(nan_word, 0, sizeof(unsigned), c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot clear the dense covariance's NaN count"); return -1; }
+        for (long g0 = 0; g0 < nbatch; g0 += groups) {
+            const int ng = (int)(nbatch - g0 < groups ? nbatch - g0 : groups);
+            const long first = g0 * per, last = first + (long)ng * per < n ? first + (long)ng * per : n;
+            auto nreq_of = [&](int g) { const long b0 = first + (long)g * per; return (int)(last - b0 < per ? last - b0 : per); };
+            std::vector<int> padded((size_t)ng * (size_t)K, 0);      // (a batch's ids at a stride of K)
+            for (int g = 0; g < ng; ++g) for (int j = 0; j < nreq_of(g); ++j) padded[(size_t)g * K + (size_t)j] = in[(size_t)(first + (long)g * per + j)];
+            if (hipMemcpy(sdc_ids_.ptr, padded.data(), sizeof(int) * padded.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("bundle_adjustment: cannot upload the covariance's ids"); return -1; }
+            for (int g = 0; g < ng; ++g)
+                if ((rc = thallo_hip_ba_cov_rhs(&sys, input, (const int*)sdc_ids_.ptr + (size_t)g * K, nreq_of(g), (float*)sdc_panels_.ptr + (size_t)g * (size_t)pn, c.stream)) < 0) break;
+            if (rc >= 0) rc = thallo_hip_dense_potrs_cols(sd_n, sd_ld_, (const float*)sd_T_.ptr, (const float*)sd_d_.ptr, (float*)sdc_panels_.ptr, ng, THALLO_HIP_DENSE_BOTH, c.stream);
+            for (int g = 0; g < ng && rc >= 0; ++g)
+                rc = thallo_hip_ba_cov_out(&sys, input, (const int*)sdc_ids_.ptr + (size_t)g * K, nreq_of(g), (const float*)sdc_panels_.ptr + (size_t)g * (size_t)pn,
+                                           (float*)sdc_out_.ptr + (size_t)g * (size_t)fl * (size_t)per, nan_word, c.stream);
+            if (rc < 0) { set_error("bundle_adjustment: the dense covariance's column solve failed (%d)", rc); return -1; }
+            if (hipMemcpyAsync(host_out + (size_t)fl * (size_t)first, sdc_out_.ptr, sizeof(float) * (size_t)fl * (size_t)(last - first), hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+                hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance blocks"); return -1; }
+        }
+        unsigned nans = 0;
+        if (hipMemcpy(&nans, nan_word, sizeof(nans), hipMemcpyDeviceToHost) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance's NaN count"); return -1; }
+        info->nan_blocks = (int)nans;
+        if (input == 0) {
+            for (long i = 0; i < n; ++i)
+                for (int a = 0; a < 9; ++a) {
+                    const size_t u = 9 * (size_t)ids[i] + (size_t)a;
+                    if (hold && hh[u]) continue;                                  // (a held scalar's unit column is zero and needs no solve)
+                    if (dh[u] > 0.0f) info->columns++; else info->not_converged++;
+                }
+        } else info->columns = (int)(3 * n) - 3 * (int)nans;
         return 0;
     }
     ~BundleAdjustmentPlugin() override { if (cov_pinned_) (void)hipHostFree(cov_pinned_); }

@@ -267,6 +267,7 @@ const char* env_switch(const char* name)
         { "THALLO_INC_LANES", "inc_lanes" },                    // N (a power of two <= 64): lanes per owner in the generated index-map gather kernels (default: by list length and owner count)
         { "THALLO_DELTA_FIRST_TOUCH", "delta_first_touch" },    // 0: PCGInit1 zeroes delta in every schedule, and the ring schedule's first delta update of a GN step reads those zeros back
         { "THALLO_SCHUR_S_MAX_MB", "schur_s_max_mb" },          // N: the assembled reduced camera matrix (ThalloX_PlanSetLinearSolver kind 2) may take at most N MiB of device memory (default: a quarter of what is free)
+        { "THALLO_SCHUR_DENSE_MAX_MB", "schur_dense_max_mb" },  // N: the dense lower triangle of the reduced camera matrix (ThalloX_PlanSetLinearSolver kind 3) may take at most N MiB of device memory (default: what kind 2's budget leaves)
         { "THALLO_PERSIST", "persist" },                        // 1: iterations 1 .. L-1 of a GN step of image_warping's marching kernel as persistent launches (bit-identical, measured slower)
     };
     for (const char* k : known) if (!strcmp(k, name)) return getenv(name);

@@ -153,10 +153,11 @@ public:
     int  set_preconditioner(int kind);
     int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
     const char* schedule_name();          // the plugin's, and the opt-in forms that run (before the first Init: that were asked for)
-    // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG or THALLOX_SOLVER_SCHUR_EXPLICIT_PCG; takes effect at the next Init.  0 = ok
+    // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG or THALLOX_SOLVER_SCHUR_DENSE; takes effect at the next Init.  0 = ok
     int  set_linear_solver(int kind);
     int  schur_blocks() const { return schur_on_ && schur_explicit_ ? (int)schur_blocks_ : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
     int  schur_held_points();             // points the last step's elimination held fixed (-1: the Schur form does not run)
+    int  schur_dense_nonpositive();       // scalars of the last dense factor whose diagonal of S was not positive (identity rows; -1: the dense form does not run)
     // ThalloX_PlanSetHeldUnknowns: the mask of one Unknown (host bytes in the caller's ids, nonzero = that scalar is a constant of the solve; NULL clears it); takes effect
     // at the next Init.  0 = ok
     int  set_held_unknowns(int input, const unsigned char* held, long n);
@@ -340,6 +341,9 @@ private:
     bool schur_want_ = false, schur_on_ = false;
     bool schur_explicit_want_ = false, schur_explicit_ = false;      // kind 2 (asked for / running since the last Init): S assembled once per step by the plugin (ba_schur_explicit.hip), the loop's applies multiply by it
     long schur_blocks_ = -1;                            // ... its stored blocks, known at Init
+    bool schur_dense_want_ = false, schur_dense_ = false;      // kind 3 (asked for / running since the last Init): kind 2's structure and assembly, and a dense Cholesky factor of S in place of the reduced PCG loop (ba_schur_dense.hip)
+    bool  schur_dense_step(const float* g);             // expand, factor, delta_c = S^-1 g, the read-back of the factor's info word; false: the error is set, nothing was applied
+    void  schur_dense_pivot_error(int index, const char* where);
     long schur_n_ = 0, schur_hp_off_ = 0, schur_pt_off_ = 0;      // camera unknowns; the point blocks' place in H; the points' place in the flat vector
     float *schur_Ge_ = nullptr, *schur_y_ = nullptr, *schur_g_ = nullptr;
     unsigned* schur_held_ = nullptr;

@@ -33,8 +33,9 @@ int Plan::forms_prepare()
     robust_on_ = robust_want_; robust_on_scale_ = robust_want_scale_;
     block_on_ = false;
     schur_on_ = false;
+    schur_dense_ = false;
     if (schur_want_) { if (schur_prepare()) return -1; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
-    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes)
+    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes, the dense matrix with it)
     if (!schur_want_ && block_want_) { if (block_prepare()) return -1; block_on_ = true; }
     if (schur_on_ || block_on_) { precond_regions_ = block_regions_; if (schur_on_) precond_regions_.n = 1; }      // (Schur: the camera region alone)
     return 0;
@@ -75,10 +76,11 @@ int Plan::forms_setup(const float* shift, const float* b, float* rz_out, int nb,
 // PCGLinearUpdate then adds the complete delta.
 int Plan::step_gn_blocks(int ev_iter)
 {
-    const int L = schur_empty() ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    const int L = schur_empty() || schur_dense_ ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
     int ev_lin, nb;
     if (!gn_begin(ev_iter, ev_lin)) return 0;
+    if (schur_dense_ && !schur_dense_step(schur_g_)) return 0;      // (delta_c is in place, or the factor failed: nothing has been applied)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         const PrevAlpha a = prev_alpha(k);
@@ -117,7 +119,7 @@ void Plan::lm_loop_blocks(LmStep& st)
 {
     hipStream_t s = st.s;
     const bool schur = schur_on_;
-    const int L = schur_empty() ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const int L = schur_empty() || schur_dense_ ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
     const long n = schur ? schur_n_ : v_.n;
     const float* b = schur ? schur_g_ : v_.b;
     float* p = v_.p[0];
@@ -129,6 +131,7 @@ void Plan::lm_loop_blocks(LmStep& st)
         return rc;
     };
     int nb = 0;
+    if (schur_dense_ && !schur_dense_step(schur_g_)) { st.failed = true; return; }      // (S carries the step's CtC: each step factors anew)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
@@ -178,7 +181,10 @@ const char* Plan::schedule_name()
             t += "; Schur complement on the cameras, assembled";
             if (schur_on_ && schur_blocks_ >= 0) t += " (" + std::to_string(schur_blocks_) + " blocks)";
         } else t += "; Schur complement on the cameras";
-        t += "; block-Jacobi on S";
+        if (schur_on_ ? schur_dense_ : schur_dense_want_) {
+            t += "; dense Cholesky of S";
+            if (schur_on_ && plugin->schur_dense_n() >= 0) t += " (n = " + std::to_string(plugin->schur_dense_n()) + ")";
+        } else t += "; block-Jacobi on S";
     } else if (block_on_ || block_want_) t += "; block-Jacobi preconditioner (unfused PCG loop)";
     const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
     if (kind) {
@@ -282,15 +288,21 @@ int Plan::preconditioner_fallbacks() { return (block_on_ || schur_on_) && block_
 // ------------------------------------------------------------------ Schur complement on the cameras (ba_schur.hip, DESIGN.md "Schur complement on the cameras")
 int Plan::set_linear_solver(int kind)
 {
-    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG && kind != THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) { set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; schur_explicit_want_ = false; return 0; }
+    if (kind != THALLOX_SOLVER_PCG && kind != THALLOX_SOLVER_SCHUR_PCG && kind != THALLOX_SOLVER_SCHUR_EXPLICIT_PCG && kind != THALLOX_SOLVER_SCHUR_DENSE) {
+        set_error("%s: unknown linear solver kind %d", plugin->name(), kind); return -1;
+    }
+    if (kind == THALLOX_SOLVER_PCG) { schur_want_ = false; schur_explicit_want_ = false; schur_dense_want_ = false; return 0; }
     if (!ok_) return -1;
-    const bool ex = kind == THALLOX_SOLVER_SCHUR_EXPLICIT_PCG;
-    const char* what = ex ? "assembled Schur-complement solve" : "Schur-complement solve";
-    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a"); return -1; }
+    const bool dense = kind == THALLOX_SOLVER_SCHUR_DENSE, ex = dense || kind == THALLOX_SOLVER_SCHUR_EXPLICIT_PCG;      // (kind 3 implies the structure of kind 2)
+    const char* what = dense ? "dense Cholesky Schur-complement solve" : ex ? "assembled Schur-complement solve" : "Schur-complement solve";
+    if (plugin->direct_solve()) {
+        if (dense) set_error("%s: a direct-solve plan has no Schur complement to factor (it solves the full normal equations directly)", plugin->name());
+        else set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a");
+        return -1;
+    }
     if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
     if (dist_) { set_error("%s: the %s runs on one GPU (this plan is distributed)", plugin->name(), what); return -1; }
-    schur_want_ = true; schur_explicit_want_ = ex;
+    schur_want_ = true; schur_explicit_want_ = ex; schur_dense_want_ = dense;
     return 0;
 }
 
@@ -305,9 +317,12 @@ int Plan::schur_prepare()
     schur_pt_off_ = block_regions_.r[1].offset;
     // the assembled form: the structure of S, sized and checked against its budget before it is allocated
     schur_explicit_ = false;
+    plugin->schur_dense_want(schur_dense_want_);      // (the dense matrix is sized, refused, allocated and freed with the structure)
     schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
     if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
     schur_explicit_ = schur_explicit_want_;
+    schur_dense_ = schur_dense_want_ && plugin->schur_dense_n() >= 0;
+    if (schur_dense_want_ && !schur_dense_) { set_error("%s: the dense Cholesky Schur-complement solve is not available for this energy", plugin->name()); return -1; }
     if (schur_Ge_) return 0;
     const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
     schur_Ge_ = (float*)device_alloc((ns * (ns + 1) / 2 * np + 64) * sizeof(float)); schur_y_ = (float*)device_alloc((ns * np + 64) * sizeof(float));
@@ -320,6 +335,28 @@ int Plan::schur_prepare()
 }
 
 int Plan::schur_held_points() { return schur_on_ && schur_held_ ? read_word(schur_held_) : -1; }
+
+// ------------------------------------------------------------------ dense Cholesky of S (ba_schur_dense.hip, DESIGN.md "Dense Cholesky Schur solve")
+int Plan::schur_dense_nonpositive() { return schur_on_ && schur_dense_ && plugin->schur_dense_words() ? read_word(plugin->schur_dense_words() + 1) : -1; }
+
+void Plan::schur_dense_pivot_error(int index, const char* where)
+{
+    set_error("%s: %sthe dense Cholesky factor of the reduced camera matrix met a pivot that is not positive at camera %d, scalar %d (index %d of %ld): the system is singular or "
+              "indefinite in float32 -- fix the gauge with ThalloX_PlanSetHeldUnknowns (hold) or use Levenberg-Marquardt (ThalloX_EnableLM)", plugin->name(), where, index / 9, index % 9, index,
+              plugin->schur_dense_n());
+}
+
+// One step's dense solve behind forms_setup: expand, factor, delta_c = D L^-T L^-1 D g into the camera part of delta.  The step's ONE extra read-back sits here, behind
+// the solve's launch and in front of the back-substitution: a failed factor ends the step before anything is applied to the unknowns.  false: the error is set
+bool Plan::schur_dense_step(const float* g)
+{
+    const int rc = plugin->schur_dense_solve(ctx, held_on() ? held_mask_ : nullptr, g, v_.delta);
+    if (rc < 0) { set_error("%s: the dense Cholesky Schur-complement solve failed to launch (%d)", plugin->name(), rc); return false; }
+    const int info = read_word(plugin->schur_dense_words());
+    if (info < 0) { set_error("%s: cannot read the dense Cholesky factor's status word", plugin->name()); return false; }
+    if (info > 0) { schur_dense_pivot_error(info - 1, ""); return false; }
+    return true;
+}
 
 // ------------------------------------------------------------------ marginal covariances (ba_covariance.hip, DESIGN.md "Marginal covariances")
 // Sigma = (A_FF)^-1 with A = J_s^T J_s at the current unknowns, no CtC, on an LM plan too: the call re-linearises with the launches of a GN step's head -- PCGInit1
@@ -336,7 +373,8 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     if (dist_) { set_error("%s: the covariance runs on one GPU (this plan is distributed)", e); return -1; }
     if (!ready_) { set_error("%s: ThalloX_PlanCovariance before Thallo_ProblemInit: the covariance is taken at the unknowns of an initialised plan", e); return -1; }
     if (!schur_on_ || !schur_explicit_) {
-        set_error("%s: the plan's last Init did not run the assembled Schur-complement solve: set ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) before Thallo_ProblemInit", e);
+        set_error("%s: the plan's last Init did not run the assembled Schur-complement solve: set ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) before Thallo_ProblemInit "
+                  "(columns by PCG), or THALLOX_SOLVER_SCHUR_DENSE (columns through a dense Cholesky factor)", e);
         return -1;
     }
     const long elems = plugin->cov_elements(input);
@@ -344,8 +382,9 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     if (n <= 0 || !ids || !host_out) { set_error("%s: a covariance needs n > 0 ids and an output array (n = %ld)", e, n); return -1; }
     const float rel_tol = opt ? opt->rel_tol : 1e-6f;
     const int max_it = opt ? opt->max_iterations : 500;
-    if (!(rel_tol > 0.0f) || !std::isfinite(rel_tol)) { set_error("%s: the covariance's rel_tol must be finite and positive (got %g)", e, (double)rel_tol); return -1; }
-    if (max_it < 1) { set_error("%s: the covariance's max_iterations must be at least 1 (got %d)", e, max_it); return -1; }
+    if (schur_dense_) {}      // (the dense form accepts and ignores both)
+    else if (!(rel_tol > 0.0f) || !std::isfinite(rel_tol)) { set_error("%s: the covariance's rel_tol must be finite and positive (got %g)", e, (double)rel_tol); return -1; }
+    if (!schur_dense_ && max_it < 1) { set_error("%s: the covariance's max_iterations must be at least 1 (got %d)", e, max_it); return -1; }
     {   std::vector<char> seen((size_t)elems, 0);
         for (long i = 0; i < n; ++i) {
             if (ids[i] < 0 || ids[i] >= elems) { set_error("%s: covariance id %d (at %ld) is out of range: input %d has %ld elements", e, ids[i], i, input, elems); return -1; }
@@ -360,6 +399,12 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     const char* what = nullptr;
     if ((nb = forms_setup(nullptr, v_.r, slot(2), nb, what)) < 0) { set_error("%s: covariance: %s failed (%d)", e, what, nb); return -1; }
     thallo_cov_info_t ci;
+    if (schur_dense_) {      // expand and factor once per call, then every batch through two triangular sweeps: iterations 0, worst residual 0
+        int pivot = -1;
+        const int rc = plugin->covariance_dense(ctx, input, ids, n, block_G_, schur_Ge_, held_on() ? held_mask_ : nullptr, host_out, &ci, &pivot);
+        if (rc == -2) { schur_dense_pivot_error(pivot, "covariance: "); return -2; }
+        if (rc) return -1;
+    } else
     if (plugin->covariance(ctx, input, ids, n, block_G_, schur_Ge_, held_on() ? held_mask_ : nullptr, rel_tol, max_it, host_out, &ci)) return -1;
     if (info) { info->iterations = ci.iterations; info->columns = ci.columns; info->not_converged = ci.not_converged; info->nan_blocks = ci.nan_blocks; info->worst_residual = ci.worst; }
     return ci.not_converged;
