@@ -1,5 +1,5 @@
 """Shared helper of the per-kernel tests (test_gpu_pcg_chain.py, test_gpu_transport_kernels.py, test_gpu_sparse_kernels.py, test_gpu_graph_kernels.py,
-test_gpu_sfs_kernels.py, test_shim_references.py).
+test_gpu_sfs_kernels.py, test_gpu_ba_kernels.py, test_ba_reference.py, test_shim_references.py).
 
 Four things live here:
   * shim(): the library with argtypes / restype declared once for every thallo_hip.h entry point those files call;
@@ -136,6 +136,18 @@ def shim():
         "sfs_lm_model_cost": [it] * 6 + [vp] * 11 + [it, vp, it, vp, vp, vp, vp, vp],
         "sfs_march_debug_set": [it, it], "sfs_planes_layout": [it, it], "sfs_march_fits": [it], "sfs_lm_pupdate_supported": [],
         "checksum_i32": [lg, vp, vp, vp],
+        # bundle adjustment (csrc/energy_ba.hip; test_gpu_ba_kernels.py): C, P first; the lists, cameras, points, JP, JpC = 8 pointers
+        "ba_cost": [it] * 3 + [vp] * 7,
+        "ba_compute_j": [it] + [vp] * 9, "ba_compute_j_ad": [it] + [vp] * 9, "ba_compute_j_robust": [it] + [vp] * 6 + [it, fl] + [vp] * 4,
+        "ba_pcg_init": [it, it] + [vp] * 15,
+        "ba_point_order": [it, vp, vp, vp], "ba_pack_point_blocks": [it, vp, vp, vp, vp],
+        "ba_apply2_camera_slots": [it, it],
+        "ba_apply_jtj2": [it, it] + [vp] * 8 + [vp] * 7 + [vp],
+        "ba_apply_jtj2_fin": [it, it] + [vp] * 8 + [vp] * 7 + [FinT, vp],
+        "ba_apply_jtj2_fin_robust": [it, it] + [vp] * 8 + [vp] * 7 + [FinT, vp, vp],
+        "ba_apply_jtj2_lm": [it, it] + [vp] * 8 + [vp] * 5 + [vp],
+        "ba_lm_reset_residual": [it, it] + [vp] * 8 + [vp] * 7 + [vp],
+        "ba_pcg_apply_lm": [it, it] + [vp] * 8 + [vp] * 10 + [FinT, vp, it, fl, it, it, vp],
     }
     for name, args in sig.items():
         f = getattr(L, "thallo_hip_" + name)
