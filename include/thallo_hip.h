@@ -263,11 +263,12 @@ int thallo_hip_lapimg_pcg_step1(int W, int H, float w_fit, int xguard,
  *                            bits2-4 = number of valid neighbour pairs (0..4)
  * Row slabs: W x H is the LOCAL image, which may carry one ghost row above and/or below; the kernels
  * produce outputs for the owned rows [row0,row1) only (row0=0,row1=H for a whole image) and read the
- * ghost rows as stencil halo.  pcg_init also fills cs/flags (and p_prev=0) on ghost rows; the fused
- * pcg_step1 also keeps p current on ghost rows (p = z + beta p), so per PCG iteration only the ghost
- * rows of z have to be refreshed from the neighbouring slab.
- * `irregular` (device int, may be NULL): pcg_init stores the number of pixels whose right/down UrShape neighbours are
- * NOT at exact unit offsets; when it is 0 (UrShape = the pixel grid, which is what the reference's harness always
+ * ghost rows as stencil halo.  pcg_init also fills cs/flags (and p_prev=0) on ghost rows -- of the flags byte bit 0
+ * only: the fit bit and the count depend on rows the slab does not hold, the caller copies the byte from the
+ * neighbouring slab; the fused pcg_step1 also keeps p current on ghost rows (p = z + beta p), so per PCG iteration
+ * only the ghost rows of z have to be refreshed from the neighbouring slab.
+ * `irregular` (device int, may be NULL): pcg_init stores the number of pixels of the owned rows whose right/down UrShape
+ * neighbours (inside the local image) are NOT at exact unit offsets; when it is 0 (UrShape = the pixel grid, which is what the reference's harness always
  * passes: CombinedSolver.h:158-176) pcg_step1 / apply_jtj skip the UrShape plane (-8 B/pixel); the bits of the
  * result are the same either way. */
 int thallo_hip_iw_cost(int W, int H, int row0, int row1, const float* offset, const float* angle, const float* urshape,
@@ -355,8 +356,9 @@ unsigned thallo_hip_iw_iter_size(void);         /* sizeof(thallo_iw_iter_t) as t
  * peer-to-peer, and its last workgroup is the scalar exchange), and on a ghost row J^T J p_in is READ from Ap_in, where the exchange put it -- so the two kernels
  * are interchangeable launch by launch.  Replaces PCGStep1 + PCGStep2 + PCGStep3 (gauss_newton.t:734-752,801-843,889-899). */
 enum { THALLO_IW_ITER_TILE = 0, THALLO_IW_ITER_MARCH = 1, THALLO_IW_ITER_MARCH_RC = 2 };
-/* Returns the workgroup count (= number of partials), or a negative hipError_t: -hipErrorInvalidValue for a malformed block, -hipErrorNotSupported for a form
- * the kernel does not have (the deferred cross-rank finish on the tile or stored-plane kernel, `prev` with `dist` but no gs) or a shape it does not take. */
+/* Returns the workgroup count (= number of partials), or a negative hipError_t: -hipErrorInvalidValue for a malformed block (an odd W on a marching kernel and a first
+ * iteration on the recomputing one included), -hipErrorNotSupported for a form the kernel does not have (the deferred cross-rank finish on the tile or stored-plane
+ * kernel, `prev` with `dist` but no gs) or a shape it does not take (more column strips than workgroup slots: thallo_hip_iw_march_rows() == 0; a vector of 4 GiB). */
 int thallo_hip_iw_pcg_iter(int kernel, const thallo_iw_iter_t* a, thallo_stream_t stream);
 /* 1: the deferred cross-rank finish may run on `rows` owned rows of a W-wide slab (every workgroup of its launch, the eight extra ones included, is resident at once:
    its working waves wait for the last workgroup's granules); 0: the caller leaves gs NULL (the exchange at the launch's end) */
@@ -411,7 +413,9 @@ int thallo_hip_iw_pcg_iter_finish(const float* alphaD_partials, const double* s1
 
 /* image_warping's PCGStep2 (gauss_newton.t:801-843 minus delta): r -= alpha*Ap, betaN partials = sum (M^-1 r).r over the owned
  * rows.  When *irregular == 0 (UrShape = unit pixel grid) M^-1 is recomputed from the flags byte and z is NOT written
- * (37 B/pixel instead of 60) -- pcg_step1 then forms z = M^-1 r from `r` on the fly; otherwise pre is read and z written. */
+ * (37 B/pixel instead of 60) -- pcg_step1 then forms z = M^-1 r from `r` on the fly; otherwise pre is read and z written.
+ * Where the image or the row range is not 16-byte granular (2 W H, W row0 or W rows no multiple of 4) pre is read and z written whatever the word says: a whole
+ * image through thallo_hip_pcg_step2 (vectors padded to a multiple of 4 floats), a row range element by element. */
 int thallo_hip_iw_pcg_step2(int W, int H, int row0, int row1, const unsigned char* flags, float w_fit, float w_reg,
                             float* r, const float* Ap, const float* pre, float* z,
                             thallo_sum_t alphaN, thallo_sum_t alphaD, const int* irregular, float* betaN_out, thallo_stream_t stream);

@@ -1,5 +1,5 @@
 """Shared helper of the per-kernel tests (test_gpu_pcg_chain.py, test_gpu_transport_kernels.py, test_gpu_sparse_kernels.py, test_gpu_graph_kernels.py,
-test_gpu_sfs_kernels.py, test_gpu_ba_kernels.py, test_ba_reference.py, test_shim_references.py).
+test_gpu_sfs_kernels.py, test_gpu_ba_kernels.py, test_gpu_iw_kernels.py, test_ba_reference.py, test_shim_references.py).
 
 Four things live here:
   * shim(): the library with argtypes / restype declared once for every thallo_hip.h entry point those files call;
@@ -45,6 +45,9 @@ class PrevT(C.Structure):            # thallo_prev_t
 class FinT(C.Structure):             # thallo_fin_t
     _fields_ = [("alphaN", api.SumT), ("tickets", C.c_void_p), ("alphaD_word", C.c_void_p), ("betaN_word", C.c_void_p)]
 
+
+IwIterT = api.IwIterT                # thallo_iw_iter_t: the one mirror of the block (thallo_amd/api.py); shim() checks it against thallo_hip_iw_iter_size()
+IW_ITER_TILE, IW_ITER_MARCH, IW_ITER_MARCH_RC = api.IW_ITER_TILE, api.IW_ITER_MARCH, api.IW_ITER_MARCH_RC
 
 NO_FIN = FinT(api.SumT(None, 0), None, None, None)
 FIN_TICKET_WORDS = 528           # THALLO_HIP_FIN_TICKET_WORDS
@@ -148,11 +151,30 @@ def shim():
         "ba_apply_jtj2_lm": [it, it] + [vp] * 8 + [vp] * 5 + [vp],
         "ba_lm_reset_residual": [it, it] + [vp] * 8 + [vp] * 7 + [vp],
         "ba_pcg_apply_lm": [it, it] + [vp] * 8 + [vp] * 10 + [FinT, vp, it, fl, it, it, vp],
+        # the image-stencil plugins (csrc/energy_image_warping*.hip, energy_laplacian_image.hip; test_gpu_iw_kernels.py): W, H (, row0, row1) first
+        "iw_cost": [it] * 4 + [vp] * 5 + [fl, fl, vp, vp],
+        "iw_pcg_init": [it] * 4 + [vp] * 5 + [fl, fl] + [vp] * 11,
+        "iw_pcg_step1": [it] * 4 + [vp] * 3 + [fl, fl] + [vp] * 5 + [it] + [S] * 5 + [vp] * 4,
+        "iw_pcg_step2": [it] * 4 + [vp, fl, fl] + [vp] * 4 + [S, S] + [vp] * 3,
+        "iw_apply_jtj": [it] * 4 + [vp] * 3 + [fl, fl] + [vp] * 5,
+        "iw_pcg_iter": [it, C.POINTER(api.IwIterT), vp], "iw_iter_size": [],
+        "iw_pcg_iter_finish": [vp, vp, it, S, vp, vp, vp],
+        "iw_urshape_irregular": [it, it, vp, vp, vp],
+        "iw_march_rows": [it, it], "iw_march_place": [it] * 5 + [vp], "march_debug_set": [it, it],
+        "iw_resident_rows": [it, it], "iw_resident_bytes": [it, it], "resident_debug_set": [it, it],
+        "iw_pcg_resident": [it] * 4 + [vp, vp, fl, fl] + [vp] * 6 + [S] + [vp] * 5 + [it, vp],
+        "iw_resident_status": [vp, it, it, vp, vp],
+        "lapimg_cost": [it, it, vp, vp, fl, it, vp, vp],
+        "lapimg_pcg_init": [it, it, vp, vp, fl, it] + [vp] * 7,
+        "lapimg_apply_jtj": [it, it, fl, it] + [vp] * 4,
+        "lapimg_pcg_step1": [it, it, fl, it] + [vp] * 5 + [it] + [S] * 3 + [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, "thallo_hip_" + name)
         f.argtypes = args
-        f.restype = None if name in ("lm_set_gate", "arap_debug_set", "sfs_march_debug_set") else lg if name == "vector_elems" else it
+        f.restype = (None if name in ("lm_set_gate", "arap_debug_set", "sfs_march_debug_set", "march_debug_set", "resident_debug_set")
+                     else lg if name in ("vector_elems", "iw_resident_bytes") else C.c_uint if name == "iw_iter_size" else it)
+    assert L.thallo_hip_iw_iter_size() == C.sizeof(api.IwIterT), "thallo_iw_iter_t and its ctypes mirror differ"
     _SHIM = L
     return L
 

@@ -344,6 +344,25 @@ __global__ __launch_bounds__(BLOCK) void k_step2_iw(float4* __restrict__ r, cons
     block_store_partial(acc, bN_out, red);
 }
 
+// A row range that is not 16-byte granular (odd W x row0 or W x rows: the float4 kernels above and the generic ranges kernel cannot address it): the same
+// update element by element, the generic form (reads pre -- NULL: the identity --, writes z).  No slab the solver cuts is such a range; the entry point takes one.
+__global__ __launch_bounds__(BLOCK) void k_step2_iw_rows(float* __restrict__ r, const float* __restrict__ Ap, const float* __restrict__ pre, float* __restrict__ z,
+                                                         long off0, long len0, long off1, long len1, thallo_sum_t aN, thallo_sum_t aD, float* __restrict__ bN_out)
+{
+    __shared__ float red[16];
+    const float alpha = safe_div<false>(sum_partials(aN.partials, aN.count), sum_partials(aD.partials, aD.count));
+    float acc = 0.0f;
+    const long n = len0 + len1;
+    for (long j = (long)blockIdx.x * BLOCK + threadIdx.x; j < n; j += (long)gridDim.x * BLOCK) {
+        const long i = j < len0 ? off0 + j : off1 + (j - len0);
+        const float rv = r[i] - alpha * Ap[i];
+        const float zv = pre ? pre[i] * rv : rv;
+        r[i] = rv; z[i] = zv;
+        acc += zv * rv;
+    }
+    block_store_partial(acc, bN_out, red);
+}
+
 // ------------------------------------------------------------------------------------------ PCGInit1 (+_Finish)
 // Once per GN iteration: evalJTF in gather form, guardedInvert, z = M^-1 r, p_prev = 0, delta = 0 (unless delta == NULL), the
 // (cos,sin) and validity planes, alphaN partials.  Not pipelined (1 % of a GN iteration).
@@ -392,8 +411,9 @@ __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict_
                 const long pix = (long)gy * g.W + gx;
                 const unsigned char act = T.f[i] & 1;
                 // is UrShape the unit pixel grid here?  (right and down neighbour inside the local image)
-                if (gx + 1 < g.W && (T.ux[i + 1] - T.ux[i] != 1.0f || T.uy[i + 1] - T.uy[i] != 0.0f)) bad = 1;
-                if (gy + 1 < g.H && (T.ux[i + LW] - T.ux[i] != 0.0f || T.uy[i + LW] - T.uy[i] != 1.0f)) bad = 1;
+                const bool bad_x = gx + 1 < g.W && (T.ux[i + 1] - T.ux[i] != 1.0f || T.uy[i + 1] - T.uy[i] != 0.0f);
+                const bool bad_y = gy + 1 < g.H && (T.ux[i + LW] - T.ux[i] != 0.0f || T.uy[i + LW] - T.uy[i] != 1.0f);
+                if (bad_x || bad_y) ++bad;                          // one per PIXEL: the header promises their number
                 float rx = 0.f, ry = 0.f, ra = 0.f, mx = 0.f, my = 0.f, ma = 0.f, dgo_raw = 0.f, dga_raw = 0.f;
                 unsigned char fl = act;
                 if (act) {
@@ -447,7 +467,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict_
         }
         __syncthreads();
     }
-    if (irregular && __any(bad) && (threadIdx.x & 63) == 0) atomicAdd(irregular, 1);     // int atomic: exact, order-free
+    if (irregular && bad) atomicAdd(irregular, bad);     // int atomic: exact, order-free; no thread gets here on the unit grid
     block_store_partial(acc, aN_out, red);
 }
 
@@ -859,7 +879,13 @@ int thallo_hip_iw_pcg_step2(int W, int H, int row0, int row1, const unsigned cha
     const long off0 = 2L * W * row0, len0 = 2L * W * rows, off1 = 2 * N + (long)W * row0, len1 = (long)W * rows;
     if (g_no_grid || ((off0 | len0 | off1 | len1 | (2 * N)) & 3)) {     // not 16-byte granular: the generic kernels (read pre, write z)
         if (row0 == 0 && row1 == H) return thallo_hip_pcg_step2(r, Ap, pre, z, 3 * N, aN, aD, bN_out, stream);
-        return thallo_hip_pcg_step2_ranges(r, Ap, pre, z, off0, len0, off1, len1, aN, aD, bN_out, stream);
+        if (!((off0 | len0 | off1 | len1) & 3)) return thallo_hip_pcg_step2_ranges(r, Ap, pre, z, off0, len0, off1, len1, aN, aD, bN_out, stream);
+        if (!z) return -(int)hipErrorInvalidValue;
+        long want1 = (len0 + len1 + BLOCK - 1) / BLOCK;                 // (the ranges kernel refuses what is not a multiple of 4 floats)
+        int grid1 = thallo_hip_device_cu_count() * 4; if (grid1 > THALLO_MAX_PARTIALS) grid1 = THALLO_MAX_PARTIALS; grid1 -= grid1 % 8;
+        if (want1 < grid1) grid1 = (int)(want1 < 1 ? 1 : want1);
+        hipLaunchKernelGGL(k_step2_iw_rows, dim3(grid1), dim3(BLOCK), 0, (hipStream_t)stream, r, Ap, pre, z, off0, len0, off1, len1, aN, aD, bN_out);
+        int e1 = check_launch(); return e1 ? e1 : grid1;
     }
     long want = ((len0 + len1) / 4 + BLOCK - 1) / BLOCK;
     int grid = thallo_hip_device_cu_count() * 4; if (grid > THALLO_MAX_PARTIALS) grid = THALLO_MAX_PARTIALS; grid -= grid % 8;

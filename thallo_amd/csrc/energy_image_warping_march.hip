@@ -270,10 +270,12 @@ __global__ __launch_bounds__(256) void k_urshape_check(int W, int H, const float
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % W), y = (int)(i / W);
         const float2 u = ur[i];
-        if (x + 1 < W) { const float2 v = ur[i + 1]; if (v.x - u.x != 1.0f || v.y - u.y != 0.0f) bad = 1; }
-        if (y + 1 < H) { const float2 v = ur[i + W]; if (v.x - u.x != 0.0f || v.y - u.y != 1.0f) bad = 1; }
+        bool off = false;
+        if (x + 1 < W) { const float2 v = ur[i + 1]; off = v.x - u.x != 1.0f || v.y - u.y != 0.0f; }
+        if (y + 1 < H) { const float2 v = ur[i + W]; off = off || v.x - u.x != 0.0f || v.y - u.y != 1.0f; }
+        if (off) ++bad;                                  // one per PIXEL: *count_out is their number
     }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicAdd(bad_out, 1);
+    if (bad) atomicAdd(bad_out, bad);
 }
 
 constexpr int MARCH_OCC = 2;     // register budget: two workgroups of 4 waves per CU (<= 256 VGPRs), the grid is sized for one
