@@ -138,7 +138,29 @@ const char* ThalloX_PlanScheduleName(Thallo_Plan* plan);
  * plan (ThalloX_PlanSetDistributed after this call is refused likewise), a direct-solve plan. */
 #define THALLOX_PRECOND_JACOBI       0   /* the reference's; default */
 #define THALLOX_PRECOND_BLOCK_JACOBI 1
+/* THALLOX_PRECOND_TWO_LEVEL: on the ASSEMBLED reduced camera matrix (THALLOX_SOLVER_SCHUR_EXPLICIT_PCG below), the camera blocks plus a coarse correction that couples
+ * neighbouring cameras, M^-1 = G^T G + P S_c^-1 P^T: the cameras are aggregated by co-visibility, the coarse space is piecewise constant per camera parameter (9 K scalars
+ * for K aggregates, empty at held scalars), S_c = P^T S P is assembled, Jacobi-scaled and factored densely in float32 every step (in LM with the step's diagonal), and
+ * every M^-1 r of the reduced PCG loop -- ThalloX_PlanCovariance's column PCG too -- adds P Z^T Z P^T r, Z = L^-1 D.  It removes most of the growth of the iteration count
+ * with the length of the camera chain, which the camera blocks cannot bridge: it is for covariances and for tight reduced solves (a small q_tolerance, GN with many
+ * lIterations); at q_tolerance = 0.1 an LM step's reduced solve takes 2 - 3 iterations either way and the set-up is pure cost.  What it does not fix: the converged float32
+ * column still differs from a float64 solve by the float32 S's own error.  Accepted and refused exactly where THALLOX_PRECOND_BLOCK_JACOBI is; takes effect at the next
+ * Init, WHICH FAILS (ThalloX_PlanReady 0, ThalloX_LastError naming both settings) unless the plan's linear solver is THALLOX_SOLVER_SCHUR_EXPLICIT_PCG -- in whichever
+ * order the two setters were called; THALLOX_SOLVER_SCHUR_DENSE ignores the preconditioner as before.  ThalloX_PlanScheduleName then ends "...; two-level on S (K
+ * aggregates, n_c = N)".  A coarse factor that meets a pivot that is not positive fails nothing: Z = 0 for that step (block Jacobi alone) and ThalloX_PlanCoarseSpace
+ * counts it.  The coarse matrices' bytes are added to the structure's count before anything is allocated.  A plan that never asks for it launches what it launched before. */
+#define THALLOX_PRECOND_TWO_LEVEL    2
 int ThalloX_PlanSetPreconditioner(Thallo_Plan* plan, int kind);
+/* The aggregates of THALLOX_PRECOND_TWO_LEVEL, between Thallo_ProblemPlan and Thallo_ProblemInit (or before a re-Init).  (0, NULL, 0): the default, greedy aggregates of at
+ * most k = max(8, ceil(C / 128)) cameras; (k >= 1, NULL, 0): greedy aggregates of at most k cameras -- built on the host at Init from the structure of S: cameras in
+ * ascending id, an unassigned camera seeds an aggregate, which repeatedly takes the unassigned camera with the largest summed number of co-visible points to its members
+ * (ties: the lower id) until it has k members or no connected camera is left; deterministic; held cameras are assigned like any other (their rows of P are zero).  Or
+ * aggregate_of_camera: n = C ids in the caller's camera ids, dense 0 .. K - 1 with every id used.  Returns 0, or nonzero with ThalloX_LastError naming the reason. */
+int ThalloX_PlanSetCoarseAggregates(Thallo_Plan* plan, int cameras_per_aggregate, const int* aggregate_of_camera, long n);
+/* out = { the aggregates K, the coarse scalars n_c = 9 K, the coarse scalars of the last set-up that were given the identity's row (every member held there, or nothing
+ * observed), the coarse factors since Thallo_ProblemInit that met a pivot that is not positive }; returns 0, or -1 when the two-level form does not run.  Synchronises the
+ * plan's stream. */
+int ThalloX_PlanCoarseSpace(Thallo_Plan* plan, long out[4]);
 /* Blocks of the last step's factorisation that were not positive definite in float32 and fell back to their point-Jacobi diagonal (they behave as under
  * THALLOX_PRECOND_JACOBI); -1 when the block form does not run.  Synchronises the plan's stream. */
 int ThalloX_PlanPreconditionerFallbacks(Thallo_Plan* plan);

@@ -920,6 +920,50 @@ int thallo_hip_dense_potrs_cols(long n, long ld, const float* L, const float* d,
 /* x = D L^-T L^-1 D b for one right-hand side (x != b; d = NULL: D = I; sweeps as above): one launch, one workgroup. */
 int thallo_hip_dense_potrs_vec(long n, long ld, const float* L, const float* d, const float* b, float* x, int sweeps, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- the coarse correction of the two-level preconditioner on S (ba_coarse.hip; DESIGN.md "Two-level preconditioner")
+ * The cameras in K aggregates (agg: C ids in 0 .. K - 1, every id used; mem_ptr / mem: the aggregates' member lists, K + 1 places and C cameras), the coarse space piecewise
+ * constant per camera parameter and empty at held scalars: P[9 c + j, 9 agg[c] + j] = 1 where hold[9 c + j] == 0 (hold: 9 C bytes or NULL), n = 9 K coarse scalars.
+ * T (the dense lower triangle of P^T S P, then of its Jacobi scaling, then its Cholesky factor: ld x n floats in thallo_hip_dense_ld's layout, 16-byte aligned), d (n),
+ * Z = L^-1 D and Zt = Z^T (row-major, ld x n floats each), y (n) and three words -- [0] thallo_hip_dense_potrf's info, [1] the coarse scalars of the last scaling that got
+ * the identity's row, [2] the factors since the caller zeroed it that met a pivot that is not positive -- are the caller's device buffers.  No float atomics, one summation
+ * order per shape: two runs give equal bits. */
+#define THALLO_HIP_COARSE_MAX_N    8192     /* coarse scalars: r_c sits in LDS (910 aggregates) */
+#define THALLO_HIP_COARSE_PARTIALS 64       /* the most partials of y . y an apply leaves */
+typedef struct thallo_coarse_t {
+    int C, K;
+    long n, ld;                           /* 9 K, thallo_hip_dense_ld(n) */
+    const int *agg, *mem_ptr, *mem;
+    const unsigned char* hold;
+    float *T, *d, *Z, *Zt, *y;
+    unsigned* words;
+} thallo_coarse_t;
+/* The lower triangle of S_c = P^T S P into T, unscaled, for the assembled S of thallo_hip_ba_schur_assemble: block (a, b), b <= a, is the sum of S_cc' over c in a (list
+ * order) and the blocks of row c with c' in b (ascending column), held rows and columns left out.  Writes every entry (i, j), j <= i < n, and nothing else. */
+int thallo_hip_ba_coarse_assemble(const thallo_coarse_t* c, long nblk, const int* row_ptr, const int* col, const float* S, thallo_stream_t stream);
+/* d[i] = 1 / sqrt(T_ii) and T_ij = float(float(d_i T_ij) d_j) in place, j <= i.  A coarse scalar whose diagonal is not positive gets d = 0 and the identity's row and column;
+ * words[1] = their number. */
+int thallo_hip_ba_coarse_scale(const thallo_coarse_t* c, thallo_stream_t stream);
+/* Z = L^-1 D and Zt = Z^T from the factor thallo_hip_dense_potrf left in T: identity panels (panels: thallo_hip_ba_coarse_panel_floats(n) device floats of work) through
+ * thallo_hip_dense_potrs_cols' forward sweep, then a packing launch.  It reads words[0] on the device: where it is not zero, Z and Zt are all zeros and words[2] goes up by one. */
+long thallo_hip_ba_coarse_panel_floats(long n);
+int thallo_hip_ba_coarse_inverse(const thallo_coarse_t* c, float* panels, thallo_stream_t stream);
+/* z += P Zt Z P^T r for camera vectors r, z (9 C floats; z holds the block term already) and the partials of |Z P^T r|^2 into yy_out (returns their number,
+ * <= THALLO_HIP_COARSE_PARTIALS): two launches.  z at a held scalar is not touched.  gate: as thallo_hip_ba_schur_apply_s. */
+int thallo_hip_ba_coarse_apply(const thallo_coarse_t* c, const float* r, float* z, float* yy_out, const unsigned* gate, thallo_stream_t stream);
+/* The covariance's panel form: Zp += P Zt Z P^T R for panels [9 C][THALLO_HIP_COV_K] (Zp holds the block term already), one lane per column, and per column the partials of
+ * |Z P^T r|^2 at yy_out[w * THALLO_HIP_COV_K + column] (returns their number per column, <= THALLO_HIP_COARSE_COLS_PARTIALS): three launches.  A column's result does not
+ * depend on its companions, a zero column stays zero; a column with frozen[column] != 0 (THALLO_HIP_COV_K device words, or NULL: none) is not touched and leaves zero
+ * partials.  work: thallo_hip_ba_coarse_cols_work_floats(n) device floats. */
+#define THALLO_HIP_COARSE_COLS_PARTIALS 256
+long thallo_hip_ba_coarse_cols_work_floats(long n);
+int thallo_hip_ba_coarse_apply_cols(const thallo_coarse_t* c, float* work, const float* R, float* Zp, const unsigned* frozen, float* yy_out, thallo_stream_t stream);
+/* thallo_hip_ba_cov_solve with the two-level preconditioner: the same batch, every Z = M^-1 R of its PCG with the coarse term added by thallo_hip_ba_coarse_apply_cols and the
+ * partials of |y|^2 behind those of r . z_B in the slot the scalar launch adds up, one fixed order.  coarse == NULL: thallo_hip_ba_cov_solve itself, launch for launch.
+ * work: thallo_hip_ba_cov_coarse_work_bytes(C, n) device bytes (n: the coarse scalars, 0 without the form). */
+long thallo_hip_ba_cov_coarse_work_bytes(int C, long n);
+int thallo_hip_ba_cov_solve_coarse(const thallo_cov_sys_t* sys, const thallo_coarse_t* coarse, int mode, const int* ids, int nreq, float rel_tol, int max_iterations, void* work,
+                                   unsigned* pinned, float* out, thallo_cov_info_t* info, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- materialized schedules (CSR) */
 /* y = A x for a CSR matrix (rows+1 row pointers, int32 columns, float values); with dot_with / dot_out (both or neither) it also writes
    the per-workgroup partials of dot_with . y.  Replaces the cuSPARSE csrmv calls of gauss_newton.t:1470-1517: `[Jt][[J]p]` = two calls

@@ -132,6 +132,9 @@ def lib():
     L.ThalloX_PlanSchurBlocks.argtypes = [vp]; L.ThalloX_PlanSchurBlocks.restype = C.c_int
     if hasattr(L, "ThalloX_PlanSchurDenseNonPositive"):      # (THALLO_LIB may name an A/B build from before the call existed)
         L.ThalloX_PlanSchurDenseNonPositive.argtypes = [vp]; L.ThalloX_PlanSchurDenseNonPositive.restype = C.c_int
+    if hasattr(L, "ThalloX_PlanSetCoarseAggregates"):      # (likewise)
+        L.ThalloX_PlanSetCoarseAggregates.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetCoarseAggregates.restype = C.c_int
+        L.ThalloX_PlanCoarseSpace.argtypes = [vp, vp]; L.ThalloX_PlanCoarseSpace.restype = C.c_int
     L.ThalloX_PlanSetHeldUnknowns.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetHeldUnknowns.restype = C.c_int
     L.ThalloX_PlanHeldUnknowns.argtypes = [vp]; L.ThalloX_PlanHeldUnknowns.restype = C.c_long
     if hasattr(L, "ThalloX_PlanSetRobustLoss"):      # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_robust_bench.py --ab)
@@ -410,15 +413,35 @@ class ThalloSolver:
         """Run the LM branch of gauss_newton.t (dead as shipped in the reference, see include/Thallo.h)."""
         self._L.ThalloX_EnableLM(self.plan, 1 if on else 0)
 
-    PRECONDITIONERS = {"jacobi": 0, "block_jacobi": 1}      # THALLOX_PRECOND_* of include/Thallo.h
+    PRECONDITIONERS = {"jacobi": 0, "block_jacobi": 1, "two_level": 2}      # THALLOX_PRECOND_* of include/Thallo.h
 
     def set_preconditioner(self, kind):
-        """"jacobi" (the reference's, default) or "block_jacobi" (bundle_adjustment: 9 x 9 camera and 3 x 3 point blocks); before init().  Raises, with the library's
-        reason, where the plan has no block form (include/Thallo.h ThalloX_PlanSetPreconditioner)."""
+        """"jacobi" (the reference's, default), "block_jacobi" (bundle_adjustment: 9 x 9 camera and 3 x 3 point blocks) or "two_level" (on the "schur_explicit_pcg" linear
+        solver alone -- init() fails otherwise: the camera blocks plus a dense coarse correction over aggregates of co-visible cameras, for covariances and tight reduced
+        solves); before init().  Raises, with the library's reason, where the plan has no block form (include/Thallo.h ThalloX_PlanSetPreconditioner)."""
         if kind not in self.PRECONDITIONERS:
             raise ValueError(f"preconditioner {kind!r}: expected one of {sorted(self.PRECONDITIONERS)}")
         if self._L.ThalloX_PlanSetPreconditioner(self.plan, self.PRECONDITIONERS[kind]) != 0:
             raise RuntimeError("ThalloX_PlanSetPreconditioner failed: " + last_error())
+
+    def set_coarse_aggregates(self, cameras_per_aggregate=None, aggregates=None):
+        """The aggregates of the "two_level" preconditioner (include/Thallo.h ThalloX_PlanSetCoarseAggregates): nothing given = the default size, `cameras_per_aggregate`
+        = greedy aggregates of at most that many co-visible cameras, or `aggregates` = one dense aggregate id per camera (the caller's camera ids); before init()."""
+        if aggregates is not None:
+            import numpy as np
+            a = np.ascontiguousarray(np.asarray(aggregates), dtype=np.int32).reshape(-1)
+            rc = self._L.ThalloX_PlanSetCoarseAggregates(self.plan, 0, a.ctypes.data_as(C.c_void_p), int(a.size))
+        else:
+            rc = self._L.ThalloX_PlanSetCoarseAggregates(self.plan, int(cameras_per_aggregate or 0), None, 0)
+        if rc != 0:
+            raise RuntimeError("ThalloX_PlanSetCoarseAggregates failed: " + last_error())
+
+    def coarse_space(self):
+        """{"aggregates", "coarse_scalars", "identity_rows", "failed_factors"} of the "two_level" preconditioner since init(), or None when it does not run."""
+        out = (C.c_long * 4)()
+        if self._L.ThalloX_PlanCoarseSpace(self.plan, out) != 0:
+            return None
+        return {"aggregates": out[0], "coarse_scalars": out[1], "identity_rows": out[2], "failed_factors": out[3]}
 
     def preconditioner_fallbacks(self):
         """Blocks of the last step that fell back to their diagonal (-1: the block form does not run)."""

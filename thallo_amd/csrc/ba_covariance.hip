@@ -377,4 +377,87 @@ int thallo_hip_ba_cov_solve(const thallo_cov_sys_t* sys, int mode, const int* id
     return done(0);
 }
 
+// ------------------------------------------------------------------ the same batch under the two-level preconditioner (ba_coarse.hip)
+// The work buffer: thallo_hip_ba_cov_solve's, then the slot of r . z with room for the coarse partials behind the block term's, then the coarse panels r_c and Y
+long thallo_hip_ba_cov_coarse_work_bytes(int C_, long n)
+{
+    const long base = thallo_hip_ba_cov_work_bytes(C_);
+    if (base < 0 || n < 0) return -1;
+    if (n == 0) return base;
+    const long cw = thallo_hip_ba_coarse_cols_work_floats(n);
+    return cw < 0 ? -1 : base + (((long)cov_grid(C_) + THALLO_HIP_COARSE_COLS_PARTIALS) * K + cw + 64) * (long)sizeof(float);
+}
+
+int thallo_hip_ba_cov_solve_coarse(const thallo_cov_sys_t* sys, const thallo_coarse_t* coarse, int mode, const int* ids, int nreq, float rel_tol, int max_iterations, void* work,
+                                   unsigned* pinned, float* out, thallo_cov_info_t* info, thallo_stream_t stream)
+{
+    if (!coarse) return thallo_hip_ba_cov_solve(sys, mode, ids, nreq, rel_tol, max_iterations, work, pinned, out, info, stream);
+    if (!sys_ok(sys) || (mode != 0 && mode != 1) || !ids || nreq < 1 || nreq > max_requests(mode) || !work || !out || !info || max_iterations < 1 || !(rel_tol > 0.0f) ||
+        !std::isfinite(rel_tol) || (mode == 1 && !points_ok(sys)) || coarse->C != sys->C) return -(int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const int C_ = sys->C, g = cov_grid(C_);
+    const long pn = panel_floats(C_);
+    const Work w = carve(work, C_);
+    float* pb2 = reinterpret_cast<float*>(static_cast<char*>(work) + thallo_hip_ba_cov_work_bytes(C_));      // the slot of r . z: g partials of the block term, then the coarse term's
+    float* cwork = pb2 + ((long)g + THALLO_HIP_COARSE_COLS_PARTIALS) * K;
+    const unsigned* frozen = reinterpret_cast<const unsigned*>(w.sc) + SC_FROZEN * K;
+    const float tol2 = rel_tol * rel_tol;
+    hipError_t he;
+    auto bad = [&](hipError_t e) { return -(int)e; };
+    if ((he = hipMemsetAsync(w.X, 0, sizeof(float) * (size_t)pn, s)) != hipSuccess) return bad(he);
+    if ((he = hipMemsetAsync(w.words, 0, 4 * sizeof(unsigned), s)) != hipSuccess) return bad(he);
+    int rc, gc;
+    if ((rc = thallo_hip_ba_cov_rhs(sys, mode, ids, nreq, w.R, stream)) < 0) return rc;
+    if ((rc = thallo_hip_ba_cov_precond_cols(C_, sys->Gc, w.R, w.Z, pb2, stream)) < 0) return rc;
+    if ((gc = thallo_hip_ba_coarse_apply_cols(coarse, cwork, w.R, w.Z, nullptr, pb2 + (long)g * K, stream)) < 0) return gc;
+    hipLaunchKernelGGL(k_cov_scal<SCAL_INIT>, dim3(1), dim3(4 * K), 0, s, g + gc, pb2, w.sc, tol2, w.words);
+    if ((rc = check_launch()) < 0) return rc;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    if (pinned) for (int i = 0; i < 2; ++i) if ((he = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) { if (ev[0]) (void)hipEventDestroy(ev[0]); return bad(he); }
+    auto done = [&](int code) { for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); return code; };
+    const int pgrid = (int)((pn + 255) / 256 > 2048 ? 2048 : (pn + 255) / 256);
+    int it = 0, chunk = 0;
+    unsigned frozen_host = 0;
+    bool all_frozen = false;
+    while (it < max_iterations && !all_frozen) {
+        const int n = max_iterations - it < THALLO_HIP_COV_CHUNK ? max_iterations - it : THALLO_HIP_COV_CHUNK;
+        for (int i = 0; i < n; ++i, ++it) {
+            hipLaunchKernelGGL(k_cov_pupdate, dim3(pgrid), dim3(256), 0, s, pn, w.Z, w.P, w.sc, it == 0 ? 1 : 0);
+            hipLaunchKernelGGL(k_apply_s_cols, dim3(g), dim3(K), 0, s, C_, sys->nblk, sys->row_ptr, sys->col, sys->S, w.P, w.Y, w.pa);
+            hipLaunchKernelGGL(k_cov_scal<SCAL_ALPHA>, dim3(1), dim3(4 * K), 0, s, g, w.pa, w.sc, tol2, w.words);
+            hipLaunchKernelGGL(k_cov_step<true>, dim3(g), dim3(K), 0, s, C_, sys->Gc, w.X, w.P, w.R, w.Y, w.Z, w.sc, pb2);
+            if ((rc = thallo_hip_ba_coarse_apply_cols(coarse, cwork, w.R, w.Z, frozen, pb2 + (long)g * K, stream)) < 0) return done(rc);
+            hipLaunchKernelGGL(k_cov_scal<SCAL_BETA>, dim3(1), dim3(4 * K), 0, s, g + gc, pb2, w.sc, tol2, w.words);
+        }
+        if ((rc = check_launch()) < 0) return done(rc);
+        if (!pinned) {
+            if ((he = hipMemcpyAsync(&frozen_host, w.words, sizeof(unsigned), hipMemcpyDeviceToHost, s)) != hipSuccess || (he = hipStreamSynchronize(s)) != hipSuccess) return done(bad(he));
+            all_frozen = frozen_host == (unsigned)K;
+        } else {
+            const int slot = chunk & 1;
+            if ((he = hipMemcpyAsync(pinned + slot, w.words, sizeof(unsigned), hipMemcpyDeviceToHost, s)) != hipSuccess || (he = hipEventRecord(ev[slot], s)) != hipSuccess) return done(bad(he));
+            if (chunk > 0) {
+                if ((he = hipEventSynchronize(ev[slot ^ 1])) != hipSuccess) return done(bad(he));
+                all_frozen = pinned[slot ^ 1] == (unsigned)K;
+            }
+        }
+        ++chunk;
+    }
+    if ((rc = thallo_hip_ba_cov_out(sys, mode, ids, nreq, w.X, out, w.words + 1, stream)) < 0) return done(rc);
+    float sc[SC_ROWS * K]; unsigned words[2] = { 0, 0 };
+    if ((he = hipMemcpyAsync(sc, w.sc, sizeof(sc), hipMemcpyDeviceToHost, s)) != hipSuccess || (he = hipMemcpyAsync(words, w.words, sizeof(words), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (he = hipStreamSynchronize(s)) != hipSuccess) return done(bad(he));
+    info->iterations = it; info->columns = 0; info->not_converged = 0; info->nan_blocks = (int)words[1]; info->worst = 0.0f;
+    const unsigned* fz = reinterpret_cast<const unsigned*>(sc) + SC_FROZEN * K;
+    for (int k = 0; k < nreq * (mode == 0 ? 9 : 3); ++k) {
+        const float r0 = sc[SC_R0 * K + k], rz = sc[SC_AN * K + k];
+        if (!(r0 > 0.0f) && !std::isnan(r0)) continue;
+        info->columns++;
+        if (!fz[k]) info->not_converged++;
+        const float rel = std::sqrt(rz / r0);
+        if (!(rel <= info->worst)) info->worst = rel;
+    }
+    return done(0);
+}
+
 }  // extern "C"

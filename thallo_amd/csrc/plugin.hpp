@@ -246,6 +246,19 @@ public:
     virtual long schur_dense_n() const { return -1; }
     virtual int schur_dense_solve(LaunchCtx&, const unsigned char* /*hold*/, const float* /*g*/, float* /*delta_c*/) { return -1; }
     virtual const unsigned* schur_dense_words() const { return nullptr; }
+    // the two-level preconditioner's coarse correction on the assembled S (ThalloX_PlanSetPreconditioner kind 2; ba_coarse.hip).  coarse_want(on, k, agg), before
+    // schur_explicit(true): the aggregates -- agg: the caller's (C ids, dense, checked) or NULL: greedy aggregates of at most k cameras (k = 0: the default size) built from
+    // the structure -- the dense coarse matrix, Z, Z^T and the work panels are part of the structure: counted in its budget before anything is allocated, allocated
+    // behind it, freed with it or by the next schur_explicit that does not want them.  coarse_n: the coarse scalars (-1: the form does not run).  coarse_setup, every step
+    // behind schur_assemble: S_c, its scaling, the factor, Z.  coarse_apply: z += P Z^T Z P^T r, the partials of |Z P^T r|^2 into yy_out -> their number.  coarse_words:
+    // three device words: the last factor's info, the coarse scalars with the identity's row, the factors since Init that met a non-positive pivot.  A plugin that runs
+    // the form hands its operands to its covariance's column solve as well
+    virtual void coarse_want(bool /*on*/, int /*k*/, const int* /*agg*/) {}
+    virtual long coarse_n() const { return -1; }
+    virtual int coarse_aggregates() const { return -1; }
+    virtual int coarse_setup(LaunchCtx&, const unsigned char* /*hold*/) { return -1; }
+    virtual int coarse_apply(LaunchCtx&, const unsigned char* /*hold*/, const float* /*r*/, float* /*z*/, float* /*yy_out*/, const unsigned* /*gate*/) { return -1; }
+    virtual const unsigned* coarse_words() const { return nullptr; }
     // ---- held unknowns (opt-in: ThalloX_PlanSetHeldUnknowns; held.hip): plugins all of whose PCG routes form M^-1 from the stored SolverVectors::pre.  hold_to_internal,
     // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
     virtual bool hold_ok() const { return false; }

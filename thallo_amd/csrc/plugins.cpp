@@ -968,12 +968,72 @@ public:
     long sd_ld_ = 0;
     DeviceBuffer sd_T_, sd_d_, sd_words_;
     void schur_dense_want(bool on) override { sd_want_ = on; }
+    // the two-level preconditioner's coarse correction (ThalloX_PlanSetPreconditioner kind 2; ba_coarse.hip): the aggregates (built below, from the structure), the dense
+    // coarse matrix T (S_c, its scaling, its factor in place), d, Z, Z^T, y, the identity panels of the inverse and three words.  Part of the assembled structure like the dense form
+    bool cz_want_ = false, cz_on_ = false;
+    int cz_k_ = 0, cz_K_ = 0;
+    std::vector<int> cz_given_;
+    DeviceBuffer cz_agg_, cz_mem_ptr_, cz_mem_, cz_T_, cz_d_, cz_Z_, cz_Zt_, cz_y_, cz_panels_, cz_words_;
+    void coarse_want(bool on, int k, const int* agg) override { cz_want_ = on; cz_k_ = k; cz_given_.clear(); if (on && agg) cz_given_.assign(agg, agg + C); }
+    long coarse_n() const override { return cz_on_ ? 9L * cz_K_ : -1; }
+    int coarse_aggregates() const override { return cz_on_ ? cz_K_ : -1; }
+    const unsigned* coarse_words() const override { return cz_on_ ? (const unsigned*)cz_words_.ptr : nullptr; }
+    void coarse_release() { for (DeviceBuffer* b : { &cz_agg_, &cz_mem_ptr_, &cz_mem_, &cz_T_, &cz_d_, &cz_Z_, &cz_Zt_, &cz_y_, &cz_panels_, &cz_words_ }) b->release(); }
+    thallo_coarse_t coarse_operands(const unsigned char* hold) const
+    {
+        thallo_coarse_t c;
+        c.C = C; c.K = cz_K_; c.n = 9L * cz_K_; c.ld = thallo_hip_dense_ld(c.n); c.agg = (const int*)cz_agg_.ptr; c.mem_ptr = (const int*)cz_mem_ptr_.ptr; c.mem = (const int*)cz_mem_.ptr;
+        c.hold = hold; c.T = (float*)cz_T_.ptr; c.d = (float*)cz_d_.ptr; c.Z = (float*)cz_Z_.ptr; c.Zt = (float*)cz_Zt_.ptr; c.y = (float*)cz_y_.ptr; c.words = (unsigned*)cz_words_.ptr;
+        return c;
+    }
+    // Greedy aggregates of at most k cameras from the lower blocks of the structure (keys: row * C + column, column <= row; the weight of a pair = its block's term count =
+    // its co-visible points): cameras in ascending id, an unassigned one seeds an aggregate, which repeatedly takes the unassigned camera with the largest summed weight
+    // to its members (ties: the lower id) until it has k members or no connected camera is left.  Deterministic.  -> agg, the member lists in the order of joining
+    static void coarse_greedy(int C_, int k, const std::vector<long>& keys, const std::vector<int>& term_ptr, std::vector<int>& agg, std::vector<int>& mem_ptr, std::vector<int>& mem)
+    {
+        std::vector<size_t> at((size_t)C_ + 1, 0);
+        for (long key : keys) { const int i = (int)(key / C_), j = (int)(key % C_); if (i != j) { at[(size_t)i + 1]++; at[(size_t)j + 1]++; } }
+        for (int c = 0; c < C_; ++c) at[(size_t)c + 1] += at[(size_t)c];
+        std::vector<int> nbr(at[(size_t)C_]), wgt(at[(size_t)C_]);
+        std::vector<size_t> fill(at.begin(), at.end() - 1);
+        for (size_t l = 0; l < keys.size(); ++l) {
+            const int i = (int)(keys[l] / C_), j = (int)(keys[l] % C_), w = term_ptr[l + 1] - term_ptr[l];
+            if (i == j) continue;
+            nbr[fill[(size_t)i]] = j; wgt[fill[(size_t)i]++] = w; nbr[fill[(size_t)j]] = i; wgt[fill[(size_t)j]++] = w;
+        }
+        agg.assign((size_t)C_, -1); mem_ptr.clear(); mem.clear();
+        std::vector<long> score((size_t)C_, 0);
+        std::vector<int> cand;
+        int K_ = 0;
+        for (int seed = 0; seed < C_; ++seed) {
+            if (agg[(size_t)seed] >= 0) continue;
+            const int a = K_++;
+            mem_ptr.push_back((int)mem.size());
+            cand.clear();
+            int next = seed, size = 0;
+            while (next >= 0) {
+                agg[(size_t)next] = a; mem.push_back(next); ++size;
+                for (size_t t = at[(size_t)next]; t < at[(size_t)next + 1]; ++t) {
+                    const int u = nbr[t];
+                    if (agg[(size_t)u] >= 0) continue;
+                    if (score[(size_t)u] == 0) cand.push_back(u);
+                    score[(size_t)u] += wgt[t] > 0 ? wgt[t] : 1;
+                }
+                next = -1;
+                if (size >= k) break;
+                for (int u : cand) if (agg[(size_t)u] < 0 && (next < 0 || score[(size_t)u] > score[(size_t)next] || (score[(size_t)u] == score[(size_t)next] && u < next))) next = u;
+            }
+            for (int u : cand) score[(size_t)u] = 0;
+        }
+        mem_ptr.push_back((int)mem.size());
+    }
     long schur_dense_n() const override { return sd_on_ ? 9L * C : -1; }
     const unsigned* schur_dense_words() const override { return sd_on_ ? (const unsigned*)sd_words_.ptr : nullptr; }
     long schur_explicit(bool on) override
     {
-        sx_on_ = false; sd_on_ = false;
+        sx_on_ = false; sd_on_ = false; cz_on_ = false;
         if (!on || !sd_want_) for (DeviceBuffer* b : { &sd_T_, &sd_d_, &sd_words_ }) b->release();
+        if (!on || !cz_want_) coarse_release();
         if (!on) { for (DeviceBuffer* b : { &sx_row_ptr_, &sx_col_, &sx_lower_, &sx_term_ptr_, &sx_terms_, &sx_W_, &sx_S_ }) b->release(); return 0; }
         if (C < 1) { set_error("bundle_adjustment: the assembled Schur-complement solve needs at least one camera"); return -1; }
         std::vector<int> pp((size_t)P + 1), ppos((size_t)O), qc((size_t)O), qp((size_t)O), cp((size_t)C + 1);
@@ -1046,7 +1106,41 @@ public:
         tq.resize(2 * (size_t)nterms);
         const unsigned long long nlower = keys.size(), nblk = 2 * nlower - (unsigned long long)C;
         if (nblk > 0x7fffffffULL / 3) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu blocks, more than its int32 indices hold", nblk); return -1; }
-        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5) + dense_bytes;
+        // the coarse correction: its aggregates come from the blocks just listed; its bytes -- T, Z, Z^T, the identity panels, d, y, the lists, the words -- join the count
+        std::vector<int> cz_agg, cz_mem_ptr, cz_mem;
+        unsigned long long coarse_bytes = 0;
+        long cz_n = 0, cz_ld = 0;
+        if (cz_want_) {
+            if (!cz_given_.empty()) {
+                cz_agg = cz_given_;
+                int K_ = 0;
+                for (int a : cz_agg) if (a + 1 > K_) K_ = a + 1;
+                cz_mem_ptr.assign((size_t)K_ + 1, 0);
+                for (int a : cz_agg) cz_mem_ptr[(size_t)a + 1]++;
+                for (int a = 0; a < K_; ++a) cz_mem_ptr[(size_t)a + 1] += cz_mem_ptr[(size_t)a];
+                cz_mem.resize((size_t)C);
+                std::vector<int> fillm(cz_mem_ptr.begin(), cz_mem_ptr.end() - 1);
+                for (int c = 0; c < C; ++c) cz_mem[(size_t)fillm[(size_t)cz_agg[(size_t)c]]++] = c;      // (members in ascending id)
+            } else {
+                const int k = cz_k_ > 0 ? cz_k_ : std::max(8, (C + 127) / 128);
+                coarse_greedy(C, k, keys, term_ptr, cz_agg, cz_mem_ptr, cz_mem);
+            }
+            cz_K_ = (int)cz_mem_ptr.size() - 1;
+            cz_n = 9L * cz_K_; cz_ld = thallo_hip_dense_ld(cz_n);
+            if (cz_n > THALLO_HIP_COARSE_MAX_N) {
+                set_error("bundle_adjustment: the two-level preconditioner's coarse space has n_c = %ld scalars (%d aggregates), more than its kernels take (%d): use larger aggregates "
+                          "(ThalloX_PlanSetCoarseAggregates)", cz_n, cz_K_, THALLO_HIP_COARSE_MAX_N);
+                return -1;
+            }
+            coarse_bytes = 3ULL * 4 * (unsigned long long)cz_ld * (unsigned long long)cz_n + 4ULL * (unsigned long long)thallo_hip_ba_coarse_panel_floats(cz_n) + 2ULL * 4 * (unsigned long long)cz_n +
+                           4ULL * (2ULL * (unsigned long long)C + (unsigned long long)cz_K_ + 1) + 6 * 64;
+        }
+        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5) + dense_bytes + coarse_bytes;
+        if (bytes > allowed && cz_want_) {
+            set_error("bundle_adjustment: the assembled reduced camera matrix and the two-level preconditioner's coarse matrices want %llu bytes of device memory (%llu blocks of 9 x 9, %llu terms, "
+                      "%d observations; %llu bytes coarse, %d aggregates, n_c = %ld), the budget allows %llu (%s)", bytes, nblk, nterms, O, coarse_bytes, cz_K_, cz_n, allowed, why);
+            return -1;
+        }
         if (bytes > allowed) return over(bytes, nblk, "");
         std::vector<int> row_ptr((size_t)C + 1, 0);
         for (long key : keys) { const int i = (int)(key / C), j = (int)(key % C); row_ptr[i + 1]++; if (i != j) row_ptr[j + 1]++; }
@@ -1077,7 +1171,18 @@ public:
             set_error("bundle_adjustment: out of device memory for the dense reduced camera matrix (%llu bytes): %s", dense_bytes, whyn.c_str());
             return -1;
         }
-        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true; sd_on_ = sd_want_; sd_ld_ = sd_ld;
+        if (cz_want_) {
+            const size_t tz = 4 * (size_t)cz_ld * (size_t)cz_n + 64;
+            if (up(cz_agg_, cz_agg) || up(cz_mem_ptr_, cz_mem_ptr) || up(cz_mem_, cz_mem) || cz_T_.alloc(tz) || cz_Z_.alloc(tz) || cz_Zt_.alloc(tz) || cz_d_.alloc(4 * (size_t)cz_n + 64) ||
+                cz_y_.alloc(4 * (size_t)cz_n + 64) || cz_panels_.alloc(4 * (size_t)thallo_hip_ba_coarse_panel_floats(cz_n) + 64) || cz_words_.alloc(64) ||
+                hipMemset(cz_words_.ptr, 0, 64) != hipSuccess) {
+                const std::string whyn = last_error();
+                coarse_release();
+                set_error("bundle_adjustment: out of device memory for the two-level preconditioner's coarse matrices (%llu bytes): %s", coarse_bytes, whyn.c_str());
+                return -1;
+            }
+        }
+        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true; sd_on_ = sd_want_; sd_ld_ = sd_ld; cz_on_ = cz_want_;
         return sx_nblk_;
     }
     // expand + factor of the step's (or the covariance call's) assembled S; hold: the plan's mask over the flat vector (its first 9 C bytes are the cameras') or NULL
@@ -1098,6 +1203,25 @@ public:
         if (rc < 0) return rc;
         TimedLaunch t(c, "SchurDenseSolve");
         return thallo_hip_dense_potrs_vec(9L * C, sd_ld_, (const float*)sd_T_.ptr, (const float*)sd_d_.ptr, g, delta_c, THALLO_HIP_DENSE_BOTH, c.stream);
+    }
+    int coarse_setup(LaunchCtx& c, const unsigned char* hold) override
+    {
+        if (!cz_on_) return -1;
+        const thallo_coarse_t cz = coarse_operands(hold);
+        int rc;
+        {   TimedLaunch t(c, "CoarseAssemble");
+            if ((rc = thallo_hip_ba_coarse_assemble(&cz, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, c.stream)) < 0) return rc; }
+        { TimedLaunch t(c, "CoarseScale"); if ((rc = thallo_hip_ba_coarse_scale(&cz, c.stream)) < 0) return rc; }
+        { TimedLaunch t(c, "CoarseFactor"); if ((rc = thallo_hip_dense_potrf(cz.n, cz.ld, cz.T, (int*)cz.words, c.stream)) < 0) return rc; }
+        TimedLaunch t(c, "CoarseInverse");
+        return thallo_hip_ba_coarse_inverse(&cz, (float*)cz_panels_.ptr, c.stream);
+    }
+    int coarse_apply(LaunchCtx& c, const unsigned char* hold, const float* r, float* z, float* yy_out, const unsigned* gate) override
+    {
+        if (!cz_on_) return -1;
+        const thallo_coarse_t cz = coarse_operands(hold);
+        TimedLaunch t(c, "CoarseApply");
+        return thallo_hip_ba_coarse_apply(&cz, r, z, yy_out, gate, c.stream);
     }
     int schur_assemble(LaunchCtx& c, const float* H, const float* Ge, const float* ctc) override
     {
@@ -1166,10 +1290,12 @@ public:
     {
         if (!sx_on_) { set_error("bundle_adjustment: a covariance needs the assembled reduced camera matrix"); return -1; }
         const int per = input == 0 ? THALLO_HIP_COV_K / 9 : THALLO_HIP_COV_K / 3, fl = input == 0 ? 81 : 9;
-        if (!cov_work_.ptr && (cov_work_.alloc((size_t)thallo_hip_ba_cov_work_bytes(C)) || cov_ids_.alloc(sizeof(int) * THALLO_HIP_COV_K) ||
+        const long cov_bytes = thallo_hip_ba_cov_coarse_work_bytes(C, cz_on_ ? 9L * cz_K_ : 0);
+        if (cov_work_.ptr && cov_work_.bytes < (size_t)cov_bytes) cov_work_.release();      // (a re-Init switched the two-level form on, or to more aggregates)
+        if (!cov_work_.ptr && (cov_work_.alloc((size_t)cov_bytes) || cov_ids_.alloc(sizeof(int) * THALLO_HIP_COV_K) ||
                                cov_out_.alloc(sizeof(float) * 81 * (THALLO_HIP_COV_K / 9) + 64))) {
             for (DeviceBuffer* b : { &cov_work_, &cov_ids_, &cov_out_ }) b->release();
-            set_error("bundle_adjustment: out of device memory for the covariance's work vectors (%ld bytes)", thallo_hip_ba_cov_work_bytes(C)); return -1;
+            set_error("bundle_adjustment: out of device memory for the covariance's work vectors (%ld bytes)", cov_bytes); return -1;
         }
         if (!cov_pinned_ && hipHostMalloc((void**)&cov_pinned_, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { cov_pinned_ = nullptr; (void)hipGetLastError(); }      // (without them: a blocking read per chunk)
         std::vector<int> in(ids, ids + n);
@@ -1182,11 +1308,14 @@ public:
         sys.C = C; sys.P = P; sys.nblk = sx_nblk_; sys.row_ptr = (const int*)sx_row_ptr_.ptr; sys.col = (const int*)sx_col_.ptr; sys.S = (const float*)sx_S_.ptr;
         sys.Gc = Gc; sys.Ge = Ge; sys.W = (const float*)sx_W_.ptr; sys.pt_ptr = (const int*)pt_ptr.ptr; sys.pt_pos = (const int*)pt_pos.ptr; sys.q_cam = (const int*)q_cam.ptr; sys.hold = hold;
         *info = thallo_cov_info_t{ 0, 0, 0, 0, 0.0f };
+        thallo_coarse_t cz{};
+        if (cz_on_) cz = coarse_operands(hold);      // (the two-level preconditioner of the plan's last Init: its Z is this call's set-up's)
         for (long b0 = 0; b0 < n; b0 += per) {
             const int nreq = (int)(n - b0 < per ? n - b0 : per);
             thallo_cov_info_t bi;
             if (hipMemcpyAsync(cov_ids_.ptr, in.data() + b0, sizeof(int) * (size_t)nreq, hipMemcpyHostToDevice, c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot upload the covariance's ids"); return -1; }
-            const int rc = thallo_hip_ba_cov_solve(&sys, input, (const int*)cov_ids_.ptr, nreq, rel_tol, max_iterations, cov_work_.ptr, cov_pinned_, (float*)cov_out_.ptr, &bi, c.stream);
+            const int rc = thallo_hip_ba_cov_solve_coarse(&sys, cz_on_ ? &cz : nullptr, input, (const int*)cov_ids_.ptr, nreq, rel_tol, max_iterations, cov_work_.ptr, cov_pinned_,
+                                                          (float*)cov_out_.ptr, &bi, c.stream);
             if (rc < 0) { set_error("bundle_adjustment: the covariance's column solve failed (%d)", rc); return -1; }
             if (hipMemcpyAsync(host_out + (size_t)fl * (size_t)b0, cov_out_.ptr, sizeof(float) * (size_t)fl * (size_t)nreq, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
                 hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance blocks"); return -1; }

@@ -151,6 +151,11 @@ public:
     bool lm() const { return lm_; }
     // ThalloX_PlanSetPreconditioner: THALLOX_PRECOND_JACOBI (the reference's, default) or THALLOX_PRECOND_BLOCK_JACOBI; takes effect at the next Init.  0 = ok
     int  set_preconditioner(int kind);
+    // ThalloX_PlanSetCoarseAggregates: the two-level preconditioner's aggregates -- (0, NULL, 0) the default size, (k, NULL, 0) greedy aggregates of at most k cameras, or
+    // the caller's array of n = C dense ids; takes effect at the next Init.  0 = ok
+    int  set_coarse_aggregates(int cameras_per_aggregate, const int* aggregate_of_camera, long n);
+    // ThalloX_PlanCoarseSpace: { aggregates, coarse scalars, coarse scalars of the last set-up with the identity's row, coarse factors since Init that met a non-positive pivot } -> 0, or -1 (the form does not run)
+    int  coarse_space(long out[4]);
     int  preconditioner_fallbacks();      // blocks of the last step's factorisation that fell back to the diagonal (-1: the block form does not run)
     const char* schedule_name();          // the plugin's, and the opt-in forms that run (before the first Init: that were asked for)
     // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG or THALLOX_SOLVER_SCHUR_DENSE; takes effect at the next Init.  0 = ok
@@ -336,6 +341,14 @@ private:
     float *block_H_ = nullptr, *block_G_ = nullptr;
     unsigned* block_status_ = nullptr;
     int   block_prepare();                              // Init: the regions and the buffers
+    // ---- the two-level preconditioner on the assembled S (ba_coarse.hip): M^-1 = G^T G + P Z^T Z P^T.  Asked for by kind 2 of set_preconditioner (block_want_ goes with
+    // it), runs on kind 2 of the linear solver alone; the aggregates and every coarse buffer are the plugin's, built and allocated with the structure of S
+    bool coarse_want_ = false, coarse_on_ = false;
+    int  coarse_k_ = 0;                                 // cameras per aggregate asked for (0: the default)
+    std::vector<int> coarse_agg_;                       // ... or the caller's aggregates (empty: greedy)
+    // z += the coarse term of M^-1 r behind the launch that left z = G^T G r and nb partials of r . z in `part`: the partials of |Z P^T r|^2 go behind them, so every reader
+    // of the slot adds r . z_B + |y|^2 in one fixed order -> the slot's partial count (nb itself where the form does not run), or a negative code
+    int   coarse_apply(float* part, int nb, const unsigned* gate);
     // ---- Schur complement on the cameras (ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
     // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are its own
     bool schur_want_ = false, schur_on_ = false;

@@ -34,6 +34,13 @@ int Plan::forms_prepare()
     block_on_ = false;
     schur_on_ = false;
     schur_dense_ = false;
+    coarse_on_ = false;
+    if (coarse_want_ && !(schur_want_ && schur_explicit_want_)) {
+        set_error("%s: the two-level preconditioner (ThalloX_PlanSetPreconditioner THALLOX_PRECOND_TWO_LEVEL) needs the assembled reduced camera matrix: set "
+                  "ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG); this plan's linear solver is %s", plugin->name(),
+                  schur_want_ ? "THALLOX_SOLVER_SCHUR_PCG" : "THALLOX_SOLVER_PCG");
+        return -1;
+    }
     if (schur_want_) { if (schur_prepare()) return -1; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
     else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes, the dense matrix with it)
     if (!schur_want_ && block_want_) { if (block_prepare()) return -1; block_on_ = true; }
@@ -64,9 +71,18 @@ int Plan::forms_setup(const float* shift, const float* b, float* rz_out, int nb,
     if (schur_on_) {
         if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
         if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;
+        if (coarse_on_ && !schur_empty() && (rc = plugin->coarse_setup(ctx, held_on() ? held_mask_ : nullptr)) < 0) { what = "two-level preconditioner set-up"; return rc; }
     }
-    TimedLaunch t(ctx, "BlockApply");
-    return thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, s);
+    { TimedLaunch t(ctx, "BlockApply"); rc = thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, s); }
+    return coarse_apply(rz_out, rc, nullptr);
+}
+
+int Plan::coarse_apply(float* part, int nb, const unsigned* gate)
+{
+    if (!coarse_on_ || schur_empty() || nb < 0) return nb;
+    if (nb + THALLO_HIP_COARSE_PARTIALS > THALLO_HIP_MAX_PARTIALS) return -(int)hipErrorInvalidValue;
+    const int nc = plugin->coarse_apply(ctx, held_on() ? held_mask_ : nullptr, v_.r, v_.z, part + nb, gate);
+    return nc < 0 ? nc : nb + nc;
 }
 
 // One GN step of the block-Jacobi and of the Schur form: the generic GN loop (step_gn's last branch) with M^-1 = G^T G -- forms_setup behind PCGInit1 replaces its
@@ -98,6 +114,7 @@ int Plan::step_gn_blocks(int ev_iter)
         {   TimedLaunch t(ctx, "BlockStep2");
             nb = thallo_hip_block_step2(precond_regions_, block_G_, v_.r, v_.Ap, v_.z, sum(jN), sum(jD), slot(jB), s); }
         if (nb < 0) { set_error("PCGStep2 (block) launch failed (%d)", nb); return 0; }
+        if ((nb = coarse_apply(slot(jB), nb, nullptr)) < 0) { set_error("PCGStep2 (coarse apply) launch failed (%d)", nb); return 0; }
         set_nb(jB, nb); finish(jB);
     }
     if (schur_on_) {
@@ -154,11 +171,15 @@ void Plan::lm_loop_blocks(LmStep& st)
             if (st.failed) return;
             nbq = nb;
             { TimedLaunch t(ctx, "BlockApply"); nb = thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, slot(jB), ctx.gate, s); st.check(nb, "PCGStep2 (block apply) launch"); }
+            if (st.failed) return;
+            nb = coarse_apply(slot(jB), nb, ctx.gate); st.check(nb, "PCGStep2 (coarse apply) launch");
         } else {
-            TimedLaunch t(ctx, "BlockStep2LM");
-            nb = thallo_hip_block_step2_lm(precond_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, b, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s);
+            {   TimedLaunch t(ctx, "BlockStep2LM");
+                nb = thallo_hip_block_step2_lm(precond_regions_, block_G_, v_.delta, p, v_.r, v_.Ap, v_.z, b, sum(jN), sum(jD), slot(jB), slot(QS), ctx.gate, s); }
             st.check(nb, "PCGStep2 launch");
             nbq = nb;
+            if (st.failed) return;
+            nb = coarse_apply(slot(jB), nb, ctx.gate); st.check(nb, "PCGStep2 (coarse apply) launch");
         }
         if (st.failed) return;
         set_nb(jB, nb); set_nb(QS, nbq);
@@ -184,6 +205,9 @@ const char* Plan::schedule_name()
         if (schur_on_ ? schur_dense_ : schur_dense_want_) {
             t += "; dense Cholesky of S";
             if (schur_on_ && plugin->schur_dense_n() >= 0) t += " (n = " + std::to_string(plugin->schur_dense_n()) + ")";
+        } else if (schur_on_ ? coarse_on_ : coarse_want_ && schur_explicit_want_) {
+            t += "; two-level on S";
+            if (schur_on_) t += " (" + std::to_string(plugin->coarse_aggregates()) + " aggregates, n_c = " + std::to_string(plugin->coarse_n()) + ")";
         } else t += "; block-Jacobi on S";
     } else if (block_on_ || block_want_) t += "; block-Jacobi preconditioner (unfused PCG loop)";
     const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
@@ -260,13 +284,48 @@ int Plan::hold_pcg(float* rz_out)
 // ------------------------------------------------------------------ block-Jacobi preconditioner (block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
 int Plan::set_preconditioner(int kind)
 {
-    if (kind != THALLOX_PRECOND_JACOBI && kind != THALLOX_PRECOND_BLOCK_JACOBI) { set_error("%s: unknown preconditioner kind %d", plugin->name(), kind); return -1; }
-    if (kind == THALLOX_PRECOND_JACOBI) { block_want_ = false; return 0; }
+    if (kind != THALLOX_PRECOND_JACOBI && kind != THALLOX_PRECOND_BLOCK_JACOBI && kind != THALLOX_PRECOND_TWO_LEVEL) { set_error("%s: unknown preconditioner kind %d", plugin->name(), kind); return -1; }
+    if (kind == THALLOX_PRECOND_JACOBI) { block_want_ = false; coarse_want_ = false; return 0; }
     if (!ok_) return -1;
     if (!plugin->block_precond_ok()) { set_error("%s: no block-Jacobi preconditioner for this energy (its plugin states no blocks; bundle_adjustment does)", plugin->name()); return -1; }
     if (dist_) { set_error("%s: the block-Jacobi preconditioner runs on one GPU (this plan is distributed)", plugin->name()); return -1; }
     if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to precondition", plugin->name()); return -1; }
     block_want_ = true;
+    coarse_want_ = kind == THALLOX_PRECOND_TWO_LEVEL;
+    return 0;
+}
+
+// ------------------------------------------------------------------ two-level preconditioner on the assembled S (ba_coarse.hip, DESIGN.md "Two-level preconditioner")
+int Plan::set_coarse_aggregates(int k, const int* agg, long n)
+{
+    if (!ok_) return -1;
+    const long C_ = plugin->cov_elements(0);
+    if (!plugin->schur_ok() || C_ < 0) { set_error("%s: no two-level preconditioner for this energy (its plugin assembles no reduced matrix; bundle_adjustment does)", plugin->name()); return -1; }
+    if (!agg) {
+        if (k < 0 || n != 0) { set_error("%s: coarse aggregates: cameras_per_aggregate must be >= 0 (0: the default) and n = 0 without an array (got %d, n = %ld)", plugin->name(), k, n); return -1; }
+        coarse_k_ = k; coarse_agg_.clear();
+        return 0;
+    }
+    if (n != C_) { set_error("%s: coarse aggregates: the array has %ld ids, the plan has %ld cameras", plugin->name(), n, C_); return -1; }
+    int K_ = 0;
+    for (long c = 0; c < n; ++c) {
+        if (agg[c] < 0 || agg[c] >= n) { set_error("%s: coarse aggregates: id %d of camera %ld is out of range [0, %ld)", plugin->name(), agg[c], c, n); return -1; }
+        if (agg[c] + 1 > K_) K_ = agg[c] + 1;
+    }
+    std::vector<char> used((size_t)K_, 0);
+    for (long c = 0; c < n; ++c) used[(size_t)agg[c]] = 1;
+    for (int a = 0; a < K_; ++a) if (!used[(size_t)a]) { set_error("%s: coarse aggregates: the ids must be dense: aggregate %d of 0 .. %d has no camera", plugin->name(), a, K_ - 1); return -1; }
+    if (9L * K_ > THALLO_HIP_COARSE_MAX_N) { set_error("%s: coarse aggregates: %d aggregates give n_c = %ld coarse scalars, more than the kernels take (%d)", plugin->name(), K_, 9L * K_, THALLO_HIP_COARSE_MAX_N); return -1; }
+    coarse_k_ = 0; coarse_agg_.assign(agg, agg + n);
+    return 0;
+}
+
+int Plan::coarse_space(long out[4])
+{
+    if (!ok_ || !ready_ || !coarse_on_ || !out) return -1;
+    unsigned w[3] = { 0, 0, 0 };
+    if (hipMemcpyAsync(w, plugin->coarse_words(), sizeof(w), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
+    out[0] = plugin->coarse_aggregates(); out[1] = plugin->coarse_n(); out[2] = (long)w[1]; out[3] = (long)w[2];
     return 0;
 }
 
@@ -318,9 +377,13 @@ int Plan::schur_prepare()
     // the assembled form: the structure of S, sized and checked against its budget before it is allocated
     schur_explicit_ = false;
     plugin->schur_dense_want(schur_dense_want_);      // (the dense matrix is sized, refused, allocated and freed with the structure)
+    const bool coarse = coarse_want_ && schur_explicit_want_ && !schur_dense_want_;      // (the dense form ignores the preconditioner)
+    plugin->coarse_want(coarse, coarse_k_, coarse && !coarse_agg_.empty() ? coarse_agg_.data() : nullptr);      // (... and the coarse matrices likewise)
     schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
     if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
     schur_explicit_ = schur_explicit_want_;
+    coarse_on_ = coarse && plugin->coarse_n() >= 0;
+    if (coarse && !coarse_on_) { set_error("%s: the two-level preconditioner is not available for this energy", plugin->name()); return -1; }
     schur_dense_ = schur_dense_want_ && plugin->schur_dense_n() >= 0;
     if (schur_dense_want_ && !schur_dense_) { set_error("%s: the dense Cholesky Schur-complement solve is not available for this energy", plugin->name()); return -1; }
     if (schur_Ge_) return 0;
