@@ -216,6 +216,26 @@ int ThalloX_PlanSetHeldUnknowns(Thallo_Plan* plan, int input, const unsigned cha
  * its meaning: the points the elimination's factor rule held. */
 long ThalloX_PlanHeldUnknowns(Thallo_Plan* plan);
 
+/* Gaussian priors on single unknowns, the soft form of ThalloX_PlanSetHeldUnknowns: calibrated intrinsics with a tolerance, GPS / IMU pose priors, surveyed control
+ * points, a soft gauge.  `input` is the Inputs{} index of an Unknown (bundle_adjustment: 0 cameras, 1 points); mean and weight are HOST arrays of n = elements x components
+ * floats in the caller's ids; weight is the precision 1 / sigma^2 in residual^2 per unknown^2, 0 = no prior on that scalar; weight == NULL clears that input's prior.
+ * The solve is that of the energy with one more residual sqrt(w) (x - mean) per scalar with w > 0: the cost gains 1/2 w (x - mean)^2 (Thallo_ProblemCurrentCost, accept /
+ * revert and the trust region see the full cost; ThalloX_PlanPriorCost returns the prior's share), the right-hand side -W (x - mean), the system matrix W -- in PCG's
+ * preconditioner, the block and elimination factors, the assembled S, LM's diagonal and model cost, and ThalloX_PlanCovariance, whose Sigma becomes (A_FF)^-1 with W
+ * inside A: a prior on one camera's pose and one more scalar is a gauge under which every camera has a finite block.  A robust loss is never applied to a prior; a held
+ * scalar with a prior keeps delta = 0 and its constant term still counts in the cost.  Works with every preconditioner, linear solver, loss and mask above; no launch is
+ * added to a PCG iteration.  A plan that never makes the call, clears its priors or sets no positive weight launches what it launches otherwise, bit for bit.  Between
+ * Thallo_ProblemPlan and Thallo_ProblemInit, or before a re-Init: it takes effect at the next Init.
+ * Returns 0, or nonzero with ThalloX_LastError naming the energy and the reason: every energy but bundle_adjustment (generated ones included), a doublePrecision = 1 state,
+ * a distributed plan (ThalloX_PlanSetDistributed after this call is refused likewise), a direct-solve plan, an input that is not an Unknown, an n that is not
+ * elements x components, a weight that is negative or not finite, a mean that is not finite where its weight is positive. */
+int ThalloX_PlanSetPrior(Thallo_Plan* plan, int input, const float* mean, const float* weight, long n);
+/* Scalars with a positive weight since the last Thallo_ProblemInit (ThalloX_PlanScheduleName then ends in "; N priors"); -1 when there was no Init. */
+long ThalloX_PlanPriorTerms(Thallo_Plan* plan);
+/* The prior's share of the cost at the current unknowns, sum 1/2 w (x - mean)^2, into *out (0 where no prior is in force): Thallo_ProblemCurrentCost minus it is the
+ * reprojection cost.  Synchronises the plan's stream.  Returns 0, or nonzero on failure. */
+int ThalloX_PlanPriorCost(Thallo_Plan* plan, double* out);
+
 /* A robust loss for observations that are mismatches: one loss over the whole residual vector of an observation (bundle_adjustment: its 2 reprojection components).  With
  * s = |r|^2 of an observation and scale a > 0 in residual units (pixels) the cost becomes sum_o 1/2 rho(s_o):
  *   THALLOX_LOSS_TRIVIAL  rho = s                                        (the default: the squared loss)

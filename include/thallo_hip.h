@@ -806,6 +806,24 @@ int thallo_hip_block_hold(thallo_block_regions_t regions, const unsigned char* m
  * has G = 0 (thallo_hip_ba_schur_factor's held-point rule). */
 int thallo_hip_block_hold_factor(thallo_block_regions_t regions, const unsigned char* mask, float* G, thallo_stream_t stream);
 
+/* ---------------------------------------------------------------- Gaussian priors on single unknowns (prior.hip; opt-in, DESIGN.md "Gaussian priors")
+ * w, mu: one float per scalar of the flat vector, w = 0: no prior on that scalar (mu is not read there).  The energy gains the residual sqrt(w) (x - mu): the cost
+ * 1/2 w (x - mu)^2, b = -J^T F - W (x - mu), A = J^T J + W.  W reaches every product with A through the flat diagonal that the applies, thallo_hip_block_factor,
+ * thallo_hip_ba_schur_factor / _apply / _assemble already take (the LM CtC's argument); these launches form the rest.  The unknowns live in two arrays: x0 holds the
+ * first n0 scalars of the flat vector, x1 the other n - n0 (n0 == n: x1 is not read).  One partial per workgroup in a fixed order, no float atomics. */
+#define THALLO_HIP_PRIOR_COST_PARTIALS 64
+/* The partials of 1/2 sum w (x - mu)^2, at most THALLO_HIP_PRIOR_COST_PARTIALS of them.  onto = 0: stored into out (returns their number).  onto = k > 0: out holds the k
+ * partials a cost kernel left earlier on the stream; this launch's at most min(k, THALLO_HIP_PRIOR_COST_PARTIALS) partials are added onto the first of them, one writer per
+ * word (returns k): the slot keeps its count -- a cost kernel may fill all THALLO_HIP_MAX_PARTIALS -- and its one reader adds everything in a fixed order. */
+int thallo_hip_prior_cost(const float* w, const float* mu, const float* x0, const float* x1, long n0, long n, float* out, int onto, thallo_stream_t stream);
+/* Behind PCGInit1 (r = -J^T F, diag = diag(J^T J), pre, z), in front of thallo_hip_lm_finalize_diagonal and thallo_hip_hold_pcg: where w > 0, r -= w (x - mu),
+ * diag += w, pre = 1 / (1 + sqrt(diag))^2 (thallo_hip_pcg_init_finish's guarded inverse; 1 without preconditioner), z = pre r; the partials of r . z over all n
+ * scalars anew (returns their number). */
+int thallo_hip_prior_init(const float* w, const float* mu, const float* x0, const float* x1, long n0, long n, float* r, float* diag, float* pre, float* z, int use_preconditioner,
+                          float* rz_out, thallo_stream_t stream);
+/* LM, behind thallo_hip_lm_finalize_diagonal: shift = float32(CtC + w), the plane handed to every ctc / shift argument of the step. */
+int thallo_hip_prior_lm_shift(const float* w, const float* ctc, long n, float* shift, thallo_stream_t stream);
+
 /* ---------------------------------------------------------------- Schur complement on the cameras (ba_schur.hip; opt-in, DESIGN.md "Schur complement on the cameras")
  * Bundle adjustment with the points eliminated exactly through their 3 x 3 blocks: with A = J^T J (+ diag(CtC) in LM) = [[B, E], [E^T, Cp]] and b = [b_c; b_p],
  * S = B - E Cp^-1 E^T, g = b_c - E Cp^-1 b_p, PCG on S delta_c = g, delta_p = Cp^-1 (b_p - E^T delta_c).  Index lists, Jb and JP as thallo_hip_ba_block_diag takes them (the

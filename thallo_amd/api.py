@@ -137,6 +137,10 @@ def lib():
         L.ThalloX_PlanCoarseSpace.argtypes = [vp, vp]; L.ThalloX_PlanCoarseSpace.restype = C.c_int
     L.ThalloX_PlanSetHeldUnknowns.argtypes = [vp, C.c_int, vp, C.c_long]; L.ThalloX_PlanSetHeldUnknowns.restype = C.c_int
     L.ThalloX_PlanHeldUnknowns.argtypes = [vp]; L.ThalloX_PlanHeldUnknowns.restype = C.c_long
+    if hasattr(L, "ThalloX_PlanSetPrior"):           # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_prior_bench.py --ab)
+        L.ThalloX_PlanSetPrior.argtypes = [vp, C.c_int, vp, vp, C.c_long]; L.ThalloX_PlanSetPrior.restype = C.c_int
+        L.ThalloX_PlanPriorTerms.argtypes = [vp]; L.ThalloX_PlanPriorTerms.restype = C.c_long
+        L.ThalloX_PlanPriorCost.argtypes = [vp, C.POINTER(C.c_double)]; L.ThalloX_PlanPriorCost.restype = C.c_int
     if hasattr(L, "ThalloX_PlanSetRobustLoss"):      # (THALLO_LIB may name an A/B build from before the call existed: tools/ba_robust_bench.py --ab)
         L.ThalloX_PlanSetRobustLoss.argtypes = [vp, C.c_int, C.c_float]; L.ThalloX_PlanSetRobustLoss.restype = C.c_int
         L.ThalloX_PlanRobustWeights.argtypes = [vp, vp, C.c_long]; L.ThalloX_PlanRobustWeights.restype = C.c_long
@@ -490,6 +494,33 @@ class ThalloSolver:
     def held_unknowns(self):
         """Scalars held since the last init() (-1: no mask in force)."""
         return self._L.ThalloX_PlanHeldUnknowns(self.plan)
+
+    def set_prior(self, input, mean, weight):
+        """Gaussian priors 1/2 w (x - mean)^2 on single scalars (include/Thallo.h ThalloX_PlanSetPrior): `input` is the Inputs{} index of an Unknown (bundle_adjustment:
+        0 cameras, 1 points), `mean` and `weight` arrays of elements x components floats in the caller's ids (weight = 1 / sigma^2, 0 = no prior on that scalar), or
+        weight None to clear that input's prior; before init().  Raises, with the library's reason, where the plan cannot take priors."""
+        if weight is None:
+            rc = self._L.ThalloX_PlanSetPrior(self.plan, int(input), None, None, 0)
+        else:
+            import numpy as np
+            w = np.ascontiguousarray(weight, dtype=np.float32).reshape(-1)
+            m = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+            if m.size != w.size:
+                raise ValueError("set_prior: mean has %d scalars, weight %d" % (m.size, w.size))
+            rc = self._L.ThalloX_PlanSetPrior(self.plan, int(input), m.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), int(w.size))
+        if rc != 0:
+            raise RuntimeError("ThalloX_PlanSetPrior failed: " + last_error())
+
+    def prior_terms(self):
+        """Scalars with a positive prior weight since the last init() (-1: there was none)."""
+        return self._L.ThalloX_PlanPriorTerms(self.plan)
+
+    def prior_cost(self):
+        """The prior's share of the current cost, sum 1/2 w (x - mean)^2 (0.0 where no prior is in force)."""
+        out = C.c_double(0.0)
+        if self._L.ThalloX_PlanPriorCost(self.plan, C.byref(out)) != 0:
+            raise RuntimeError("ThalloX_PlanPriorCost failed: " + last_error())
+        return out.value
 
     ROBUST_LOSSES = {"trivial": 0, "huber": 1, "cauchy": 2}
 

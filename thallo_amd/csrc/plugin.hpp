@@ -263,6 +263,9 @@ public:
     // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
     virtual bool hold_ok() const { return false; }
     virtual void hold_to_internal(int /*k*/, const unsigned char* /*caller*/, unsigned char* /*flat*/) const {}
+    // ---- Gaussian priors (opt-in: ThalloX_PlanSetPrior; prior.hip): for the plugins that hold unknowns (hold_ok) whose applies add LaunchCtx::lm_ctc (apply_adds_ctc).
+    // prior_to_internal: one float plane of unknown image k (a mean or a weight, the caller's ids) into the plane over the flat vector, as hold_to_internal maps a mask
+    virtual void prior_to_internal(int /*k*/, const float* /*caller*/, float* /*flat*/) const {}
     // ---- robust losses (opt-in: ThalloX_PlanSetRobustLoss; DESIGN.md "Robust losses"): plugins whose cost, precomputeJ and block-rebuilding apply routes have a robust
     // instantiation.  robust_prepare, at Init behind prepare(): the loss of this solve (kind 0: none -- the routes launch what they launch without the call) and the
     // buffer of weights -> 0, or -1 with the reason set.  robust_weights: rho'(s) per observation of the last linearisation into host_out[n], the caller's ids -> the

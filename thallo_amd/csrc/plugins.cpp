@@ -1254,6 +1254,11 @@ public:
         if (k == 0) { memcpy(flat, caller, 9 * (size_t)C); return; }
         for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3);
     }
+    void prior_to_internal(int k, const float* caller, float* flat) const override
+    {
+        if (k == 0) { memcpy(flat, caller, sizeof(float) * 9 * (size_t)C); return; }
+        for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3 * sizeof(float));
+    }
     // robust losses: cost, precomputeJ and the camera launch of every apply have a robust instantiation; every other route reads the stored (scaled) Jb, F and JP
     bool robust_ok() const override { return true; }
     int robust_prepare(int kind, float scale) override

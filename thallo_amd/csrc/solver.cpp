@@ -338,7 +338,7 @@ float* Plan::host_words()
 float Plan::compute_cost()
 {   // gauss_newton.t:1128-1136 -- partials instead of memset + atomics; same blocking 4-byte read-back
     if (dist_) return dist_cost();
-    const int nb = plugin->cost(ctx, slot(0));
+    const int nb = cost_partials(slot(0));
     if (nb < 0) { set_error("cost kernel launch failed (%d)", nb); return NAN; }
     set_nb(0, nb);
     thallo_hip_finish_sum(sum(0), (float*)scratch_.ptr, ctx.stream);
@@ -503,8 +503,9 @@ bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
     if (delta_unset) v_init.delta = nullptr;
     int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
+    if (prior_on() && (nb = prior_init(slot(2))) < 0) { set_error("the prior's launch behind PCGInit1 failed (%d)", nb); return false; }
     const char* what = nullptr;
-    if (forms_behind_init() && (nb = forms_setup(nullptr, v_.r, slot(2), nb, what)) < 0) { set_error("%s failed (%d)", what, nb); return false; }
+    if (forms_behind_init() && (nb = forms_setup(gn_shift(), v_.r, slot(2), nb, what)) < 0) { set_error("%s failed (%d)", what, nb); return false; }
     set_nb(2, nb); finish(2);
     ev_lin = timer_.stop_start(ev_setup, "Linear Solve", s);
     return true;
@@ -540,9 +541,9 @@ int Plan::step_gn(int ev_iter)
         return 1;
     }
     if (schur_on_ || block_on_) return step_gn_blocks(ev_iter);      // (solver_forms.cpp: the block forms live in the unfused loop only)
-    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on() && !robust_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan; and the block, without w: not for a robust one)
+    if (one_kernel_ && sp.lIterations >= 1 && plugin->resident_ok() && !held_on() && !robust_on() && !prior_on()) return step_gn_resident(ev_iter);      // (the resident loop restates PCGInit1's M^-1: not for a masked plan nor one with priors; and the block, without w: not for a robust one)
     if (one_kernel_ && plugin->one_kernel_iteration()) return step_gn_one_kernel(ev_iter);
-    if (plugin->apply_returns_sums()) return step_gn_expanded(ev_iter);
+    if (plugin->apply_returns_sums() && !prior_on()) return step_gn_expanded(ev_iter);      // (its apply takes no diagonal next to J^T J: a plan with priors runs the generic loop below)
     const int L = sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     int ev_lin, nb;
     if (!gn_begin(ev_iter, ev_lin)) return 0;
@@ -552,7 +553,7 @@ int Plan::step_gn(int ev_iter)
         // PCGStep1 (+ previous iteration's PCGStep3 and delta update)
         const PrevAlpha a = prev_alpha(k);
         if (batched) nb = plugin->pcg_step1_mode(ctx, v_, cur_, THALLO_IW_STEP1_MODE(k, 1), a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD));
-        else         nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
+        else         nb = gn_step1(k, a, sum(jN), slot(jD));
         if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
         set_nb(jD, nb); finish(jD); cur_ ^= 1;
         nb = plugin->pcg_step2(ctx, v_, sum(jN), sum(jD), slot(jB));      // PCGStep2 (r, z, betaN)
@@ -577,8 +578,8 @@ int Plan::ensure_lm_vectors()
 {
     if (v_.b) return 0;
     float** vecs[] = { &v_.b, &v_.Adelta, &v_.CtC, &v_.SSq, &v_.prevX, &v_.diag };
-    for (float** vp : vecs)
-        if (!(*vp = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return -1;
+    for (float** vp : vecs)      // (diag: a plan with priors has it already)
+        if (!*vp && !(*vp = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float)))) return -1;
     return 0;
 }
 
@@ -968,16 +969,21 @@ bool Plan::lm_setup(LmStep& st)
         }
     } else {
         if (!st.skip()) { nb = plugin->pcg_init(ctx, v_, cur_, slot(B)); st.check(nb, "PCGInit1 launch"); }        // r, raw diag (v_.diag); delta = 0
+        if (prior_on() && !st.skip()) { nb = prior_init(slot(B)); st.check(nb, "the prior's launch behind PCGInit1"); }      // r and the raw diag with W: SSq, CtC, pre, b and z below are formed from them
         if (!st.skip()) {
             TimedLaunch t(ctx, "PCGFinalizeDiagonal");                // :1596-1604 (alphaN restarts from 0)
             nb = thallo_hip_lm_finalize_diagonal(v_.diag + o, v_.SSq + o, v_.CtC + o, v_.pre + o, v_.r + o, v_.b + o, v_.z + o, st.n, radius_, sp.min_lm_diagonal, sp.max_lm_diagonal,
                                                  sp.nIter == 0 ? 1 : 0, st.pc ? 1 : 0, slot(B), s);
             st.check(nb, "PCGFinalizeDiagonal launch");
         }
+        if (prior_on() && !st.skip()) {                               // the step's shift plane: float32(CtC + w); CtC itself stays the reference's
+            TimedLaunch t(ctx, "PriorShift");
+            st.check(thallo_hip_prior_lm_shift(prior_w_, v_.CtC, v_.n, prior_shift_, s), "the prior's shift-plane launch");
+        }
     }
     if (forms_behind_init() && !st.skip()) {      // SSq, CtC, pre and b stay the reference's; z and alphaN_0 (Schur: r_c = g too) become the form's.  Every step: CtC follows the trust-region radius
         const char* what = nullptr;
-        nb = forms_setup(v_.CtC, v_.b, slot(B), nb, what);
+        nb = forms_setup(lm_shift(), v_.b, slot(B), nb, what);
         st.check(nb, what);
     }
     if (st.failed) return false;
@@ -1059,6 +1065,9 @@ void Plan::lm_loop_one_kernel(LmStep& st)
     const int L = st.L, B = st.B, period = st.period;
     float* lmst = st.lmst;
     cur_ = 0;
+    // (the plugin's launches of this loop read the diagonal next to J^T J from SolverVectors::CtC: with priors that is the step's shift plane while the loop is enqueued)
+    struct ShiftAsCtC { float*& ctc; float* const saved; ShiftAsCtC(float*& c, float* shift) : ctc(c), saved(c) { if (shift) ctc = shift; } ~ShiftAsCtC() { ctc = saved; } }
+        shift_as_ctc(v_.CtC, prior_on() ? prior_shift_ : nullptr);
     // alphaN_0 as a word (the owed-delta launch reads the scalars of iteration "done - 1" by address)
     st.check(thallo_hip_finish_sum(partial_sum(B), scal(B), s), "alphaN_0 sum");
     if (!st.failed) fin_[B] = 1;
@@ -1138,7 +1147,7 @@ void Plan::lm_loop_reference(LmStep& st)
         if (!st.skip()) {
             if (fold_p) {                                             // PCGStep3 + PCGStep1 + PCGStep1_Finish in one launch; p ping-pongs between the two buffers
                 float* pn = p == v_.p[0] ? v_.p[1] : v_.p[0];
-                ctx.lm_ctc = v_.CtC;
+                ctx.lm_ctc = lm_shift();
                 nb = plugin->apply_jtj_pupdate(ctx, v_.z, p, pn, v_.Ap, slot(jD), k == 0, sum(k ? jN - 2 : jN), sum(jN));
                 ctx.lm_ctc = nullptr;
                 st.check(nb, "PCGStep1 (+ PCGStep3) launch");
@@ -1148,7 +1157,7 @@ void Plan::lm_loop_reference(LmStep& st)
                     st.check(thallo_hip_pcg_pupdate(v_.z + st.oe, p + st.oe, p + st.oe, nullptr, st.ne, k == 0, sum(k ? jN - 2 : jN), sum(k ? jD - 2 : jD), sum(jN), s), "PCGStep3 launch");
                 }
                 if (fold_ctc) {                                       // PCGStep1 + PCGStep1_Finish in one launch: (J^T J + CtC) p ; alphaD
-                    ctx.lm_ctc = v_.CtC;
+                    ctx.lm_ctc = lm_shift();
                     nb = plugin->apply_jtj(ctx, p, v_.Ap, slot(jD));
                     ctx.lm_ctc = nullptr;
                     st.check(nb, "PCGStep1 launch");
@@ -1173,7 +1182,7 @@ void Plan::lm_loop_reference(LmStep& st)
             if (st.global_rows(-1, v_.delta)) { st.coll_failed = true; return; }          // (slab: applyJTJ reads delta on the ghost rows)
             if (!st.skip()) {
                 TimedLaunch t(ctx, "PCGStep2");
-                ctx.lm_ctc = fold_ctc ? v_.CtC : nullptr;
+                ctx.lm_ctc = fold_ctc ? lm_shift() : nullptr;
                 nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0));         // computeAdelta (+ CtC delta)
                 ctx.lm_ctc = nullptr;
                 st.check(nb, "computeAdelta launch");
@@ -1247,7 +1256,8 @@ int Plan::lm_finish(LmStep& st)
     if (st.global_rows(-1, v_.delta)) return 0;
     int nb = 0;
     if (!st.model_cost_done) {
-        if (!st.skip()) { nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); st.check(nb, "model cost: applyJTJ launch"); }
+        // (with priors the model's rows include theirs, 1/2 w (x - mu + delta)^2: b carries -W (x - mu) already and the apply adds W delta through its diagonal)
+        if (!st.skip()) { ctx.lm_ctc = gn_shift(); nb = plugin->apply_jtj(ctx, v_.delta, v_.Adelta, slot(T0)); ctx.lm_ctc = nullptr; st.check(nb, "model cost: applyJTJ launch"); }
         if (!st.skip()) set_nb(T0, nb);
         if (!st.skip()) { nb = thallo_hip_dot(v_.delta + st.o, v_.b + st.o, st.n, slot(T1), s); st.check(nb, "model cost: dot launch"); }
         if (!st.skip()) set_nb(T1, nb);
@@ -1274,7 +1284,7 @@ int Plan::lm_finish(LmStep& st)
     if (slab && dist_exchange_unknown_rows()) return 0;
     // cost after the step, into the same report: ONE blocking read per GN step
     int nbc = 0;
-    if (!st.skip()) { nbc = plugin->cost(ctx, slot(0)); st.check(nbc, "cost kernel launch"); }
+    if (!st.skip()) { nbc = cost_partials(slot(0)); st.check(nbc, "cost kernel launch"); }
     if (st.failed) return 0;
     if (!st.skip()) set_nb(0, nbc);
     const bool failed_before_cost_exchange = slab && dist_->failed;   // (then this rank's payload in the exchange below is poisoned: every rank's new cost is NaN)

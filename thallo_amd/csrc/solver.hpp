@@ -167,6 +167,11 @@ public:
     // at the next Init.  0 = ok
     int  set_held_unknowns(int input, const unsigned char* held, long n);
     long held_unknowns() const { return ready_ ? held_count_ : -1; }      // held scalars since the last Init (-1: no mask in force)
+    // ThalloX_PlanSetPrior: a Gaussian prior 1/2 w (x - mean)^2 per scalar of one Unknown (host floats in the caller's ids; weight 0: none there; weight NULL clears the
+    // input's prior); takes effect at the next Init.  0 = ok
+    int  set_prior(int input, const float* mean, const float* weight, long n);
+    long prior_terms() const { return ready_ ? prior_count_ : -1; }      // scalars with a positive weight since the last Init (-1: there was none)
+    int  prior_cost(double* out);                       // the prior's share of the cost at the current unknowns (0 where no prior is in force); nonzero: failed
     // ThalloX_PlanSetRobustLoss: kind THALLOX_LOSS_*, scale in residual units; takes effect at the next Init.  0 = ok
     int  set_robust_loss(int kind, float scale);
     long robust_weights(float* host_out, long n);      // rho'(s) per observation of the last linearisation, the caller's ids -> O, or -1 (no loss in force, n != O)
@@ -330,6 +335,21 @@ private:
     bool  schur_empty() const { return schur_on_ && held_on() && held_first_ == schur_n_; }
     int   held_prepare();
     int   hold_pcg(float* rz_out);                      // pre = z = 0 at the held scalars, the partials of r . z anew -> their number
+    // ---- Gaussian priors (prior.hip): the caller's (mean, weight) by unknown image; since the last Init the count of positive weights and the planes w, mu over the flat
+    // vector in the plan's internal ids on the device.  The launches run only when a weight is positive.  W reaches A through the shift: GN hands w itself to every
+    // ctc / shift argument, LM float32(CtC + w) in a plane of its own (prior_shift_, formed behind PCGFinalizeDiagonal); H stays without W
+    struct PriorInput { std::vector<float> mean, weight; };
+    std::map<int, PriorInput> prior_inputs_;
+    long prior_count_ = -1;
+    float *prior_w_ = nullptr, *prior_mu_ = nullptr, *prior_shift_ = nullptr;
+    bool  prior_on() const { return prior_count_ > 0; }
+    int   prior_prepare();
+    const float* gn_shift() const { return prior_on() ? prior_w_ : nullptr; }      // what a GN step (and the covariance) hands to a ctc / shift argument
+    const float* lm_shift() const { return prior_on() ? prior_shift_ : v_.CtC; }   // ... and an LM step
+    int   prior_cost_partials(float* out, int onto);    // the partials of the prior's cost at the current unknowns: stored (onto = 0 -> their number) or added onto the `onto` partials in out (-> onto)
+    int   prior_init(float* rz_out);                    // behind PCGInit1: r, diag, pre, z at the scalars with a prior, the partials of r . z anew -> their number
+    int   cost_partials(float* out);                    // the plugin's cost partials with the prior's added onto them -> the slot's count, the plugin's
+    int   gn_step1(int k, const PrevAlpha& a, thallo_sum_t bN, float* out);      // PCGStep3 + the apply of a GN iteration: the plugin's pcg_step1, with priors (J^T J + W) p
     // ---- robust loss (energy_ba.hip): handed to the plugin at Init
     int   robust_want_ = 0, robust_on_ = 0;
     float robust_want_scale_ = 0.0f, robust_on_scale_ = 0.0f;

@@ -117,6 +117,7 @@ int Plan::set_distributed(const ThalloX_Distributed& cfg)
     if (block_want_) { set_error("distributed: %s: the block-Jacobi preconditioner runs on one GPU (ThalloX_PlanSetPreconditioner came first)", plugin->name()); return -1; }
     if (!held_masks_.empty()) { set_error("distributed: %s: held unknowns run on one GPU (ThalloX_PlanSetHeldUnknowns came first)", plugin->name()); return -1; }
     if (robust_want_) { set_error("distributed: %s: robust losses run on one GPU (ThalloX_PlanSetRobustLoss came first)", plugin->name()); return -1; }
+    if (!prior_inputs_.empty()) { set_error("distributed: %s: priors run on one GPU (ThalloX_PlanSetPrior came first)", plugin->name()); return -1; }
     if (schur_want_) { set_error("distributed: %s: the %sSchur-complement solve runs on one GPU (ThalloX_PlanSetLinearSolver came first)", plugin->name(), schur_dense_want_ ? "dense Cholesky " : schur_explicit_want_ ? "assembled " : ""); return -1; }
     const int rc = set_distributed_impl(cfg);
     if (rc && dist_) {      // failed half-way (out of memory, a failing callback ...): the plan's vectors may already live in the released exchange block

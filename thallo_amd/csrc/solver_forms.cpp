@@ -27,6 +27,7 @@ int Plan::read_word(const unsigned* dev)
 int Plan::forms_prepare()
 {
     if (held_prepare()) return -1;
+    if (prior_prepare()) return -1;
     robust_on_ = 0;
     if (robust_want_ && refuse_unless_one_gpu_pcg(plugin->robust_ok(), "a robust loss needs")) return -1;
     if (plugin->robust_prepare(robust_want_, robust_want_scale_)) return -1;      // (kind 0: the plugin's routes launch what they launch without the call)
@@ -104,10 +105,10 @@ int Plan::step_gn_blocks(int ev_iter)
             {   TimedLaunch t(ctx, "PCGStep3");
                 nb = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, schur_n_, k == 0 ? 1 : 0, a.aN, a.aD, sum(jN), s); }
             if (nb < 0) { set_error("PCGStep3 launch failed (%d)", nb); return 0; }
-            nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], nullptr, v_.Ap, slot(jD), nullptr);
+            nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], gn_shift(), v_.Ap, slot(jD), nullptr);
             if (nb < 0) { set_error("Schur apply launch failed (%d)", nb); return 0; }
         } else {
-            nb = plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, sum(jN), slot(jD));
+            nb = gn_step1(k, a, sum(jN), slot(jD));
             if (nb < 0) { set_error("PCGStep1 launch failed (%d)", nb); return 0; }
         }
         set_nb(jD, nb); finish(jD); cur_ ^= 1;
@@ -141,8 +142,8 @@ void Plan::lm_loop_blocks(LmStep& st)
     const float* b = schur ? schur_g_ : v_.b;
     float* p = v_.p[0];
     auto apply = [&](const float* x, float* Ax, float* xAx_out) {      // (S + CtC_c) x or (J^T J + CtC) x ; the partials of x . that
-        if (schur) return plugin->schur_apply(ctx, schur_Ge_, x, v_.CtC, Ax, xAx_out, ctx.gate);
-        ctx.lm_ctc = v_.CtC;
+        if (schur) return plugin->schur_apply(ctx, schur_Ge_, x, lm_shift(), Ax, xAx_out, ctx.gate);
+        ctx.lm_ctc = lm_shift();
         const int rc = plugin->apply_jtj(ctx, x, Ax, xAx_out);
         ctx.lm_ctc = nullptr;
         return rc;
@@ -217,6 +218,7 @@ const char* Plan::schedule_name()
         t += sc;
     }
     if (held_on()) t += "; " + std::to_string(held_count_) + " unknowns held";
+    if (prior_on()) t += "; " + std::to_string(prior_count_) + " priors";
     return t.c_str();
 }
 
@@ -279,6 +281,101 @@ int Plan::hold_pcg(float* rz_out)
 {
     TimedLaunch t(ctx, "HoldPCG");
     return thallo_hip_hold_pcg(held_mask_, v_.r, v_.pre, v_.z, v_.n, rz_out, ctx.stream);
+}
+
+// ------------------------------------------------------------------ Gaussian priors (prior.hip, DESIGN.md "Gaussian priors")
+int Plan::set_prior(int input, const float* mean, const float* weight, long n)
+{
+    if (!ok_) return -1;
+    const auto& imgs = plugin->unknown_images();
+    int k = -1;
+    for (size_t i = 0; i < imgs.size(); ++i) if (imgs[i].param_index == input) k = (int)i;
+    if (!weight) { if (k >= 0) prior_inputs_.erase(k); return 0; }
+    if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no PCG loop to carry a prior through", plugin->name()); return -1; }
+    if (!plugin->hold_ok() || !plugin->apply_adds_ctc()) { set_error("%s: no priors for this energy (not every route of its plugin takes a flat diagonal next to J^T J; bundle_adjustment's do)", plugin->name()); return -1; }
+    if (dist_) { set_error("%s: priors run on one GPU (this plan is distributed)", plugin->name()); return -1; }
+    if (k < 0) { set_error("%s: input %d is not an Unknown of this energy", plugin->name(), input); return -1; }
+    if (n != imgs[(size_t)k].n_floats) { set_error("%s: the prior of input %d has %ld scalars, the unknown has %ld (elements x components)", plugin->name(), input, n, imgs[(size_t)k].n_floats); return -1; }
+    if (!mean) { set_error("%s: the prior of input %d has weights but no means", plugin->name(), input); return -1; }
+    for (long i = 0; i < n; ++i) {
+        if (!(weight[i] >= 0.0f) || !std::isfinite(weight[i])) { set_error("%s: the prior's weight of scalar %ld of input %d must be finite and not negative (got %g)", plugin->name(), i, input, (double)weight[i]); return -1; }
+        if (weight[i] > 0.0f && !std::isfinite(mean[i])) { set_error("%s: the prior's mean of scalar %ld of input %d must be finite where its weight is positive (got %g)", plugin->name(), i, input, (double)mean[i]); return -1; }
+    }
+    PriorInput& in = prior_inputs_[k];
+    in.mean.assign(mean, mean + n); in.weight.assign(weight, weight + n);
+    return 0;
+}
+
+int Plan::prior_prepare()
+{   // the planes in the plan's internal ids, counted, uploaded
+    prior_count_ = 0;
+    if (prior_inputs_.empty()) return 0;
+    if (refuse_unless_one_gpu_pcg(plugin->hold_ok() && plugin->apply_adds_ctc(), "priors need")) { prior_count_ = -1; return -1; }
+    std::vector<float> w((size_t)v_.n, 0.0f), mu((size_t)v_.n, 0.0f);
+    for (const auto& in : prior_inputs_) { plugin->prior_to_internal(in.first, in.second.weight.data(), w.data()); plugin->prior_to_internal(in.first, in.second.mean.data(), mu.data()); }
+    long count = 0;
+    for (size_t i = 0; i < w.size(); ++i) { if (w[i] > 0.0f) ++count; else mu[i] = 0.0f; }
+    if (count == 0) return 0;      // (no positive weight: the plan launches what it launches without a prior)
+    const size_t bytes = ((size_t)v_.n_alloc + 64) * sizeof(float);
+    if (!prior_w_) { prior_w_ = (float*)device_alloc(bytes); prior_mu_ = (float*)device_alloc(bytes); prior_shift_ = (float*)device_alloc(bytes); }
+    if (!v_.diag) v_.diag = (float*)device_alloc((size_t)v_.n_alloc * sizeof(float));      // (GN keeps no raw diagonal otherwise; the LM vectors take it over)
+    if (!prior_w_ || !prior_mu_ || !prior_shift_ || !v_.diag) { prior_w_ = prior_mu_ = prior_shift_ = nullptr; set_error("%s: out of device memory for the priors' planes", plugin->name()); return -1; }
+    if (hipMemcpy(prior_w_, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(prior_mu_, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("%s: cannot upload the priors' planes", plugin->name()); return -1; }
+    prior_count_ = count;
+    return 0;
+}
+
+int Plan::prior_cost_partials(float* out, int onto)
+{
+    TimedLaunch t(ctx, "PriorCost");
+    const long n0 = plugin->unknown_images()[0].n_floats;
+    return thallo_hip_prior_cost(prior_w_, prior_mu_, plugin->unknown_ptr(0), n0 < v_.n ? plugin->unknown_ptr(1) : nullptr, n0, v_.n, out, onto, ctx.stream);
+}
+
+int Plan::prior_init(float* rz_out)
+{
+    TimedLaunch t(ctx, "PriorInit");
+    const long n0 = plugin->unknown_images()[0].n_floats;
+    return thallo_hip_prior_init(prior_w_, prior_mu_, plugin->unknown_ptr(0), n0 < v_.n ? plugin->unknown_ptr(1) : nullptr, n0, v_.n, v_.r, v_.diag, v_.pre, v_.z,
+                                 plugin->use_preconditioner() ? 1 : 0, rz_out, ctx.stream);
+}
+
+// The cost kernel's partials with the prior's added onto the first of them, in the same slot: the slot's one reader adds everything in a fixed order and the slot keeps its
+// count, with priors and without (bundle adjustment's cost kernel fills all THALLO_HIP_MAX_PARTIALS from 262144 observations on: there is no room behind them)
+int Plan::cost_partials(float* out)
+{
+    const int nb = plugin->cost(ctx, out);      // (it also brings the plan's copy of the unknowns up to date: the prior's launch reads that copy)
+    if (nb < 1 || !prior_on()) return nb;
+    return prior_cost_partials(out, nb);
+}
+
+int Plan::prior_cost(double* out)
+{
+    if (!ok_ || !out) return -1;
+    *out = 0.0;
+    if (!ready_ || !prior_on()) return 0;
+    float* part = slot(1);      // (LM's q slot: written anew by every step before it is read)
+    const int nb = prior_cost_partials(part, 0);
+    if (nb < 0) { set_error("%s: the prior's cost launch failed (%d)", plugin->name(), nb); return -1; }
+    float h[THALLO_HIP_PRIOR_COST_PARTIALS];
+    if (hipMemcpyAsync(h, part, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) {
+        set_error("%s: cannot read the prior's cost", plugin->name()); return -1;
+    }
+    for (int i = 0; i < nb; ++i) *out += (double)h[i];
+    return 0;
+}
+
+// PCGStep3 + the apply of one iteration of the generic GN loop.  Without priors the plugin's pcg_step1; with them the same two launches, the apply through the plugin's
+// CtC-carrying entry point with w as the diagonal (ungated: GN has no gate word)
+int Plan::gn_step1(int k, const PrevAlpha& a, thallo_sum_t bN, float* out)
+{
+    if (!prior_on()) return plugin->pcg_step1(ctx, v_, cur_, k == 0, a.aN, a.aD, bN, out);
+    { TimedLaunch t(ctx, "PCGStep3"); const int rc = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, v_.n, k == 0 ? 1 : 0, a.aN, a.aD, bN, ctx.stream); if (rc < 0) return rc; }
+    ctx.lm_ctc = prior_w_;
+    const int nb = plugin->apply_jtj(ctx, v_.p[cur_ ^ 1], v_.Ap, out);
+    ctx.lm_ctc = nullptr;
+    return nb;
 }
 
 // ------------------------------------------------------------------ block-Jacobi preconditioner (block_precond.hip, DESIGN.md "Block-Jacobi preconditioner")
@@ -422,7 +519,7 @@ bool Plan::schur_dense_step(const float* g)
 }
 
 // ------------------------------------------------------------------ marginal covariances (ba_covariance.hip, DESIGN.md "Marginal covariances")
-// Sigma = (A_FF)^-1 with A = J_s^T J_s at the current unknowns, no CtC, on an LM plan too: the call re-linearises with the launches of a GN step's head -- PCGInit1
+// Sigma = (A_FF)^-1 with A = J_s^T J_s (+ W where priors are in force) at the current unknowns, no CtC, on an LM plan too: the call re-linearises with the launches of a GN step's head -- PCGInit1
 // (precomputeJ, `pre`) and forms_setup with shift = NULL: the mask, the block diagonal, both factors, W and the assembly -- and hands the step's S, both factors and the
 // mask to the plugin's column solve.  Everything those launches write, every step rewrites before use (r, pre, z, p, delta, diag; H, G, the status words, y, g, W, S;
 // slot 2); the LM state -- the radius and its decrease factor, SSq, CtC, b, the previous cost, prevX -- and the unknowns are not touched, no partial count is recorded, and
@@ -459,8 +556,9 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     struct NoStats { LaunchCtx& c; KernelTimer* t; NoStats(LaunchCtx& ctx) : c(ctx), t(ctx.timer) { c.timer = nullptr; } ~NoStats() { c.timer = t; } } no_stats(ctx);
     int nb = plugin->pcg_init(ctx, v_, 0, slot(2));
     if (nb < 0) { set_error("%s: covariance: PCGInit1 launch failed (%d)", e, nb); return -1; }
+    if (prior_on() && (nb = prior_init(slot(2))) < 0) { set_error("%s: covariance: the prior's launch failed (%d)", e, nb); return -1; }      // (W is part of A: the shift is w, on an LM plan too)
     const char* what = nullptr;
-    if ((nb = forms_setup(nullptr, v_.r, slot(2), nb, what)) < 0) { set_error("%s: covariance: %s failed (%d)", e, what, nb); return -1; }
+    if ((nb = forms_setup(gn_shift(), v_.r, slot(2), nb, what)) < 0) { set_error("%s: covariance: %s failed (%d)", e, what, nb); return -1; }
     thallo_cov_info_t ci;
     if (schur_dense_) {      // expand and factor once per call, then every batch through two triangular sweeps: iterations 0, worst residual 0
         int pivot = -1;
