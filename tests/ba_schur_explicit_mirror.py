@@ -3,7 +3,8 @@ kind 2) -- TEST INFRASTRUCTURE, not a test.  Everything but the application of S
 
   S_ij = [i = j] (B_ii + diag CtC_c,i) - sum over the terms (q, q') of block (i, j) of W_q W_q'^T,      W_q = (J_c,q^T J_p,q) G_p^T  (9 x 3),  Cp^-1 = G^T G
 
-  SchurStructure          the symbolic structure as BundleAdjustmentPlugin::schur_explicit builds it (vectorised), brute_force_counts the same numbers the slow way
+  SchurStructure          the symbolic structure as ReducedCameraSystem::configure builds it from csrc/ba_structure.cpp's count_terms / list_terms / place_blocks (vectorised;
+                          tests/test_ba_structure_host.py compares the two entry by entry), brute_force_counts the same numbers the slow way
   ExplicitSchurSystem     a SchurSystem whose apply multiplies by an S assembled block-wise from float32 W's with float32 accumulation (BaSchurExplicitMirror runs
                           BaSchurMirror's GN and LM loops on it)
   blocks64                float64 block-wise W and S from one Jb (no dense J)
@@ -86,6 +87,13 @@ def brute_force_counts(oc, op, C):
         per_row[i] += 1
         if i != j: per_row[j] += 1
     return len(blocks), terms, int(per_row.sum()), per_row
+
+
+def hand_made():
+    """4 cameras, 5 points, 12 observations: (camera 1, point 2) is observed twice, (camera 3, point 0) three times; camera 2 sees one point only; point 4 is seen once"""
+    oc = np.array([0, 1, 1, 3, 3, 3, 0, 2, 1, 0, 3, 1], np.int32)
+    op = np.array([0, 2, 2, 0, 0, 0, 1, 1, 1, 3, 3, 4], np.int32)
+    return oc, op, 4, 5
 
 
 def jb_of(J, C):

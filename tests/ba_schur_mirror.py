@@ -224,7 +224,7 @@ class BaSchurMirror(BaBlockMirror):
 
 # ------------------------------------------------------------------ the kernel tests' two sides: float64 (dense) and float32 in the kernels' order, both from one Jb
 class SchurLists:
-    """The index lists of BundleAdjustmentPlugin::prepare in the caller's point order or -- renumber -- in the plan's (points by first observing camera, a camera's
+    """The index lists of BundleAdjustmentPlugin::prepare (csrc/ba_structure.cpp incidence_lists; compared entry by entry in tests/test_ba_structure_host.py) in the caller's point order or -- renumber -- in the plan's (points by first observing camera, a camera's
     observations by internal point id); new2old: the plan's point j is the caller's new2old[j] (identity without renumbering)"""
 
     def __init__(self, oc, op, C, P, renumber=False):

@@ -4,7 +4,8 @@ they are.
 
   M^-1 = G^T G + P S_c^-1 P^T,   S_c = P^T S P,   P[9 c + j, 9 a(c) + j] = 1 at a free scalar,   S_c^-1 = Z^T Z,  Z = L^-1 D,  D S_c D = L L^T
 
-  default_k / greedy_aggregates / member_lists / validate_aggregates     the aggregates as BundleAdjustmentPlugin::schur_explicit builds and Plan::set_coarse_aggregates checks them
+  default_k / greedy_aggregates / member_lists / validate_aggregates     the aggregates as csrc/ba_structure.cpp builds them (greedy_aggregates, member_lists:
+                          compared entry by entry in tests/test_ba_structure_host.py) and Plan::set_coarse_aggregates checks them
   Coarse                  S_c, its scaling, Z and the apply from the stored blocks of an ExplicitSchurSystem: float64, or float32 (a LAPACK spotrf / strtrs on the rounded S_c)
   two_level_system        an ExplicitSchurSystem (under a mask: held_system) whose M adds the coarse term; BaTwoLevelMirror runs BaSchurMirror's GN and LM loops on it
   pcg32                   a plain float32 PCG on dense matrices for ITERATION COUNTS (not bits): the stop is sqrt(r . z / r0 . z0) <= tol

@@ -10,7 +10,7 @@ import pytest
 from thallo_amd import synthetic as syn
 
 from ba_schur_mirror import BaSchurMirror, SchurLists, dense_reduced_solve, with_extras
-from ba_schur_explicit_mirror import BaSchurExplicitMirror, SchurStructure, blocks64, brute_force_counts, jb_of
+from ba_schur_explicit_mirror import BaSchurExplicitMirror, SchurStructure, blocks64, brute_force_counts, hand_made, jb_of
 
 LM = dict(q_tolerance=0.1, function_tolerance=0.0)
 TABLE = [((24, 300, 1200), 12, 52), ((48, 1200, 5000), 16, 69)]      # ..., the block mirror's LM 5 x 150 iterations in total
@@ -60,13 +60,6 @@ def test_assembled_mirror_runs_the_matrix_free_mirrors_solves(dims, band, block_
     assert np.abs(np.array(ce) / np.array(cm) - 1).max() <= 1e-5
     assert np.abs(np.array(ge) / np.array(gm) - 1).max() <= 1e-5
     assert sum(ie) <= block_total, (ie, block_total)
-
-
-def hand_made():
-    """4 cameras, 5 points, 12 observations: (camera 1, point 2) is observed twice, (camera 3, point 0) three times; camera 2 sees one point only; point 4 is seen once"""
-    oc = np.array([0, 1, 1, 3, 3, 3, 0, 2, 1, 0, 3, 1], np.int32)
-    op = np.array([0, 2, 2, 0, 0, 0, 1, 1, 1, 3, 3, 4], np.int32)
-    return oc, op, 4, 5
 
 
 def test_structure_builder_against_a_brute_force_count():

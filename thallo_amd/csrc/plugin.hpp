@@ -14,6 +14,8 @@
 
 namespace thallo {
 
+class ReducedCameraSystem;
+
 void set_error(const char* fmt, ...);
 const char* last_error();
 // the value of one of the library's environment switches (A/B comparisons for tests and tools; the one table of them is in solver.cpp), or NULL
@@ -220,45 +222,10 @@ public:
     virtual bool block_precond_ok() const { return false; }
     virtual thallo_block_regions_t block_regions() const { thallo_block_regions_t r; r.n = 0; return r; }
     virtual int block_diag(LaunchCtx&, float* /*H*/) { return -1; }
-    // ---- Schur complement (opt-in: ThalloX_PlanSetLinearSolver; ba_schur.hip): plugins whose second block region can be eliminated exactly through its diagonal blocks, leaving
-    // PCG on the first region.  The defaults refuse.  reduce: the elimination factor Ge of the second region's blocks Hp (+ shift_p) with the held count, y and g = b_c - E y
-    // (also into r_out); apply: Sx = S x (+ ctc x) for a first-region vector and the partials of x . S x -> their number; back: the second region of delta from its first
-    // (p non-NULL: delta_c += (aN / aD) p first)
-    virtual bool schur_ok() const { return false; }
-    // (hold: the plan's mask of held unknowns over the flat vector or NULL -- the elimination factor then gets zero rows and columns there: thallo_hip_block_hold_factor)
-    virtual int schur_reduce(LaunchCtx&, const float* /*Hp*/, const float* /*shift_p*/, float* /*Ge*/, unsigned* /*held*/, const float* /*b*/, float* /*y*/, float* /*g*/, float* /*r_out*/,
-                             const unsigned char* /*hold*/) { return -1; }
-    virtual int schur_apply(LaunchCtx&, const float* /*Ge*/, const float* /*x*/, const float* /*ctc*/, float* /*Sx*/, float* /*xSx_out*/, const unsigned* /*gate*/) { return -1; }
-    // the assembled form (ThalloX_PlanSetLinearSolver kind 2; ba_schur_explicit.hip).  schur_explicit(true), at Init behind prepare(): build the symbolic structure of S in the
-    // plan's internal ids and allocate it -> the stored blocks, or -1 with the reason set (budget, int32 indices, memory); from then on schur_apply multiplies by the
-    // assembled S (and ignores ctc: the assembly added it).  schur_explicit(false): back to the matrix-free apply.  schur_assemble, every step behind schur_reduce: W and S
-    // from the step's blocks H, the elimination factor Ge and the LM CtC of the first region (or NULL)
-    virtual long schur_explicit(bool /*on*/) { return -1; }
-    virtual int schur_assemble(LaunchCtx&, const float* /*H*/, const float* /*Ge*/, const float* /*ctc*/) { return -1; }
-    virtual int schur_back(LaunchCtx&, const float* /*Ge*/, const float* /*b*/, float* /*delta*/, const float* /*p*/, thallo_sum_t /*aN*/, thallo_sum_t /*aD*/) { return -1; }
-    // the dense form (ThalloX_PlanSetLinearSolver kind 3; ba_schur_dense.hip): the assembled form plus a dense Cholesky factor of S in place of the reduced PCG loop.
-    // schur_dense_want(on), before schur_explicit(true): the dense lower triangle is part of the structure -- its bytes are added to the budget before anything is
-    // allocated, it is allocated behind the structure and freed with it, or by the next schur_explicit that does not want it.  schur_dense_n: the order of the matrix
-    // (-1: the dense form does not run).  schur_dense_solve, every step behind schur_assemble: T = D S D with the identity at the scalars `hold` holds (the plan's mask over
-    // the flat vector or NULL) and at non-positive diagonals, T = L L^T, delta_c = D L^-T L^-1 D g -> 0 or a negative launch code.  schur_dense_words: two device words
-    // of the last factor, [0] 1 + the index of the first pivot that was not positive (0: none), [1] the non-positive diagonals
-    virtual void schur_dense_want(bool /*on*/) {}
-    virtual long schur_dense_n() const { return -1; }
-    virtual int schur_dense_solve(LaunchCtx&, const unsigned char* /*hold*/, const float* /*g*/, float* /*delta_c*/) { return -1; }
-    virtual const unsigned* schur_dense_words() const { return nullptr; }
-    // the two-level preconditioner's coarse correction on the assembled S (ThalloX_PlanSetPreconditioner kind 2; ba_coarse.hip).  coarse_want(on, k, agg), before
-    // schur_explicit(true): the aggregates -- agg: the caller's (C ids, dense, checked) or NULL: greedy aggregates of at most k cameras (k = 0: the default size) built from
-    // the structure -- the dense coarse matrix, Z, Z^T and the work panels are part of the structure: counted in its budget before anything is allocated, allocated
-    // behind it, freed with it or by the next schur_explicit that does not want them.  coarse_n: the coarse scalars (-1: the form does not run).  coarse_setup, every step
-    // behind schur_assemble: S_c, its scaling, the factor, Z.  coarse_apply: z += P Z^T Z P^T r, the partials of |Z P^T r|^2 into yy_out -> their number.  coarse_words:
-    // three device words: the last factor's info, the coarse scalars with the identity's row, the factors since Init that met a non-positive pivot.  A plugin that runs
-    // the form hands its operands to its covariance's column solve as well
-    virtual void coarse_want(bool /*on*/, int /*k*/, const int* /*agg*/) {}
-    virtual long coarse_n() const { return -1; }
-    virtual int coarse_aggregates() const { return -1; }
-    virtual int coarse_setup(LaunchCtx&, const unsigned char* /*hold*/) { return -1; }
-    virtual int coarse_apply(LaunchCtx&, const unsigned char* /*hold*/, const float* /*r*/, float* /*z*/, float* /*yy_out*/, const unsigned* /*gate*/) { return -1; }
-    virtual const unsigned* coarse_words() const { return nullptr; }
+    // ---- the reduced camera system (opt-in: ThalloX_PlanSetLinearSolver, kind 2 of ThalloX_PlanSetPreconditioner, ThalloX_PlanCovariance; ba_reduced.hpp): a plugin whose
+    // second block region can be eliminated exactly through its diagonal blocks, leaving PCG -- or a dense factor -- on the first region, hands out the object that does
+    // it.  NULL: this energy eliminates nothing, and every setter that needs the object refuses
+    virtual ReducedCameraSystem* reduced_system() { return nullptr; }
     // ---- held unknowns (opt-in: ThalloX_PlanSetHeldUnknowns; held.hip): plugins all of whose PCG routes form M^-1 from the stored SolverVectors::pre.  hold_to_internal,
     // at Init behind prepare(): the caller's mask of unknown image k (n_floats bytes, the caller's ids) into the mask over the flat vector in the plan's internal ids
     virtual bool hold_ok() const { return false; }
@@ -273,17 +240,6 @@ public:
     virtual bool robust_ok() const { return false; }
     virtual int robust_prepare(int /*kind*/, float /*scale*/) { return 0; }
     virtual long robust_weights(LaunchCtx&, float* /*host_out*/, long /*n*/) { return -1; }
-    // ---- marginal covariances (ThalloX_PlanCovariance; ba_covariance.hip): plugins with an assembled Schur complement.  cov_elements: the elements of Unknown `input`
-    // (-1: not one of this energy's).  covariance, behind the GN set-up of the assembled form at the current unknowns (Plan::covariance): the blocks of the n elements
-    // ids (the caller's ids, checked) into host_out from Gc, the kept region's block factor, Ge, the elimination factor, and hold, the plan's mask or NULL; batches of
-    // thallo_hip_ba_cov_solve, whose infos are added up.  Its work buffers are the plugin's: allocated at the first call, kept, freed with it.  -> 0, or -1 with the reason set
-    virtual long cov_elements(int /*input*/) const { return -1; }
-    virtual int covariance(LaunchCtx&, int /*input*/, const int* /*ids*/, long /*n*/, const float* /*Gc*/, const float* /*Ge*/, const unsigned char* /*hold*/, float /*rel_tol*/,
-                           int /*max_iterations*/, float* /*host_out*/, thallo_cov_info_t* /*info*/) { return -1; }
-    // ... on a plan of the dense form: the columns through the factor (expanded and factored once per call) -> 0, -1 with the reason set, or -2 with *pivot = the index
-    // of the pivot that was not positive
-    virtual int covariance_dense(LaunchCtx&, int /*input*/, const int* /*ids*/, long /*n*/, const float* /*Gc*/, const float* /*Ge*/, const unsigned char* /*hold*/, float* /*host_out*/,
-                                 thallo_cov_info_t* /*info*/, int* /*pivot*/) { return -1; }
     // pointer to unknown image k as currently bound
     virtual float* unknown_ptr(int k) = 0;
     // the driver (or an exchange) has just written the unknowns: whatever the plugin derived from them (shape_from_shading's precomputed planes) is stale
@@ -327,6 +283,7 @@ public:
 struct DeviceBuffer {
     void* ptr = nullptr; size_t bytes = 0;
     int alloc(size_t n);
+    int upload(const std::vector<int>& h);      // alloc (with four words to spare) + copy -> 0, or nonzero
     void release();
     ~DeviceBuffer() { release(); }
 };

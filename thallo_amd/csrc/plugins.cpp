@@ -1,6 +1,8 @@
 // plugins.cpp -- the bundled energy plugins (host side).  Each one binds the caller's void**
 // (API/src/util.t:609-643) and forwards to the C-ABI kernel shim (include/thallo_hip.h).
 #include "plugin.hpp"
+#include "ba_reduced.hpp"
+#include "ba_structure.hpp"
 #ifdef THALLO_RESEARCH
 #include "probe/thallo_hip_research.h"      // research builds only: the persistent marching loop, bundle adjustment's one-launch loop (measured slower; not in the product)
 #endif
@@ -20,6 +22,11 @@ int DeviceBuffer::alloc(size_t n)
     bytes = n;
     e = hipMemset(ptr, 0, n);
     return e == hipSuccess ? 0 : -(int)e;
+}
+int DeviceBuffer::upload(const std::vector<int>& h)
+{
+    if (alloc(sizeof(int) * (h.size() + 4))) return -1;
+    return h.empty() || hipMemcpy(ptr, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
 void DeviceBuffer::release() { if (ptr) { hipFree(ptr); ptr = nullptr; bytes = 0; } }
 
@@ -803,7 +810,7 @@ class BundleAdjustmentPlugin : public EnergyPlugin {
     }
 public:
     BundleAdjustmentPlugin(const unsigned* dims) : C((int)dims[0]), P((int)dims[1]), O((int)dims[2])
-    { imgs.push_back({ 0, 9L * C }); imgs.push_back({ 1, 3L * P }); }
+    { imgs.push_back({ 0, 9L * C }); imgs.push_back({ 1, 3L * P }); view_.C = C; view_.P = P; view_.O = O; }      // (the sizes at once: the setters ask before the first Init)
     const char* name() const override { return "bundle_adjustment"; }
     long n_unknowns() const override { return 9L * C + 3L * P; }
     const std::vector<UnknownImage>& unknown_images() const override { return imgs; }
@@ -815,47 +822,24 @@ public:
         return 0;
     }
     int prepare(LaunchCtx&) override
-    {   // incidence lists (the reference sorts / transposes the CSR with cuSPARSE every GN iteration: gauss_newton.t:1349-1378)
+    {   // incidence lists (ba_structure.hpp), in the point order they choose
         std::vector<int> oc(O), op(O);
         if (hipMemcpy(oc.data(), oToC, sizeof(int) * O, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(op.data(), oToP, sizeof(int) * O, hipMemcpyDeviceToHost) != hipSuccess) { set_error("bundle_adjustment: cannot read the sparse maps"); return -1; }
         for (int o = 0; o < O; ++o)
             if (oc[o] < 0 || oc[o] >= C || op[o] < 0 || op[o] >= P) { set_error("bundle_adjustment: observation %d -> (camera %d, point %d) out of range", o, oc[o], op[o]); return -1; }
-        {   // the point order (see above)
-            std::vector<int> first(P, C);
-            for (int o = 0; o < O; ++o) if (oc[o] < first[op[o]]) first[op[o]] = oc[o];
-            double tv = 0.0; for (int j = 0; j + 1 < P; ++j) tv += std::abs(first[j + 1] - first[j]);
-            const char* e = env_switch("THALLO_BA_RENUMBER");
-            perm_ = !no_renumber_ && P > 1 && ((e && e[0] == '1') || (!(e && e[0] == '0') && tv > 64.0 * (double)P));
-            import_pending_ = true;
-            if (perm_) {
-                std::vector<int> new2old(P), old2new(P);
-                for (int j = 0; j < P; ++j) new2old[j] = j;
-                std::stable_sort(new2old.begin(), new2old.end(), [&](int x, int y) { return first[x] < first[y]; });
-                for (int j = 0; j < P; ++j) old2new[new2old[j]] = j;
-                h_new2old_ = new2old;
-                for (int o = 0; o < O; ++o) op[o] = old2new[op[o]];
-                if (ptsP.alloc(sizeof(float) * 3 * (size_t)P + 64) || d_new2old.alloc(sizeof(int) * ((size_t)P + 4)) || oToP_int.alloc(sizeof(int) * ((size_t)O + 4)) ||
-                    hipMemcpy(d_new2old.ptr, new2old.data(), sizeof(int) * P, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(oToP_int.ptr, op.data(), sizeof(int) * O, hipMemcpyHostToDevice) != hipSuccess) { set_error("bundle_adjustment: out of device memory for the renumbered points"); return -1; }
-            }
+        const char* e = env_switch("THALLO_BA_RENUMBER");
+        ba::Incidence L = ba::incidence_lists(C, P, O, oc, op, no_renumber_ || (e && e[0] == '0') ? ba::Renumber::Never : e && e[0] == '1' ? ba::Renumber::Always : ba::Renumber::Auto);
+        perm_ = L.perm;
+        import_pending_ = true;
+        if (perm_) {      // the solver's copy of the points in the plan's order, the order itself, and the observations' points in it
+            for (int q = 0; q < O; ++q) op[L.cam_obs[q]] = L.q_pt[q];
+            if (ptsP.alloc(sizeof(float) * 3 * (size_t)P + 64) || d_new2old.alloc(sizeof(int) * ((size_t)P + 4)) || oToP_int.alloc(sizeof(int) * ((size_t)O + 4)) ||
+                hipMemcpy(d_new2old.ptr, L.new2old.data(), sizeof(int) * P, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(oToP_int.ptr, op.data(), sizeof(int) * O, hipMemcpyHostToDevice) != hipSuccess) { set_error("bundle_adjustment: out of device memory for the renumbered points"); return -1; }
+            h_new2old_.swap(L.new2old);
         }
-        std::vector<int> cp(C + 1, 0), pp(P + 1, 0), cobs(O), qc(O), qp(O), pos(O), ppos(O);
-        for (int o = 0; o < O; ++o) { cp[oc[o] + 1]++; pp[op[o] + 1]++; }
-        for (int c = 0; c < C; ++c) cp[c + 1] += cp[c];
-        for (int j = 0; j < P; ++j) pp[j + 1] += pp[j];
-        std::vector<int> cc(cp.begin(), cp.end() - 1), pc(pp.begin(), pp.end() - 1);
-        for (int o = 0; o < O; ++o) cobs[cc[oc[o]]++] = o;
-        if (perm_)          // a renumbered plan also walks each camera's observations in the order of the (internal) point ids: its gathers then run through ptsP front to back
-            for (int c = 0; c < C; ++c) std::sort(cobs.begin() + cp[c], cobs.begin() + cp[c + 1], [&](int a, int b) { return op[a] != op[b] ? op[a] < op[b] : a < b; });
-        for (int q = 0; q < O; ++q) { const int o = cobs[q]; pos[o] = q; qc[q] = oc[o]; qp[q] = op[o]; }
-        if (perm_) { for (int q = 0; q < O; ++q) ppos[pc[qp[q]]++] = q; }          // ... and each point's observations in camera order
-        else for (int o = 0; o < O; ++o) ppos[pc[op[o]]++] = pos[o];
-        auto up = [&](DeviceBuffer& b, const std::vector<int>& h) {
-            if (b.alloc(sizeof(int) * (h.size() + 4))) return -1;
-            return hipMemcpy(b.ptr, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-        };
-        if (up(cam_ptr, cp) || up(cam_obs, cobs) || up(q_cam, qc) || up(q_pt, qp) || up(pt_ptr, pp) || up(pt_pos, ppos)) { set_error("bundle_adjustment: upload failed"); return -1; }
+        if (cam_ptr.upload(L.cam_ptr) || cam_obs.upload(L.cam_obs) || q_cam.upload(L.q_cam) || q_pt.upload(L.q_pt) || pt_ptr.upload(L.pt_ptr) || pt_pos.upload(L.pt_pos)) { set_error("bundle_adjustment: upload failed"); return -1; }
         if (!Jb.ptr && (Jb.alloc(sizeof(float) * 24 * (size_t)O + 64) || F.alloc(sizeof(float) * 2 * (size_t)O + 64))) return -1;
         {
             if (!q_ptk.ptr && (q_ptk.alloc(sizeof(int) * (size_t)O + 64) || JP.alloc(sizeof(float) * 6 * (size_t)O + 64) || JpP.alloc(sizeof(float) * 2 * (size_t)O + 64))) return -1;
@@ -864,6 +848,10 @@ public:
                 if (rc < 0 || se != hipSuccess) { set_error("bundle_adjustment: point order failed (launch %d, sync %d: %s)", rc, (int)se, hipGetErrorString(rc < 0 ? (hipError_t)(-rc) : se)); return -1; }
             }
         }
+        view_.cam_ptr = (const int*)cam_ptr.ptr; view_.cam_obs = (const int*)cam_obs.ptr; view_.q_cam = (const int*)q_cam.ptr; view_.q_pt = (const int*)q_pt.ptr;
+        view_.pt_ptr = (const int*)pt_ptr.ptr; view_.pt_pos = (const int*)pt_pos.ptr;
+        view_.Jb = (const float*)Jb.ptr; view_.JP = (const float*)JP.ptr; view_.JpP = (float*)JpP.ptr;
+        view_.new2old = perm_ ? &h_new2old_ : nullptr;
         // the PCG loop of a GN step in one launch (whole problem on one GPU) -- RESEARCH builds with THALLO_RESIDENT=2 only: bit-identical to three launches per iteration
         // but SLOWER at the ladybug shape (40.8 against 31.0 us per PCG iteration, profiles/r05/ba_resident_phases.txt: three grid-wide barriers of ~3 us each cost what the
         // launch boundaries did, and a static share of the camera blocks per workgroup balances worse than the hardware's dispatch of 431 of them); not in the product library
@@ -941,324 +929,19 @@ public:
         TimedLaunch t(c, "BlockDiag");
         return thallo_hip_ba_block_diag(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, H, c.stream);
     }
-    // Schur complement on the cameras: the launches load the camera half of Jb (what block_diag summed), the packed point blocks JP, and use JpP as their u / v / t scratch
-    bool schur_ok() const override { return true; }
-    int schur_reduce(LaunchCtx& c, const float* Hp, const float* shift_p, float* Ge, unsigned* held, const float* b, float* y, float* g, float* r_out, const unsigned char* hold) override
-    {
-        { TimedLaunch t(c, "SchurFactor"); const int rc = thallo_hip_ba_schur_factor(P, Hp, shift_p, Ge, held, c.stream); if (rc < 0) return rc; }
-        if (hold) {
-            TimedLaunch t(c, "BlockHoldFactor");
-            thallo_block_regions_t pts = block_regions(); pts.r[0] = pts.r[1]; pts.n = 1;
-            const int rc = thallo_hip_block_hold_factor(pts, hold, Ge, c.stream); if (rc < 0) return rc;
-        }
-        TimedLaunch t(c, "SchurReduce");
-        return thallo_hip_ba_schur_rhs(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, y, (float*)JpP.ptr, g, r_out,
-                                       c.stream);
-    }
-    // ---- the assembled reduced camera matrix (ThalloX_PlanSetLinearSolver kind 2; ba_schur_explicit.hip, DESIGN.md "Assembled reduced camera matrix").  The symbolic
-    // structure is built here on the host at Init from the point incidence lists as the device holds them (the plan's internal ids, a renumbered plan included): the
-    // co-visible camera pairs (every diagonal block present), and per lower-triangle block its terms (q, q'), two observations of one point, ascending.  A (camera, point)
-    // pair observed more than once simply yields more terms (both orders of the pair in the diagonal block: the lower triangle of the full sum needs both).
-    bool sx_on_ = false;
-    long sx_nblk_ = 0; int sx_nlower_ = 0;
-    DeviceBuffer sx_row_ptr_, sx_col_, sx_lower_, sx_term_ptr_, sx_terms_, sx_W_, sx_S_;
-    // the dense form (kind 3; ba_schur_dense.hip): the lower triangle T of D S D (ld x 9 C floats, factored in place every step), d, and two words -- the factor's info and the
-    // count of non-positive diagonals.  Part of the assembled structure: counted in its budget, allocated behind it, freed with it or by the next Init that does not want it
-    bool sd_want_ = false, sd_on_ = false;
-    long sd_ld_ = 0;
-    DeviceBuffer sd_T_, sd_d_, sd_words_;
-    void schur_dense_want(bool on) override { sd_want_ = on; }
-    // the two-level preconditioner's coarse correction (ThalloX_PlanSetPreconditioner kind 2; ba_coarse.hip): the aggregates (built below, from the structure), the dense
-    // coarse matrix T (S_c, its scaling, its factor in place), d, Z, Z^T, y, the identity panels of the inverse and three words.  Part of the assembled structure like the dense form
-    bool cz_want_ = false, cz_on_ = false;
-    int cz_k_ = 0, cz_K_ = 0;
-    std::vector<int> cz_given_;
-    DeviceBuffer cz_agg_, cz_mem_ptr_, cz_mem_, cz_T_, cz_d_, cz_Z_, cz_Zt_, cz_y_, cz_panels_, cz_words_;
-    void coarse_want(bool on, int k, const int* agg) override { cz_want_ = on; cz_k_ = k; cz_given_.clear(); if (on && agg) cz_given_.assign(agg, agg + C); }
-    long coarse_n() const override { return cz_on_ ? 9L * cz_K_ : -1; }
-    int coarse_aggregates() const override { return cz_on_ ? cz_K_ : -1; }
-    const unsigned* coarse_words() const override { return cz_on_ ? (const unsigned*)cz_words_.ptr : nullptr; }
-    void coarse_release() { for (DeviceBuffer* b : { &cz_agg_, &cz_mem_ptr_, &cz_mem_, &cz_T_, &cz_d_, &cz_Z_, &cz_Zt_, &cz_y_, &cz_panels_, &cz_words_ }) b->release(); }
-    thallo_coarse_t coarse_operands(const unsigned char* hold) const
-    {
-        thallo_coarse_t c;
-        c.C = C; c.K = cz_K_; c.n = 9L * cz_K_; c.ld = thallo_hip_dense_ld(c.n); c.agg = (const int*)cz_agg_.ptr; c.mem_ptr = (const int*)cz_mem_ptr_.ptr; c.mem = (const int*)cz_mem_.ptr;
-        c.hold = hold; c.T = (float*)cz_T_.ptr; c.d = (float*)cz_d_.ptr; c.Z = (float*)cz_Z_.ptr; c.Zt = (float*)cz_Zt_.ptr; c.y = (float*)cz_y_.ptr; c.words = (unsigned*)cz_words_.ptr;
-        return c;
-    }
-    // Greedy aggregates of at most k cameras from the lower blocks of the structure (keys: row * C + column, column <= row; the weight of a pair = its block's term count =
-    // its co-visible points): cameras in ascending id, an unassigned one seeds an aggregate, which repeatedly takes the unassigned camera with the largest summed weight
-    // to its members (ties: the lower id) until it has k members or no connected camera is left.  Deterministic.  -> agg, the member lists in the order of joining
-    static void coarse_greedy(int C_, int k, const std::vector<long>& keys, const std::vector<int>& term_ptr, std::vector<int>& agg, std::vector<int>& mem_ptr, std::vector<int>& mem)
-    {
-        std::vector<size_t> at((size_t)C_ + 1, 0);
-        for (long key : keys) { const int i = (int)(key / C_), j = (int)(key % C_); if (i != j) { at[(size_t)i + 1]++; at[(size_t)j + 1]++; } }
-        for (int c = 0; c < C_; ++c) at[(size_t)c + 1] += at[(size_t)c];
-        std::vector<int> nbr(at[(size_t)C_]), wgt(at[(size_t)C_]);
-        std::vector<size_t> fill(at.begin(), at.end() - 1);
-        for (size_t l = 0; l < keys.size(); ++l) {
-            const int i = (int)(keys[l] / C_), j = (int)(keys[l] % C_), w = term_ptr[l + 1] - term_ptr[l];
-            if (i == j) continue;
-            nbr[fill[(size_t)i]] = j; wgt[fill[(size_t)i]++] = w; nbr[fill[(size_t)j]] = i; wgt[fill[(size_t)j]++] = w;
-        }
-        agg.assign((size_t)C_, -1); mem_ptr.clear(); mem.clear();
-        std::vector<long> score((size_t)C_, 0);
-        std::vector<int> cand;
-        int K_ = 0;
-        for (int seed = 0; seed < C_; ++seed) {
-            if (agg[(size_t)seed] >= 0) continue;
-            const int a = K_++;
-            mem_ptr.push_back((int)mem.size());
-            cand.clear();
-            int next = seed, size = 0;
-            while (next >= 0) {
-                agg[(size_t)next] = a; mem.push_back(next); ++size;
-                for (size_t t = at[(size_t)next]; t < at[(size_t)next + 1]; ++t) {
-                    const int u = nbr[t];
-                    if (agg[(size_t)u] >= 0) continue;
-                    if (score[(size_t)u] == 0) cand.push_back(u);
-                    score[(size_t)u] += wgt[t] > 0 ? wgt[t] : 1;
-                }
-                next = -1;
-                if (size >= k) break;
-                for (int u : cand) if (agg[(size_t)u] < 0 && (next < 0 || score[(size_t)u] > score[(size_t)next] || (score[(size_t)u] == score[(size_t)next] && u < next))) next = u;
-            }
-            for (int u : cand) score[(size_t)u] = 0;
-        }
-        mem_ptr.push_back((int)mem.size());
-    }
-    long schur_dense_n() const override { return sd_on_ ? 9L * C : -1; }
-    const unsigned* schur_dense_words() const override { return sd_on_ ? (const unsigned*)sd_words_.ptr : nullptr; }
-    long schur_explicit(bool on) override
-    {
-        sx_on_ = false; sd_on_ = false; cz_on_ = false;
-        if (!on || !sd_want_) for (DeviceBuffer* b : { &sd_T_, &sd_d_, &sd_words_ }) b->release();
-        if (!on || !cz_want_) coarse_release();
-        if (!on) { for (DeviceBuffer* b : { &sx_row_ptr_, &sx_col_, &sx_lower_, &sx_term_ptr_, &sx_terms_, &sx_W_, &sx_S_ }) b->release(); return 0; }
-        if (C < 1) { set_error("bundle_adjustment: the assembled Schur-complement solve needs at least one camera"); return -1; }
-        std::vector<int> pp((size_t)P + 1), ppos((size_t)O), qc((size_t)O), qp((size_t)O), cp((size_t)C + 1);
-        auto down = [](std::vector<int>& h, const DeviceBuffer& b) { return h.empty() || hipMemcpy(h.data(), b.ptr, sizeof(int) * h.size(), hipMemcpyDeviceToHost) == hipSuccess; };
-        if (!down(pp, pt_ptr) || !down(ppos, pt_pos) || !down(qc, q_cam) || !down(qp, q_pt) || !down(cp, cam_ptr)) { set_error("bundle_adjustment: cannot read the incidence lists"); return -1; }
-        // a point's observations ascending in camera order: ascending cameras too, so the partners q' of q with camera(q') <= camera(q) are a prefix of the list
-        for (int j = 0; j < P; ++j) std::sort(ppos.begin() + pp[j], ppos.begin() + pp[j + 1]);
-        // the allowance: a quarter of the free device memory (the rule of the ring of p planes), or less (THALLO_AB=schur_s_max_mb=N)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { set_error("bundle_adjustment: cannot read the free device memory"); return -1; }
-        unsigned long long allowed = free_b / 4;
-        const char* why = "a quarter of the free device memory";
-        if (const char* e = env_switch("THALLO_SCHUR_S_MAX_MB")) {
-            const unsigned long long cap = strtoull(e, nullptr, 10) << 20;
-            if (cap < allowed) { allowed = cap; why = "THALLO_AB schur_s_max_mb"; }
-        }
-        // the dense form's bytes: known from C alone, refused first
-        const long sd_n = 9L * C, sd_ld = thallo_hip_dense_ld(sd_n);
-        const unsigned long long dense_bytes = sd_want_ ? 4ULL * (unsigned long long)sd_ld * (unsigned long long)sd_n + 4ULL * (unsigned long long)sd_n + 128 : 0;
-        if (sd_want_) {
-            if (sd_n > THALLO_HIP_DENSE_MAX_N) { set_error("bundle_adjustment: the dense reduced camera matrix has n = %ld, more than the dense kernels take (%ld)", sd_n, (long)THALLO_HIP_DENSE_MAX_N); return -1; }
-            unsigned long long dense_allowed = allowed; const char* dwhy = why;
-            if (const char* e = env_switch("THALLO_SCHUR_DENSE_MAX_MB")) {
-                const unsigned long long cap = strtoull(e, nullptr, 10) << 20;
-                if (cap < dense_allowed) { dense_allowed = cap; dwhy = "THALLO_AB schur_dense_max_mb"; }
-            }
-            if (dense_bytes > dense_allowed) {
-                set_error("bundle_adjustment: the dense reduced camera matrix wants %llu bytes of device memory (n = %ld scalars, leading dimension %ld), the budget allows %llu (%s): "
-                          "THALLOX_SOLVER_SCHUR_EXPLICIT_PCG solves on the block-sparse S without it", dense_bytes, sd_n, sd_ld, dense_allowed, dwhy);
-                return -1;
-            }
-        }
-        // the terms, counted before anything is built: an observation pairs with every observation of its point whose camera is not above its own
-        unsigned long long nterms = 0;
-        for (int j = 0; j < P; ++j)
-            for (int k = pp[j], e = pp[j]; k < pp[j + 1]; ++k) {
-                while (e < pp[j + 1] && qc[ppos[e]] <= qc[ppos[k]]) ++e;
-                nterms += (unsigned long long)(e - pp[j]);
-            }
-        const unsigned long long w_bytes = sizeof(float) * THALLO_HIP_SCHUR_W_STRIDE * (unsigned long long)O + 64;
-        auto over = [&](unsigned long long bytes, unsigned long long blocks, const char* least) {
-            if (sd_want_)
-                set_error("bundle_adjustment: the assembled reduced camera matrix and its dense lower triangle want %s%llu bytes of device memory (%s%llu blocks of 9 x 9, %llu terms, %d observations; "
-                          "%llu bytes dense, n = %ld), the budget allows %llu (%s): THALLOX_SOLVER_SCHUR_PCG applies S without assembling it", least, bytes, least, blocks, nterms, O, dense_bytes, sd_n, allowed, why);
-            else
-            set_error("bundle_adjustment: the assembled reduced camera matrix wants %s%llu bytes of device memory (%s%llu blocks of 9 x 9, %llu terms, %d observations), the budget allows %llu (%s): "
-                      "points seen by many cameras make the term count grow with the square of the track length; THALLOX_SOLVER_SCHUR_PCG applies S without assembling it",
-                      least, bytes, least, blocks, nterms, O, allowed, why);
-            return -1L;
-        };
-        if (nterms > 0x7fffffffULL) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu terms, more than its int32 indices hold", nterms); return -1; }
-        if (w_bytes + 8ULL * nterms + dense_bytes > allowed) return over(w_bytes + 8ULL * nterms + 81ULL * 4 * (unsigned long long)C + dense_bytes, (unsigned long long)C, "at least ");      // (the blocks are not counted yet)
-        // row by row, without a comparison sort of the terms: a row's observations ascend, a counting pass sizes its blocks, a second pass places the terms -- (q, q')
-        // ascending within every block.  Every diagonal block is present, with or without terms
-        std::vector<int> lower, term_ptr, tq(2 * (size_t)nterms + 2), cnt((size_t)C, 0), touched;
-        std::vector<long> keys;
-        size_t at = 0;
-        for (int i = 0; i < C; ++i) {
-            touched.assign(1, i);
-            for (int q = cp[i]; q < cp[i + 1]; ++q)
-                for (int k = pp[qp[q]]; k < pp[qp[q] + 1] && qc[ppos[k]] <= i; ++k) { const int c2 = qc[ppos[k]]; if (cnt[c2]++ == 0 && c2 != i) touched.push_back(c2); }
-            std::sort(touched.begin(), touched.end());
-            for (int c2 : touched) { keys.push_back((long)i * C + c2); term_ptr.push_back((int)at); const int n = cnt[c2]; cnt[c2] = (int)at; at += (size_t)n; }      // (cnt: now the block's next free place)
-            for (int q = cp[i]; q < cp[i + 1]; ++q)
-                for (int k = pp[qp[q]]; k < pp[qp[q] + 1] && qc[ppos[k]] <= i; ++k) { const size_t t = (size_t)cnt[qc[ppos[k]]]++; tq[2 * t] = q; tq[2 * t + 1] = ppos[k]; }
-            for (int c2 : touched) cnt[c2] = 0;
-        }
-        term_ptr.push_back((int)at);
-        if (at != nterms) { set_error("bundle_adjustment: internal: %zu terms listed, %llu counted", at, nterms); return -1; }
-        tq.resize(2 * (size_t)nterms);
-        const unsigned long long nlower = keys.size(), nblk = 2 * nlower - (unsigned long long)C;
-        if (nblk > 0x7fffffffULL / 3) { set_error("bundle_adjustment: the assembled reduced camera matrix has %llu blocks, more than its int32 indices hold", nblk); return -1; }
-        // the coarse correction: its aggregates come from the blocks just listed; its bytes -- T, Z, Z^T, the identity panels, d, y, the lists, the words -- join the count
-        std::vector<int> cz_agg, cz_mem_ptr, cz_mem;
-        unsigned long long coarse_bytes = 0;
-        long cz_n = 0, cz_ld = 0;
-        if (cz_want_) {
-            if (!cz_given_.empty()) {
-                cz_agg = cz_given_;
-                int K_ = 0;
-                for (int a : cz_agg) if (a + 1 > K_) K_ = a + 1;
-                cz_mem_ptr.assign((size_t)K_ + 1, 0);
-                for (int a : cz_agg) cz_mem_ptr[(size_t)a + 1]++;
-                for (int a = 0; a < K_; ++a) cz_mem_ptr[(size_t)a + 1] += cz_mem_ptr[(size_t)a];
-                cz_mem.resize((size_t)C);
-                std::vector<int> fillm(cz_mem_ptr.begin(), cz_mem_ptr.end() - 1);
-                for (int c = 0; c < C; ++c) cz_mem[(size_t)fillm[(size_t)cz_agg[(size_t)c]]++] = c;      // (members in ascending id)
-            } else {
-                const int k = cz_k_ > 0 ? cz_k_ : std::max(8, (C + 127) / 128);
-                coarse_greedy(C, k, keys, term_ptr, cz_agg, cz_mem_ptr, cz_mem);
-            }
-            cz_K_ = (int)cz_mem_ptr.size() - 1;
-            cz_n = 9L * cz_K_; cz_ld = thallo_hip_dense_ld(cz_n);
-            if (cz_n > THALLO_HIP_COARSE_MAX_N) {
-                set_error("bundle_adjustment: the two-level preconditioner's coarse space has n_c = %ld scalars (%d aggregates), more than its kernels take (%d): use larger aggregates "
-                          "(ThalloX_PlanSetCoarseAggregates)", cz_n, cz_K_, THALLO_HIP_COARSE_MAX_N);
-                return -1;
-            }
-            coarse_bytes = 3ULL * 4 * (unsigned long long)cz_ld * (unsigned long long)cz_n + 4ULL * (unsigned long long)thallo_hip_ba_coarse_panel_floats(cz_n) + 2ULL * 4 * (unsigned long long)cz_n +
-                           4ULL * (2ULL * (unsigned long long)C + (unsigned long long)cz_K_ + 1) + 6 * 64;
-        }
-        const unsigned long long bytes = 81ULL * 4 * nblk + 64 + w_bytes + 8ULL * nterms + 16 + 4ULL * ((unsigned long long)C + 5) + 4ULL * (nblk + 4) + 4ULL * (3 * nlower + 4) + 4ULL * (nlower + 5) + dense_bytes + coarse_bytes;
-        if (bytes > allowed && cz_want_) {
-            set_error("bundle_adjustment: the assembled reduced camera matrix and the two-level preconditioner's coarse matrices want %llu bytes of device memory (%llu blocks of 9 x 9, %llu terms, "
-                      "%d observations; %llu bytes coarse, %d aggregates, n_c = %ld), the budget allows %llu (%s)", bytes, nblk, nterms, O, coarse_bytes, cz_K_, cz_n, allowed, why);
-            return -1;
-        }
-        if (bytes > allowed) return over(bytes, nblk, "");
-        std::vector<int> row_ptr((size_t)C + 1, 0);
-        for (long key : keys) { const int i = (int)(key / C), j = (int)(key % C); row_ptr[i + 1]++; if (i != j) row_ptr[j + 1]++; }
-        for (int c = 0; c < C; ++c) row_ptr[c + 1] += row_ptr[c];
-        // places: the keys ascend by (row, column), so a row's lower part and diagonal are placed before the first (k, row), k > row, and those arrive with ascending k
-        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1), col((size_t)nblk);
-        lower.resize(3 * (size_t)nlower);
-        for (size_t l = 0; l < keys.size(); ++l) {
-            const int i = (int)(keys[l] / C), j = (int)(keys[l] % C);
-            const int bij = fill[i]++; col[bij] = j;
-            int bji = bij;
-            if (i != j) { bji = fill[j]++; col[bji] = i; }
-            lower[3 * l] = bij; lower[3 * l + 1] = bji; lower[3 * l + 2] = i == j ? i : -1;
-        }
-        auto up = [&](DeviceBuffer& b, const std::vector<int>& h) {
-            if (b.alloc(sizeof(int) * (h.size() + 4))) return -1;
-            return h.empty() || hipMemcpy(b.ptr, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-        };
-        if (up(sx_row_ptr_, row_ptr) || up(sx_col_, col) || up(sx_lower_, lower) || up(sx_term_ptr_, term_ptr) || up(sx_terms_, tq) ||
-            sx_W_.alloc((size_t)w_bytes) || sx_S_.alloc(sizeof(float) * 81 * (size_t)nblk + 64)) {
-            const std::string whyn = last_error();
-            set_error("bundle_adjustment: out of device memory for the assembled reduced camera matrix (%llu bytes): %s", bytes, whyn.c_str());
-            return -1;
-        }
-        if (sd_want_ && (sd_T_.alloc(4 * (size_t)sd_ld * (size_t)sd_n + 64) || sd_d_.alloc(4 * (size_t)sd_n + 64) || sd_words_.alloc(64))) {
-            const std::string whyn = last_error();
-            for (DeviceBuffer* b : { &sd_T_, &sd_d_, &sd_words_ }) b->release();
-            set_error("bundle_adjustment: out of device memory for the dense reduced camera matrix (%llu bytes): %s", dense_bytes, whyn.c_str());
-            return -1;
-        }
-        if (cz_want_) {
-            const size_t tz = 4 * (size_t)cz_ld * (size_t)cz_n + 64;
-            if (up(cz_agg_, cz_agg) || up(cz_mem_ptr_, cz_mem_ptr) || up(cz_mem_, cz_mem) || cz_T_.alloc(tz) || cz_Z_.alloc(tz) || cz_Zt_.alloc(tz) || cz_d_.alloc(4 * (size_t)cz_n + 64) ||
-                cz_y_.alloc(4 * (size_t)cz_n + 64) || cz_panels_.alloc(4 * (size_t)thallo_hip_ba_coarse_panel_floats(cz_n) + 64) || cz_words_.alloc(64) ||
-                hipMemset(cz_words_.ptr, 0, 64) != hipSuccess) {
-                const std::string whyn = last_error();
-                coarse_release();
-                set_error("bundle_adjustment: out of device memory for the two-level preconditioner's coarse matrices (%llu bytes): %s", coarse_bytes, whyn.c_str());
-                return -1;
-            }
-        }
-        sx_nblk_ = (long)nblk; sx_nlower_ = (int)nlower; sx_on_ = true; sd_on_ = sd_want_; sd_ld_ = sd_ld; cz_on_ = cz_want_;
-        return sx_nblk_;
-    }
-    // expand + factor of the step's (or the covariance call's) assembled S; hold: the plan's mask over the flat vector (its first 9 C bytes are the cameras') or NULL
-    int schur_dense_factor(LaunchCtx& c, const unsigned char* hold)
-    {
-        if (!sd_on_) return -1;
-        unsigned* words = (unsigned*)sd_words_.ptr;
-        {   TimedLaunch t(c, "SchurDenseExpand");
-            const int rc = thallo_hip_ba_schur_dense_expand(C, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, hold, sd_ld_, (float*)sd_T_.ptr, (float*)sd_d_.ptr,
-                                                            words + 1, c.stream);
-            if (rc < 0) return rc; }
-        TimedLaunch t(c, "SchurDenseFactor");
-        return thallo_hip_dense_potrf(9L * C, sd_ld_, (float*)sd_T_.ptr, (int*)words, c.stream);
-    }
-    int schur_dense_solve(LaunchCtx& c, const unsigned char* hold, const float* g, float* delta_c) override
-    {
-        const int rc = schur_dense_factor(c, hold);
-        if (rc < 0) return rc;
-        TimedLaunch t(c, "SchurDenseSolve");
-        return thallo_hip_dense_potrs_vec(9L * C, sd_ld_, (const float*)sd_T_.ptr, (const float*)sd_d_.ptr, g, delta_c, THALLO_HIP_DENSE_BOTH, c.stream);
-    }
-    int coarse_setup(LaunchCtx& c, const unsigned char* hold) override
-    {
-        if (!cz_on_) return -1;
-        const thallo_coarse_t cz = coarse_operands(hold);
-        int rc;
-        {   TimedLaunch t(c, "CoarseAssemble");
-            if ((rc = thallo_hip_ba_coarse_assemble(&cz, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, c.stream)) < 0) return rc; }
-        { TimedLaunch t(c, "CoarseScale"); if ((rc = thallo_hip_ba_coarse_scale(&cz, c.stream)) < 0) return rc; }
-        { TimedLaunch t(c, "CoarseFactor"); if ((rc = thallo_hip_dense_potrf(cz.n, cz.ld, cz.T, (int*)cz.words, c.stream)) < 0) return rc; }
-        TimedLaunch t(c, "CoarseInverse");
-        return thallo_hip_ba_coarse_inverse(&cz, (float*)cz_panels_.ptr, c.stream);
-    }
-    int coarse_apply(LaunchCtx& c, const unsigned char* hold, const float* r, float* z, float* yy_out, const unsigned* gate) override
-    {
-        if (!cz_on_) return -1;
-        const thallo_coarse_t cz = coarse_operands(hold);
-        TimedLaunch t(c, "CoarseApply");
-        return thallo_hip_ba_coarse_apply(&cz, r, z, yy_out, gate, c.stream);
-    }
-    int schur_assemble(LaunchCtx& c, const float* H, const float* Ge, const float* ctc) override
-    {
-        if (!sx_on_) return -1;
-        { TimedLaunch t(c, "SchurW"); const int rc = thallo_hip_ba_schur_w(O, P, (const int*)q_pt.ptr, (const float*)Jb.ptr, Ge, (float*)sx_W_.ptr, c.stream); if (rc < 0) return rc; }
-        TimedLaunch t(c, "SchurAssemble");
-        return thallo_hip_ba_schur_assemble(C, sx_nlower_, sx_nblk_, (const int*)sx_lower_.ptr, (const int*)sx_term_ptr_.ptr, (const int*)sx_terms_.ptr, (const float*)sx_W_.ptr, H, ctc,
-                                            (float*)sx_S_.ptr, c.stream);
-    }
-    int schur_apply(LaunchCtx& c, const float* Ge, const float* x, const float* ctc, float* Sx, float* out, const unsigned* gate) override
-    {
-        if (sx_on_) {      // (ctc is in the assembled diagonal blocks already)
-            TimedLaunch t(c, "SchurApplyS");
-            return thallo_hip_ba_schur_apply_s(C, sx_nblk_, (const int*)sx_row_ptr_.ptr, (const int*)sx_col_.ptr, (const float*)sx_S_.ptr, x, Sx, out, gate, c.stream);
-        }
-        TimedLaunch t(c, "SchurApply");
-        return thallo_hip_ba_schur_apply(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, x, ctc, (float*)JpP.ptr, Sx, out,
-                                         gate, c.stream);
-    }
-    int schur_back(LaunchCtx& c, const float* Ge, const float* b, float* delta, const float* p, thallo_sum_t aN, thallo_sum_t aD) override
-    {
-        TimedLaunch t(c, "SchurBack");
-        return thallo_hip_ba_schur_back(C, P, (const int*)cam_ptr.ptr, (const int*)pt_ptr.ptr, (const int*)pt_pos.ptr, (const float*)Jb.ptr, (const float*)JP.ptr, Ge, b, delta, p, aN, aD,
-                                        (float*)JpP.ptr, c.stream);
-    }
+    // the Schur complement on the cameras in all its forms, and the covariances: ba_reduced.hpp, which reads this plugin through view_ (filled by prepare())
+    ReducedSystemView view_;
+    ReducedCameraSystem reduced_{ view_ };
+    ReducedCameraSystem* reduced_system() override { return &reduced_; }
     // held unknowns: every PCG route of this plugin takes M^-1 from v.pre (the flat updates, k_cam2 / k_pt2's sums, the residual reset) or from G
     bool hold_ok() const override { return true; }
-    void hold_to_internal(int k, const unsigned char* caller, unsigned char* flat) const override
+    template <class T> void to_internal(int k, const T* caller, T* flat) const      // one plane of unknown image k, the caller's point ids -> the plan's
     {
-        if (k == 0) { memcpy(flat, caller, 9 * (size_t)C); return; }
-        for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3);
+        if (k == 0) { memcpy(flat, caller, sizeof(T) * 9 * (size_t)C); return; }
+        for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3 * sizeof(T));
     }
-    void prior_to_internal(int k, const float* caller, float* flat) const override
-    {
-        if (k == 0) { memcpy(flat, caller, sizeof(float) * 9 * (size_t)C); return; }
-        for (int j = 0; j < P; ++j) memcpy(flat + 9 * (size_t)C + 3 * (size_t)j, caller + 3 * (size_t)(perm_ ? h_new2old_[j] : j), 3 * sizeof(float));
-    }
+    void hold_to_internal(int k, const unsigned char* caller, unsigned char* flat) const override { to_internal(k, caller, flat); }
+    void prior_to_internal(int k, const float* caller, float* flat) const override { to_internal(k, caller, flat); }
     // robust losses: cost, precomputeJ and the camera launch of every apply have a robust instantiation; every other route reads the stored (scaled) Jb, F and JP
     bool robust_ok() const override { return true; }
     int robust_prepare(int kind, float scale) override
@@ -1285,121 +968,6 @@ public:
         for (int q = 0; q < O; ++q) host_out[co[(size_t)q]] = w[(size_t)q] * w[(size_t)q];
         return O;
     }
-    // ---- marginal covariances (ThalloX_PlanCovariance; ba_covariance.hip, DESIGN.md "Marginal covariances"): batches of 7 cameras or 21 points through
-    // thallo_hip_ba_cov_solve on the assembled S, W and the lists of this step's set-up.  The caller's point ids become the plan's as hold_to_internal maps a mask
-    DeviceBuffer cov_work_, cov_ids_, cov_out_;
-    unsigned* cov_pinned_ = nullptr;      // two pinned host words: the frozen counts of the two chunks in flight
-    long cov_elements(int input) const override { return input == 0 ? C : input == 1 ? P : -1; }
-    int covariance(LaunchCtx& c, int input, const int* ids, long n, const float* Gc, const float* Ge, const unsigned char* hold, float rel_tol, int max_iterations, float* host_out,
-                   thallo_cov_info_t* info) override
-    {
-        if (!sx_on_) { set_error("bundle_adjustment: a covariance needs the assembled reduced camera matrix"); return -1; }
-        const int per = input == 0 ? THALLO_HIP_COV_K / 9 : THALLO_HIP_COV_K / 3, fl = input == 0 ? 81 : 9;
-        const long cov_bytes = thallo_hip_ba_cov_coarse_work_bytes(C, cz_on_ ? 9L * cz_K_ : 0);
-        if (cov_work_.ptr && cov_work_.bytes < (size_t)cov_bytes) cov_work_.release();      // (a re-Init switched the two-level form on, or to more aggregates)
-        if (!cov_work_.ptr && (cov_work_.alloc((size_t)cov_bytes) || cov_ids_.alloc(sizeof(int) * THALLO_HIP_COV_K) ||
-                               cov_out_.alloc(sizeof(float) * 81 * (THALLO_HIP_COV_K / 9) + 64))) {
-            for (DeviceBuffer* b : { &cov_work_, &cov_ids_, &cov_out_ }) b->release();
-            set_error("bundle_adjustment: out of device memory for the covariance's work vectors (%ld bytes)", cov_bytes); return -1;
-        }
-        if (!cov_pinned_ && hipHostMalloc((void**)&cov_pinned_, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { cov_pinned_ = nullptr; (void)hipGetLastError(); }      // (without them: a blocking read per chunk)
-        std::vector<int> in(ids, ids + n);
-        if (input == 1 && perm_) {
-            std::vector<int> old2new((size_t)P);
-            for (int j = 0; j < P; ++j) old2new[(size_t)h_new2old_[(size_t)j]] = j;
-            for (long i = 0; i < n; ++i) in[(size_t)i] = old2new[(size_t)ids[i]];
-        }
-        thallo_cov_sys_t sys;
-        sys.C = C; sys.P = P; sys.nblk = sx_nblk_; sys.row_ptr = (const int*)sx_row_ptr_.ptr; sys.col = (const int*)sx_col_.ptr; sys.S = (const float*)sx_S_.ptr;
-        sys.Gc = Gc; sys.Ge = Ge; sys.W = (const float*)sx_W_.ptr; sys.pt_ptr = (const int*)pt_ptr.ptr; sys.pt_pos = (const int*)pt_pos.ptr; sys.q_cam = (const int*)q_cam.ptr; sys.hold = hold;
-        *info = thallo_cov_info_t{ 0, 0, 0, 0, 0.0f };
-        thallo_coarse_t cz{};
-        if (cz_on_) cz = coarse_operands(hold);      // (the two-level preconditioner of the plan's last Init: its Z is this call's set-up's)
-        for (long b0 = 0; b0 < n; b0 += per) {
-            const int nreq = (int)(n - b0 < per ? n - b0 : per);
-            thallo_cov_info_t bi;
-            if (hipMemcpyAsync(cov_ids_.ptr, in.data() + b0, sizeof(int) * (size_t)nreq, hipMemcpyHostToDevice, c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot upload the covariance's ids"); return -1; }
-            const int rc = thallo_hip_ba_cov_solve_coarse(&sys, cz_on_ ? &cz : nullptr, input, (const int*)cov_ids_.ptr, nreq, rel_tol, max_iterations, cov_work_.ptr, cov_pinned_,
-                                                          (float*)cov_out_.ptr, &bi, c.stream);
-            if (rc < 0) { set_error("bundle_adjustment: the covariance's column solve failed (%d)", rc); return -1; }
-            if (hipMemcpyAsync(host_out + (size_t)fl * (size_t)b0, cov_out_.ptr, sizeof(float) * (size_t)fl * (size_t)nreq, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-                hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance blocks"); return -1; }
-            info->iterations += bi.iterations; info->columns += bi.columns; info->not_converged += bi.not_converged; info->nan_blocks += bi.nan_blocks;
-            if (!(bi.worst <= info->worst)) info->worst = bi.worst;
-        }
-        return 0;
-    }
-    // ... and on a plan of the dense form (kind 3): S is expanded and factored once per call, then per group of up to SD_GROUPS batches thallo_hip_ba_cov_rhs per batch, ONE
-    // thallo_hip_dense_potrs_cols launch (a workgroup per batch) and thallo_hip_ba_cov_out per batch.  -> 0; -1 with the reason set; -2: the factor met a pivot that is
-    // not positive (words[0]; the plan words the message).  info->not_converged: the requested camera columns at scalars whose diagonal is not positive
-    static constexpr int SD_GROUPS = 8;
-    DeviceBuffer sdc_panels_, sdc_ids_, sdc_out_;
-    int covariance_dense(LaunchCtx& c, int input, const int* ids, long n, const float* Gc, const float* Ge, const unsigned char* hold, float* host_out, thallo_cov_info_t* info,
-                         int* pivot) override
-    {
-        if (!sd_on_) { set_error("bundle_adjustment: the dense covariance needs the dense reduced camera matrix"); return -1; }
-        const int K = THALLO_HIP_COV_K, per = input == 0 ? K / 9 : K / 3, fl = input == 0 ? 81 : 9;
-        const long sd_n = 9L * C, pn = sd_n * K;
-        const long nbatch = (n + per - 1) / per;
-        const int groups = (int)(nbatch < SD_GROUPS ? nbatch : SD_GROUPS);
-        if (sdc_panels_.bytes < sizeof(float) * (size_t)pn * (size_t)groups + 64 &&
-            (sdc_panels_.alloc(sizeof(float) * (size_t)pn * (size_t)groups + 64) || sdc_ids_.alloc(sizeof(int) * K * SD_GROUPS) || sdc_out_.alloc(sizeof(float) * 81 * (K / 9) * SD_GROUPS + 64))) {
-            for (DeviceBuffer* b : { &sdc_panels_, &sdc_ids_, &sdc_out_ }) b->release();
-            set_error("bundle_adjustment: out of device memory for the dense covariance's panels (%zu bytes)", sizeof(float) * (size_t)pn * (size_t)groups); return -1;
-        }
-        int rc = schur_dense_factor(c, hold);
-        if (rc < 0) { set_error("bundle_adjustment: the dense covariance's expansion or factor failed to launch (%d)", rc); return -1; }
-        unsigned words[2] = { 0, 0 };
-        std::vector<float> dh((size_t)sd_n);
-        std::vector<unsigned char> hh(hold ? (size_t)sd_n : 0);
-        if (hipMemcpyAsync(words, sd_words_.ptr, sizeof(words), hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-            hipMemcpyAsync(dh.data(), sd_d_.ptr, sizeof(float) * (size_t)sd_n, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-            (hold && hipMemcpyAsync(hh.data(), hold, (size_t)sd_n, hipMemcpyDeviceToHost, c.stream) != hipSuccess) ||
-            hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the dense factor's status"); return -1; }
-        if (words[0]) { *pivot = (int)words[0] - 1; return -2; }
-        std::vector<int> in(ids, ids + n);
-        if (input == 1 && perm_) {
-            std::vector<int> old2new((size_t)P);
-            for (int j = 0; j < P; ++j) old2new[(size_t)h_new2old_[(size_t)j]] = j;
-            for (long i = 0; i < n; ++i) in[(size_t)i] = old2new[(size_t)ids[i]];
-        }
-        thallo_cov_sys_t sys;
-        sys.C = C; sys.P = P; sys.nblk = sx_nblk_; sys.row_ptr = (const int*)sx_row_ptr_.ptr; sys.col = (const int*)sx_col_.ptr; sys.S = (const float*)sx_S_.ptr;
-        sys.Gc = Gc; sys.Ge = Ge; sys.W = (const float*)sx_W_.ptr; sys.pt_ptr = (const int*)pt_ptr.ptr; sys.pt_pos = (const int*)pt_pos.ptr; sys.q_cam = (const int*)q_cam.ptr; sys.hold = hold;
-        *info = thallo_cov_info_t{ 0, 0, 0, 0, 0.0f };
-        unsigned* nan_word = (unsigned*)sd_words_.ptr + 2;
-        if (hipMemsetAsync(nan_word, 0, sizeof(unsigned), c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot clear the dense covariance's NaN count"); return -1; }
-        for (long g0 = 0; g0 < nbatch; g0 += groups) {
-            const int ng = (int)(nbatch - g0 < groups ? nbatch - g0 : groups);
-            const long first = g0 * per, last = first + (long)ng * per < n ? first + (long)ng * per : n;
-            auto nreq_of = [&](int g) { const long b0 = first + (long)g * per; return (int)(last - b0 < per ? last - b0 : per); };
-            std::vector<int> padded((size_t)ng * (size_t)K, 0);      // (a batch's ids at a stride of K)
-            for (int g = 0; g < ng; ++g) for (int j = 0; j < nreq_of(g); ++j) padded[(size_t)g * K + (size_t)j] = in[(size_t)(first + (long)g * per + j)];
-            if (hipMemcpy(sdc_ids_.ptr, padded.data(), sizeof(int) * padded.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("bundle_adjustment: cannot upload the covariance's ids"); return -1; }
-            for (int g = 0; g < ng; ++g)
-                if ((rc = thallo_hip_ba_cov_rhs(&sys, input, (const int*)sdc_ids_.ptr + (size_t)g * K, nreq_of(g), (float*)sdc_panels_.ptr + (size_t)g * (size_t)pn, c.stream)) < 0) break;
-            if (rc >= 0) rc = thallo_hip_dense_potrs_cols(sd_n, sd_ld_, (const float*)sd_T_.ptr, (const float*)sd_d_.ptr, (float*)sdc_panels_.ptr, ng, THALLO_HIP_DENSE_BOTH, c.stream);
-            for (int g = 0; g < ng && rc >= 0; ++g)
-                rc = thallo_hip_ba_cov_out(&sys, input, (const int*)sdc_ids_.ptr + (size_t)g * K, nreq_of(g), (const float*)sdc_panels_.ptr + (size_t)g * (size_t)pn,
-                                           (float*)sdc_out_.ptr + (size_t)g * (size_t)fl * (size_t)per, nan_word, c.stream);
-            if (rc < 0) { set_error("bundle_adjustment: the dense covariance's column solve failed (%d)", rc); return -1; }
-            if (hipMemcpyAsync(host_out + (size_t)fl * (size_t)first, sdc_out_.ptr, sizeof(float) * (size_t)fl * (size_t)(last - first), hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-                hipStreamSynchronize(c.stream) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance blocks"); return -1; }
-        }
-        unsigned nans = 0;
-        if (hipMemcpy(&nans, nan_word, sizeof(nans), hipMemcpyDeviceToHost) != hipSuccess) { set_error("bundle_adjustment: cannot read the covariance's NaN count"); return -1; }
-        info->nan_blocks = (int)nans;
-        if (input == 0) {
-            for (long i = 0; i < n; ++i)
-                for (int a = 0; a < 9; ++a) {
-                    const size_t u = 9 * (size_t)ids[i] + (size_t)a;
-                    if (hold && hh[u]) continue;                                  // (a held scalar's unit column is zero and needs no solve)
-                    if (dh[u] > 0.0f) info->columns++; else info->not_converged++;
-                }
-        } else info->columns = (int)(3 * n) - 3 * (int)nans;
-        return 0;
-    }
-    ~BundleAdjustmentPlugin() override { if (cov_pinned_) (void)hipHostFree(cov_pinned_); }
     long shared_block_offset() const override { return 9L * C; }
     long shared_block_floats() const override { return 3L * P; }
     int shared_split_slots() const override { return thallo_hip_ba_apply2_camera_slots(C, P); }

@@ -4,6 +4,7 @@
 // fused MI355X schedule documented in DESIGN.md.
 #pragma once
 #include "plugin.hpp"
+#include "ba_reduced.hpp"
 #include "rccl_transport.hpp"
 #include "../../include/Thallo.h"
 
@@ -160,7 +161,7 @@ public:
     const char* schedule_name();          // the plugin's, and the opt-in forms that run (before the first Init: that were asked for)
     // ThalloX_PlanSetLinearSolver: THALLOX_SOLVER_PCG (default), THALLOX_SOLVER_SCHUR_PCG, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG or THALLOX_SOLVER_SCHUR_DENSE; takes effect at the next Init.  0 = ok
     int  set_linear_solver(int kind);
-    int  schur_blocks() const { return schur_on_ && schur_explicit_ ? (int)schur_blocks_ : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
+    int  schur_blocks() const { return schur_assembled() ? (int)reduced()->blocks() : -1; }      // stored blocks of the assembled S (-1: the assembled form does not run)
     int  schur_held_points();             // points the last step's elimination held fixed (-1: the Schur form does not run)
     int  schur_dense_nonpositive();       // scalars of the last dense factor whose diagonal of S was not positive (identity rows; -1: the dense form does not run)
     // ThalloX_PlanSetHeldUnknowns: the mask of one Unknown (host bytes in the caller's ids, nonzero = that scalar is a constant of the solve; NULL clears it); takes effect
@@ -362,25 +363,28 @@ private:
     unsigned* block_status_ = nullptr;
     int   block_prepare();                              // Init: the regions and the buffers
     // ---- the two-level preconditioner on the assembled S (ba_coarse.hip): M^-1 = G^T G + P Z^T Z P^T.  Asked for by kind 2 of set_preconditioner (block_want_ goes with
-    // it), runs on kind 2 of the linear solver alone; the aggregates and every coarse buffer are the plugin's, built and allocated with the structure of S
-    bool coarse_want_ = false, coarse_on_ = false;
+    // it), runs on kind 2 of the linear solver alone; the aggregates and every coarse buffer are the reduced system's, built and allocated with the structure of S
+    bool coarse_want_ = false;
     int  coarse_k_ = 0;                                 // cameras per aggregate asked for (0: the default)
     std::vector<int> coarse_agg_;                       // ... or the caller's aggregates (empty: greedy)
     // z += the coarse term of M^-1 r behind the launch that left z = G^T G r and nb partials of r . z in `part`: the partials of |Z P^T r|^2 go behind them, so every reader
     // of the slot adds r . z_B + |y|^2 in one fixed order -> the slot's partial count (nb itself where the form does not run), or a negative code
     int   coarse_apply(float* part, int nb, const unsigned* gate);
     // ---- Schur complement on the cameras (ba_schur.hip): PCG on the 9 C camera unknowns, the points eliminated through their blocks.  H, G (the camera blocks: the
-    // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, g and the held count are its own
+    // preconditioner of S) and the status word are the block preconditioner's; the elimination factor, y, the held count and every buffer of the assembled, dense and
+    // two-level forms are the plugin's reduced system's (ba_reduced.hpp), which also answers what runs since the last Init; g is the plan's, a solver vector
     bool schur_want_ = false, schur_on_ = false;
-    bool schur_explicit_want_ = false, schur_explicit_ = false;      // kind 2 (asked for / running since the last Init): S assembled once per step by the plugin (ba_schur_explicit.hip), the loop's applies multiply by it
-    long schur_blocks_ = -1;                            // ... its stored blocks, known at Init
-    bool schur_dense_want_ = false, schur_dense_ = false;      // kind 3 (asked for / running since the last Init): kind 2's structure and assembly, and a dense Cholesky factor of S in place of the reduced PCG loop (ba_schur_dense.hip)
+    bool schur_explicit_want_ = false;                  // kind 2 asked for: S assembled once per step (ba_schur_explicit.hip), the loop's applies multiply by it
+    bool schur_dense_want_ = false;                     // kind 3 asked for: kind 2's structure and assembly, and a dense Cholesky factor of S in place of the reduced PCG loop (ba_schur_dense.hip)
+    ReducedCameraSystem* reduced() const { return plugin->reduced_system(); }      // non-NULL wherever schur_on_
+    bool  schur_assembled() const { return schur_on_ && reduced()->assembled(); }
+    bool  schur_dense() const { return schur_on_ && reduced()->dense_n() >= 0; }
+    bool  coarse_on() const { return schur_on_ && reduced()->coarse_n() >= 0; }
     bool  schur_dense_step(const float* g);             // expand, factor, delta_c = S^-1 g, the read-back of the factor's info word; false: the error is set, nothing was applied
     void  schur_dense_pivot_error(int index, const char* where);
     long schur_n_ = 0, schur_hp_off_ = 0, schur_pt_off_ = 0;      // camera unknowns; the point blocks' place in H; the points' place in the flat vector
-    float *schur_Ge_ = nullptr, *schur_y_ = nullptr, *schur_g_ = nullptr;
-    unsigned* schur_held_ = nullptr;
-    int   schur_prepare();                              // Init: the buffers
+    float* schur_g_ = nullptr;
+    int   schur_prepare();                              // Init: the offsets, the reduced system's configure, g
     // ---- Levenberg-Marquardt: step_lm = lm_setup, one of five PCG loops (lm_schedule), lm_finish
     enum class LmSchedule { Reference, OneKernel, OneKernelSlab, Resident, Blocks };
     // Between the LM state reset and the end of the PCG loop the plugin's launches are gated on the state's gate word (the zeta test on the device); whichever way

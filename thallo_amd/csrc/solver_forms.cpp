@@ -34,8 +34,6 @@ int Plan::forms_prepare()
     robust_on_ = robust_want_; robust_on_scale_ = robust_want_scale_;
     block_on_ = false;
     schur_on_ = false;
-    schur_dense_ = false;
-    coarse_on_ = false;
     if (coarse_want_ && !(schur_want_ && schur_explicit_want_)) {
         set_error("%s: the two-level preconditioner (ThalloX_PlanSetPreconditioner THALLOX_PRECOND_TWO_LEVEL) needs the assembled reduced camera matrix: set "
                   "ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG); this plan's linear solver is %s", plugin->name(),
@@ -43,7 +41,7 @@ int Plan::forms_prepare()
         return -1;
     }
     if (schur_want_) { if (schur_prepare()) return -1; schur_on_ = true; }      // (its preconditioner is the camera blocks whatever block_want_ says)
-    else if (schur_explicit_) { (void)plugin->schur_explicit(false); schur_explicit_ = false; }      // (a plan that ran the assembled form and was switched back: its structure goes, the dense matrix with it)
+    else if (ReducedCameraSystem* rs = reduced()) rs->retire();      // (a plan that ran the assembled form and was switched back: its structure goes, the dense matrix with it)
     if (!schur_want_ && block_want_) { if (block_prepare()) return -1; block_on_ = true; }
     if (schur_on_ || block_on_) { precond_regions_ = block_regions_; if (schur_on_) precond_regions_.n = 1; }      // (Schur: the camera region alone)
     return 0;
@@ -70,9 +68,10 @@ int Plan::forms_setup(const float* shift, const float* b, float* rz_out, int nb,
     { TimedLaunch t(ctx, "BlockFactor"); if ((rc = thallo_hip_block_factor(precond_regions_, block_H_, shift, v_.pre, block_G_, block_status_, s)) < 0) return rc; }
     if (held_on()) { TimedLaunch t(ctx, "BlockHoldFactor"); if ((rc = thallo_hip_block_hold_factor(precond_regions_, held_mask_, block_G_, s)) < 0) return rc; }
     if (schur_on_) {
-        if ((rc = plugin->schur_reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, schur_Ge_, schur_held_, b, schur_y_, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
-        if (schur_explicit_ && (rc = plugin->schur_assemble(ctx, block_H_, schur_Ge_, shift)) < 0) return rc;
-        if (coarse_on_ && !schur_empty() && (rc = plugin->coarse_setup(ctx, held_on() ? held_mask_ : nullptr)) < 0) { what = "two-level preconditioner set-up"; return rc; }
+        ReducedCameraSystem& rs = *reduced();
+        if ((rc = rs.reduce(ctx, block_H_ + schur_hp_off_, shift ? shift + schur_pt_off_ : nullptr, b, schur_g_, v_.r, held_on() ? held_mask_ : nullptr)) < 0) return rc;
+        if (rs.assembled() && (rc = rs.assemble(ctx, block_H_, shift)) < 0) return rc;
+        if (coarse_on() && !schur_empty() && (rc = rs.coarse_setup(ctx, held_on() ? held_mask_ : nullptr)) < 0) { what = "two-level preconditioner set-up"; return rc; }
     }
     { TimedLaunch t(ctx, "BlockApply"); rc = thallo_hip_block_apply(precond_regions_, block_G_, v_.r, v_.z, rz_out, nullptr, s); }
     return coarse_apply(rz_out, rc, nullptr);
@@ -80,9 +79,9 @@ int Plan::forms_setup(const float* shift, const float* b, float* rz_out, int nb,
 
 int Plan::coarse_apply(float* part, int nb, const unsigned* gate)
 {
-    if (!coarse_on_ || schur_empty() || nb < 0) return nb;
+    if (!coarse_on() || schur_empty() || nb < 0) return nb;
     if (nb + THALLO_HIP_COARSE_PARTIALS > THALLO_HIP_MAX_PARTIALS) return -(int)hipErrorInvalidValue;
-    const int nc = plugin->coarse_apply(ctx, held_on() ? held_mask_ : nullptr, v_.r, v_.z, part + nb, gate);
+    const int nc = reduced()->coarse_apply(ctx, held_on() ? held_mask_ : nullptr, v_.r, v_.z, part + nb, gate);
     return nc < 0 ? nc : nb + nc;
 }
 
@@ -93,11 +92,11 @@ int Plan::coarse_apply(float* part, int nb, const unsigned* gate)
 // PCGLinearUpdate then adds the complete delta.
 int Plan::step_gn_blocks(int ev_iter)
 {
-    const int L = schur_empty() || schur_dense_ ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
+    const int L = schur_empty() || schur_dense() ? 0 : sp.lIterations, B = 2;   // slot layout: alphaN_k = B+2k, alphaD_k = B+2k+1, betaN_k = B+2k+2
     hipStream_t s = ctx.stream;
     int ev_lin, nb;
     if (!gn_begin(ev_iter, ev_lin)) return 0;
-    if (schur_dense_ && !schur_dense_step(schur_g_)) return 0;      // (delta_c is in place, or the factor failed: nothing has been applied)
+    if (schur_dense() && !schur_dense_step(schur_g_)) return 0;      // (delta_c is in place, or the factor failed: nothing has been applied)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         const PrevAlpha a = prev_alpha(k);
@@ -105,7 +104,7 @@ int Plan::step_gn_blocks(int ev_iter)
             {   TimedLaunch t(ctx, "PCGStep3");
                 nb = thallo_hip_pcg_pupdate(v_.z, v_.p[cur_], v_.p[cur_ ^ 1], v_.delta, schur_n_, k == 0 ? 1 : 0, a.aN, a.aD, sum(jN), s); }
             if (nb < 0) { set_error("PCGStep3 launch failed (%d)", nb); return 0; }
-            nb = plugin->schur_apply(ctx, schur_Ge_, v_.p[cur_ ^ 1], gn_shift(), v_.Ap, slot(jD), nullptr);
+            nb = reduced()->apply(ctx, v_.p[cur_ ^ 1], gn_shift(), v_.Ap, slot(jD), nullptr);
             if (nb < 0) { set_error("Schur apply launch failed (%d)", nb); return 0; }
         } else {
             nb = gn_step1(k, a, sum(jN), slot(jD));
@@ -120,7 +119,7 @@ int Plan::step_gn_blocks(int ev_iter)
     }
     if (schur_on_) {
         const int jL = B + 2 * (L - 1);
-        nb = plugin->schur_back(ctx, schur_Ge_, v_.r, v_.delta, L > 0 ? v_.p[cur_] : nullptr, sum(L > 0 ? jL : B), sum(L > 0 ? jL + 1 : B));
+        nb = reduced()->back(ctx, v_.r, v_.delta, L > 0 ? v_.p[cur_] : nullptr, sum(L > 0 ? jL : B), sum(L > 0 ? jL + 1 : B));
         if (nb < 0) { set_error("Schur back-substitution launch failed (%d)", nb); return 0; }
     }
     const int ev_fin = gn_finish(L, ev_lin);
@@ -137,19 +136,19 @@ void Plan::lm_loop_blocks(LmStep& st)
 {
     hipStream_t s = st.s;
     const bool schur = schur_on_;
-    const int L = schur_empty() || schur_dense_ ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
+    const int L = schur_empty() || schur_dense() ? 0 : st.L, B = st.B, QS = st.QS, T0 = st.T0, T1 = st.T1;
     const long n = schur ? schur_n_ : v_.n;
     const float* b = schur ? schur_g_ : v_.b;
     float* p = v_.p[0];
     auto apply = [&](const float* x, float* Ax, float* xAx_out) {      // (S + CtC_c) x or (J^T J + CtC) x ; the partials of x . that
-        if (schur) return plugin->schur_apply(ctx, schur_Ge_, x, lm_shift(), Ax, xAx_out, ctx.gate);
+        if (schur) return reduced()->apply(ctx, x, lm_shift(), Ax, xAx_out, ctx.gate);
         ctx.lm_ctc = lm_shift();
         const int rc = plugin->apply_jtj(ctx, x, Ax, xAx_out);
         ctx.lm_ctc = nullptr;
         return rc;
     };
     int nb = 0;
-    if (schur_dense_ && !schur_dense_step(schur_g_)) { st.failed = true; return; }      // (S carries the step's CtC: each step factors anew)
+    if (schur_dense() && !schur_dense_step(schur_g_)) { st.failed = true; return; }      // (S carries the step's CtC: each step factors anew)
     for (int k = 0; k < L; ++k) {
         const int jN = B + 2 * k, jD = jN + 1, jB = jN + 2;
         {   TimedLaunch t(ctx, "PCGStep3");                   // p = z + beta p  (k = 0: p = z)
@@ -191,7 +190,7 @@ void Plan::lm_loop_blocks(LmStep& st)
     }
     if (!schur) return;
     const thallo_sum_t none = { nullptr, 0 };
-    st.check(plugin->schur_back(ctx, schur_Ge_, v_.b, v_.delta, nullptr, none, none), "Schur back-substitution launch");
+    st.check(reduced()->back(ctx, v_.b, v_.delta, nullptr, none, none), "Schur back-substitution launch");
 }
 
 const char* Plan::schedule_name()
@@ -199,16 +198,16 @@ const char* Plan::schedule_name()
     std::string& t = schedule_text_;
     t = plugin->schedule_name();
     if (schur_on_ || schur_want_) {
-        if (schur_on_ ? schur_explicit_ : schur_explicit_want_) {
+        if (schur_on_ ? schur_assembled() : schur_explicit_want_) {
             t += "; Schur complement on the cameras, assembled";
-            if (schur_on_ && schur_blocks_ >= 0) t += " (" + std::to_string(schur_blocks_) + " blocks)";
+            if (schur_on_) t += " (" + std::to_string(reduced()->blocks()) + " blocks)";
         } else t += "; Schur complement on the cameras";
-        if (schur_on_ ? schur_dense_ : schur_dense_want_) {
+        if (schur_on_ ? schur_dense() : schur_dense_want_) {
             t += "; dense Cholesky of S";
-            if (schur_on_ && plugin->schur_dense_n() >= 0) t += " (n = " + std::to_string(plugin->schur_dense_n()) + ")";
-        } else if (schur_on_ ? coarse_on_ : coarse_want_ && schur_explicit_want_) {
+            if (schur_on_) t += " (n = " + std::to_string(reduced()->dense_n()) + ")";
+        } else if (schur_on_ ? coarse_on() : coarse_want_ && schur_explicit_want_) {
             t += "; two-level on S";
-            if (schur_on_) t += " (" + std::to_string(plugin->coarse_aggregates()) + " aggregates, n_c = " + std::to_string(plugin->coarse_n()) + ")";
+            if (schur_on_) t += " (" + std::to_string(reduced()->coarse_aggregates()) + " aggregates, n_c = " + std::to_string(reduced()->coarse_n()) + ")";
         } else t += "; block-Jacobi on S";
     } else if (block_on_ || block_want_) t += "; block-Jacobi preconditioner (unfused PCG loop)";
     const int kind = ready_ ? robust_on_ : robust_want_;      // (since the last Init: what runs; before it: what was asked for)
@@ -396,8 +395,9 @@ int Plan::set_preconditioner(int kind)
 int Plan::set_coarse_aggregates(int k, const int* agg, long n)
 {
     if (!ok_) return -1;
-    const long C_ = plugin->cov_elements(0);
-    if (!plugin->schur_ok() || C_ < 0) { set_error("%s: no two-level preconditioner for this energy (its plugin assembles no reduced matrix; bundle_adjustment does)", plugin->name()); return -1; }
+    const ReducedCameraSystem* rs = reduced();
+    const long C_ = rs ? rs->elements(0) : -1;
+    if (!rs) { set_error("%s: no two-level preconditioner for this energy (its plugin assembles no reduced matrix; bundle_adjustment does)", plugin->name()); return -1; }
     if (!agg) {
         if (k < 0 || n != 0) { set_error("%s: coarse aggregates: cameras_per_aggregate must be >= 0 (0: the default) and n = 0 without an array (got %d, n = %ld)", plugin->name(), k, n); return -1; }
         coarse_k_ = k; coarse_agg_.clear();
@@ -419,10 +419,10 @@ int Plan::set_coarse_aggregates(int k, const int* agg, long n)
 
 int Plan::coarse_space(long out[4])
 {
-    if (!ok_ || !ready_ || !coarse_on_ || !out) return -1;
+    if (!ok_ || !ready_ || !coarse_on() || !out) return -1;
     unsigned w[3] = { 0, 0, 0 };
-    if (hipMemcpyAsync(w, plugin->coarse_words(), sizeof(w), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
-    out[0] = plugin->coarse_aggregates(); out[1] = plugin->coarse_n(); out[2] = (long)w[1]; out[3] = (long)w[2];
+    if (hipMemcpyAsync(w, reduced()->coarse_words(), sizeof(w), hipMemcpyDeviceToHost, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess) return -1;
+    out[0] = reduced()->coarse_aggregates(); out[1] = reduced()->coarse_n(); out[2] = (long)w[1]; out[3] = (long)w[2];
     return 0;
 }
 
@@ -456,7 +456,7 @@ int Plan::set_linear_solver(int kind)
         else set_error("%s: a direct-solve plan has no PCG loop to run on %s Schur complement", plugin->name(), ex ? "an assembled" : "a");
         return -1;
     }
-    if (!plugin->schur_ok() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
+    if (!reduced() || !plugin->block_precond_ok()) { set_error("%s: no %s for this energy (its plugin eliminates nothing; bundle_adjustment does)", plugin->name(), what); return -1; }
     if (dist_) { set_error("%s: the %s runs on one GPU (this plan is distributed)", plugin->name(), what); return -1; }
     schur_want_ = true; schur_explicit_want_ = ex; schur_dense_want_ = dense;
     return 0;
@@ -464,55 +464,45 @@ int Plan::set_linear_solver(int kind)
 
 int Plan::schur_prepare()
 {
-    if (refuse_unless_one_gpu_pcg(plugin->schur_ok(), "the Schur-complement solve needs")) return -1;
+    if (refuse_unless_one_gpu_pcg(reduced() != nullptr, "the Schur-complement solve needs")) return -1;
     if (block_prepare()) return -1;                      // H, G, the status word (G's camera region: the preconditioner of S)
     if (block_regions_.n != 2 || block_regions_.r[0].offset != 0) { set_error("%s: the Schur-complement solve needs two block regions, the kept one first", plugin->name()); return -1; }
     thallo_block_regions_t cameras = block_regions_; cameras.n = 1;
     schur_n_ = (long)block_regions_.r[0].size * block_regions_.r[0].count;
     schur_hp_off_ = thallo_hip_block_floats(cameras);
     schur_pt_off_ = block_regions_.r[1].offset;
-    // the assembled form: the structure of S, sized and checked against its budget before it is allocated
-    schur_explicit_ = false;
-    plugin->schur_dense_want(schur_dense_want_);      // (the dense matrix is sized, refused, allocated and freed with the structure)
-    const bool coarse = coarse_want_ && schur_explicit_want_ && !schur_dense_want_;      // (the dense form ignores the preconditioner)
-    plugin->coarse_want(coarse, coarse_k_, coarse && !coarse_agg_.empty() ? coarse_agg_.data() : nullptr);      // (... and the coarse matrices likewise)
-    schur_blocks_ = plugin->schur_explicit(schur_explicit_want_);
-    if (schur_explicit_want_ && schur_blocks_ < 0) return -1;
-    schur_explicit_ = schur_explicit_want_;
-    coarse_on_ = coarse && plugin->coarse_n() >= 0;
-    if (coarse && !coarse_on_) { set_error("%s: the two-level preconditioner is not available for this energy", plugin->name()); return -1; }
-    schur_dense_ = schur_dense_want_ && plugin->schur_dense_n() >= 0;
-    if (schur_dense_want_ && !schur_dense_) { set_error("%s: the dense Cholesky Schur-complement solve is not available for this energy", plugin->name()); return -1; }
-    if (schur_Ge_) return 0;
-    const size_t np = (size_t)block_regions_.r[1].count, ns = (size_t)block_regions_.r[1].size;
-    schur_Ge_ = (float*)device_alloc((ns * (ns + 1) / 2 * np + 64) * sizeof(float)); schur_y_ = (float*)device_alloc((ns * np + 64) * sizeof(float));
-    schur_g_ = (float*)device_alloc(((size_t)v_.n_alloc + 64) * sizeof(float)); schur_held_ = (unsigned*)device_alloc(64);
-    if (!schur_Ge_ || !schur_y_ || !schur_g_ || !schur_held_) {
-        schur_Ge_ = schur_y_ = schur_g_ = nullptr; schur_held_ = nullptr;
-        set_error("%s: out of device memory for the Schur-complement solve", plugin->name()); return -1;
-    }
+    // the reduced system's forms: the structure of S with the dense triangle or the coarse matrices, sized and checked against its budget before it is allocated; behind
+    // it the elimination factor and y, then g
+    ReducedCameraSystem::Want want;
+    want.assembled = schur_explicit_want_; want.dense = schur_dense_want_;
+    want.two_level = coarse_want_ && schur_explicit_want_ && !schur_dense_want_;      // (the dense form ignores the preconditioner)
+    want.cameras_per_aggregate = coarse_k_;
+    want.aggregates = want.two_level && !coarse_agg_.empty() ? coarse_agg_.data() : nullptr;
+    if (reduced()->configure(want)) return -1;
+    if (schur_g_) return 0;
+    if (!(schur_g_ = (float*)device_alloc(((size_t)v_.n_alloc + 64) * sizeof(float)))) { set_error("%s: out of device memory for the Schur-complement solve", plugin->name()); return -1; }
     return 0;
 }
 
-int Plan::schur_held_points() { return schur_on_ && schur_held_ ? read_word(schur_held_) : -1; }
+int Plan::schur_held_points() { return schur_on_ ? read_word(reduced()->held_word()) : -1; }
 
 // ------------------------------------------------------------------ dense Cholesky of S (ba_schur_dense.hip, DESIGN.md "Dense Cholesky Schur solve")
-int Plan::schur_dense_nonpositive() { return schur_on_ && schur_dense_ && plugin->schur_dense_words() ? read_word(plugin->schur_dense_words() + 1) : -1; }
+int Plan::schur_dense_nonpositive() { return schur_dense() ? read_word(reduced()->dense_words() + 1) : -1; }
 
 void Plan::schur_dense_pivot_error(int index, const char* where)
 {
     set_error("%s: %sthe dense Cholesky factor of the reduced camera matrix met a pivot that is not positive at camera %d, scalar %d (index %d of %ld): the system is singular or "
               "indefinite in float32 -- fix the gauge with ThalloX_PlanSetHeldUnknowns (hold) or use Levenberg-Marquardt (ThalloX_EnableLM)", plugin->name(), where, index / 9, index % 9, index,
-              plugin->schur_dense_n());
+              reduced()->dense_n());
 }
 
 // One step's dense solve behind forms_setup: expand, factor, delta_c = D L^-T L^-1 D g into the camera part of delta.  The step's ONE extra read-back sits here, behind
 // the solve's launch and in front of the back-substitution: a failed factor ends the step before anything is applied to the unknowns.  false: the error is set
 bool Plan::schur_dense_step(const float* g)
 {
-    const int rc = plugin->schur_dense_solve(ctx, held_on() ? held_mask_ : nullptr, g, v_.delta);
+    const int rc = reduced()->dense_solve(ctx, held_on() ? held_mask_ : nullptr, g, v_.delta);
     if (rc < 0) { set_error("%s: the dense Cholesky Schur-complement solve failed to launch (%d)", plugin->name(), rc); return false; }
-    const int info = read_word(plugin->schur_dense_words());
+    const int info = read_word(reduced()->dense_words());
     if (info < 0) { set_error("%s: cannot read the dense Cholesky factor's status word", plugin->name()); return false; }
     if (info > 0) { schur_dense_pivot_error(info - 1, ""); return false; }
     return true;
@@ -529,22 +519,22 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     if (!ok_) return -1;
     const char* e = plugin->name();
     if (plugin->direct_solve()) { set_error("%s: a direct-solve plan has no assembled Schur complement to take a covariance from", e); return -1; }
-    if (!plugin->schur_ok() || plugin->cov_elements(0) < 0) { set_error("%s: no covariance for this energy (its plugin eliminates nothing and assembles no reduced matrix; bundle_adjustment does)", e); return -1; }
+    if (!reduced()) { set_error("%s: no covariance for this energy (its plugin eliminates nothing and assembles no reduced matrix; bundle_adjustment does)", e); return -1; }
     if (dist_) { set_error("%s: the covariance runs on one GPU (this plan is distributed)", e); return -1; }
     if (!ready_) { set_error("%s: ThalloX_PlanCovariance before Thallo_ProblemInit: the covariance is taken at the unknowns of an initialised plan", e); return -1; }
-    if (!schur_on_ || !schur_explicit_) {
+    if (!schur_assembled()) {
         set_error("%s: the plan's last Init did not run the assembled Schur-complement solve: set ThalloX_PlanSetLinearSolver(plan, THALLOX_SOLVER_SCHUR_EXPLICIT_PCG) before Thallo_ProblemInit "
                   "(columns by PCG), or THALLOX_SOLVER_SCHUR_DENSE (columns through a dense Cholesky factor)", e);
         return -1;
     }
-    const long elems = plugin->cov_elements(input);
+    const long elems = reduced()->elements(input);
     if (elems < 0) { set_error("%s: input %d is not an Unknown of this energy", e, input); return -1; }
     if (n <= 0 || !ids || !host_out) { set_error("%s: a covariance needs n > 0 ids and an output array (n = %ld)", e, n); return -1; }
     const float rel_tol = opt ? opt->rel_tol : 1e-6f;
     const int max_it = opt ? opt->max_iterations : 500;
-    if (schur_dense_) {}      // (the dense form accepts and ignores both)
+    if (schur_dense()) {}      // (the dense form accepts and ignores both)
     else if (!(rel_tol > 0.0f) || !std::isfinite(rel_tol)) { set_error("%s: the covariance's rel_tol must be finite and positive (got %g)", e, (double)rel_tol); return -1; }
-    if (!schur_dense_ && max_it < 1) { set_error("%s: the covariance's max_iterations must be at least 1 (got %d)", e, max_it); return -1; }
+    if (!schur_dense() && max_it < 1) { set_error("%s: the covariance's max_iterations must be at least 1 (got %d)", e, max_it); return -1; }
     {   std::vector<char> seen((size_t)elems, 0);
         for (long i = 0; i < n; ++i) {
             if (ids[i] < 0 || ids[i] >= elems) { set_error("%s: covariance id %d (at %ld) is out of range: input %d has %ld elements", e, ids[i], i, input, elems); return -1; }
@@ -560,13 +550,13 @@ long Plan::covariance(void** params, int input, const int* ids, long n, float* h
     const char* what = nullptr;
     if ((nb = forms_setup(gn_shift(), v_.r, slot(2), nb, what)) < 0) { set_error("%s: covariance: %s failed (%d)", e, what, nb); return -1; }
     thallo_cov_info_t ci;
-    if (schur_dense_) {      // expand and factor once per call, then every batch through two triangular sweeps: iterations 0, worst residual 0
+    if (schur_dense()) {      // expand and factor once per call, then every batch through two triangular sweeps: iterations 0, worst residual 0
         int pivot = -1;
-        const int rc = plugin->covariance_dense(ctx, input, ids, n, block_G_, schur_Ge_, held_on() ? held_mask_ : nullptr, host_out, &ci, &pivot);
+        const int rc = reduced()->covariance_dense(ctx, input, ids, n, block_G_, held_on() ? held_mask_ : nullptr, host_out, &ci, &pivot);
         if (rc == -2) { schur_dense_pivot_error(pivot, "covariance: "); return -2; }
         if (rc) return -1;
     } else
-    if (plugin->covariance(ctx, input, ids, n, block_G_, schur_Ge_, held_on() ? held_mask_ : nullptr, rel_tol, max_it, host_out, &ci)) return -1;
+    if (reduced()->covariance(ctx, input, ids, n, block_G_, held_on() ? held_mask_ : nullptr, rel_tol, max_it, host_out, &ci)) return -1;
     if (info) { info->iterations = ci.iterations; info->columns = ci.columns; info->not_converged = ci.not_converged; info->nan_blocks = ci.nan_blocks; info->worst_residual = ci.worst; }
     return ci.not_converged;
 }
