@@ -206,6 +206,14 @@ int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t ter
    bits of thallo_hip_linear_update_n on a delta of stored zeros, without the pass that stores them and the pass that reads them back.  X == NULL: delta is
    written (whatever it held before); X != NULL: delta is neither read nor written. */
 int thallo_hip_linear_update_n_from_zero(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream);
+/* Every term of a GN step in ONE launch: the running value starts at 0.0f and takes alpha_0 p_0, alpha_1 p_1, ... (count <= THALLO_HIP_MAX_STEP_TERMS, oldest
+   first, one fma each) -- the bits of thallo_hip_linear_update_n_from_zero followed by thallo_hip_linear_update_n per further 32 terms, without delta's round
+   trips in between.  X != NULL: X += the sum, delta is neither read nor written (it may be NULL); X == NULL: delta = the sum.  `terms` is a host array, copied
+   into the launch's argument block.  Only the first THALLO_HIP_MAX_UPDATE_TERMS terms may carry lists of partials (alphaN_0 does: PCGInit1 leaves partials);
+   behind them every alpha is a pair of single words, anything else is refused (-hipErrorInvalidValue, nothing launched), as is count > THALLO_HIP_MAX_STEP_TERMS. */
+#define THALLO_HIP_MAX_STEP_TERMS 128
+typedef struct { const float* p; thallo_sum_t alphaN, alphaD; } thallo_update_term_t;
+int thallo_hip_linear_update_all(float* X, float* delta, const thallo_update_term_t* terms, int count, long len, int max_workgroups, thallo_stream_t stream);
 /* Known-answer test of the wave64 primitives of the generated kernels (ballot, peer grouping by key, grouped sums: thallo.t:3380-3399 / cuda_util.t:334-427 for 64-wide waves),
    the reference's tests/cuda_unit_tests/{ballot,get_peers,reduce_peers}.t restated for 64 lanes; one wave, compiled from the generated kernels' own prelude with hipRTC:
    out_ballot = max over lanes of ballot(lane != 0) = 0xFFFFFFFFFFFFFFFE; out_peers = sum over lanes of (peer mask of key lane % 4) & 0xFF = 255 * 64 / 4;
@@ -270,7 +278,10 @@ int thallo_hip_lapimg_pcg_step1(int W, int H, float w_fit, int xguard,
  * `irregular` (device int, may be NULL): pcg_init stores the number of pixels of the owned rows whose right/down UrShape
  * neighbours (inside the local image) are NOT at exact unit offsets; when it is 0 (UrShape = the pixel grid, which is what the reference's harness always
  * passes: CombinedSolver.h:158-176) pcg_step1 / apply_jtj skip the UrShape plane (-8 B/pixel); the bits of the
- * result are the same either way. */
+ * result are the same either way.
+ * pcg_init: pre, z, p_prev and delta may each be NULL and are then not stored (a caller whose loop reads none of them: the marching one-kernel
+ * iteration takes M^-1 from the flags, forms p_0 = M^-1 r_0 in its first launch and starts delta's first update from 0.0f); everything else the call leaves
+ * -- r, cs, flags, the alphaN partials, the irregular word -- is the same bits. */
 int thallo_hip_iw_cost(int W, int H, int row0, int row1, const float* offset, const float* angle, const float* urshape,
                        const float* constraints, const float* mask, float w_fit, float w_reg,
                        float* cost_out, thallo_stream_t stream);

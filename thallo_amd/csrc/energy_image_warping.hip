@@ -364,7 +364,7 @@ __global__ __launch_bounds__(BLOCK) void k_step2_iw_rows(float* __restrict__ r, 
 }
 
 // ------------------------------------------------------------------------------------------ PCGInit1 (+_Finish)
-// Once per GN iteration: evalJTF in gather form, guardedInvert, z = M^-1 r, p_prev = 0, delta = 0 (unless delta == NULL), the
+// Once per GN iteration: evalJTF in gather form, guardedInvert, z = M^-1 r, p_prev = 0, delta = 0 (each unless its pointer is NULL), the
 // (cos,sin) and validity planes, alphaN partials.  Not pipelined (1 % of a GN iteration).
 __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict__ off, const float* __restrict__ ang,
                                                 const float2* __restrict__ ur, const float2* __restrict__ cons,
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict_
                 if ((gy < g.row0 || gy >= g.row1) && lx >= 1 && lx <= TW) {
                     // ghost row of a slab: the step kernel reads these planes as halo
                     cs[pix] = make_float2(cc, ss); flags[pix] = ff;
-                    reinterpret_cast<float2*>(p_prev)[pix] = make_float2(0.f, 0.f); p_prev[2 * N + pix] = 0.f;
+                    if (p_prev) { reinterpret_cast<float2*>(p_prev)[pix] = make_float2(0.f, 0.f); p_prev[2 * N + pix] = 0.f; }
                 }
             }
             T.px[idx] = ox; T.py[idx] = oy; T.c[idx] = cc; T.s[idx] = ss; T.ux[idx] = uxx; T.uy[idx] = uyy; T.f[idx] = ff;
@@ -455,10 +455,11 @@ __global__ __launch_bounds__(BLOCK) void k_init(Geo g, const float2* __restrict_
                     reinterpret_cast<float2*>(diag_out)[pix] = make_float2(dgo_raw, dgo_raw); diag_out[2 * N + pix] = dga_raw;
                 }
                 reinterpret_cast<float2*>(r)[pix] = make_float2(rx, ry);  r[2 * N + pix] = ra;
-                reinterpret_cast<float2*>(pre)[pix] = make_float2(mx, my); pre[2 * N + pix] = ma;
+                // (pre, z, p_prev == NULL: the caller's loop reads none of them -- the marching kernels take M^-1 from the flags and form p_0 = M^-1 r_0 themselves)
+                if (pre) { reinterpret_cast<float2*>(pre)[pix] = make_float2(mx, my); pre[2 * N + pix] = ma; }
                 const float zx = mx * rx, zy = my * ry, zaa = ma * ra;
-                reinterpret_cast<float2*>(z)[pix] = make_float2(zx, zy);  z[2 * N + pix] = zaa;
-                reinterpret_cast<float2*>(p_prev)[pix] = make_float2(0.f, 0.f); p_prev[2 * N + pix] = 0.f;
+                if (z) { reinterpret_cast<float2*>(z)[pix] = make_float2(zx, zy);  z[2 * N + pix] = zaa; }
+                if (p_prev) { reinterpret_cast<float2*>(p_prev)[pix] = make_float2(0.f, 0.f); p_prev[2 * N + pix] = 0.f; }
                 if (delta) { reinterpret_cast<float2*>(delta)[pix] = make_float2(0.f, 0.f);  delta[2 * N + pix] = 0.f; }      // (NULL: the caller's first update of delta starts from 0.0f itself)
                 cs[pix] = make_float2(T.c[i], T.s[i]);
                 flags[pix] = fl;

@@ -44,7 +44,9 @@ struct RawD { float4 dlo, ppo; float2 dla, ppa; };     // delta and p_{k-2} of t
 template <bool FIRST>
 __device__ __forceinline__ void take(Raw<FIRST>& d, const Raw<FIRST>& s)      // 23 moves per row (iw_march.hpp: take1)
 {
-    take4(d.ro, s.ro); take2(d.ra, s.ra); take4(d.po, s.po); take2(d.pa, s.pa); take4(d.cs, s.cs); take1(d.f, s.f);
+    take4(d.ro, s.ro); take2(d.ra, s.ra);
+    if (!FIRST) { take4(d.po, s.po); take2(d.pa, s.pa); }      // (a GN step's first launch: beta = 0, neither p_{k-1} nor A p_{k-1} is loaded)
+    take4(d.cs, s.cs); take1(d.f, s.f);
     if (!FIRST) { take4(d.ao, s.ao); take2(d.aa, s.aa); }
 }
 template <int DMODE>
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
         const long i2 = (long)tc * W2 + (xc >> 1);
         s.ro = ldf4(ro4 + i2, nt_ra); s.ra = ldf2(ra2 + i2, nt_ra);
         if (!FIRST) { s.ao = ldf4(ao4 + i2, nt_ra); s.aa = ldf2(aa2 + i2, nt_ra); }
-        s.po = ldf4(po4 + i2, nt_pin); s.pa = ldf2(pa2 + i2, nt_pin);
+        if (!FIRST) { s.po = ldf4(po4 + i2, nt_pin); s.pa = ldf2(pa2 + i2, nt_pin); }
         s.cs = ldf4(cs4 + i2, nt_const);
         // the aligned dword that holds the pair's two flag bytes (publish shifts): a 16-bit load would leave a zero-extension of the
         // raw value for the compiler to place -- it places it at the loop latch, behind a wait for the fresh load
@@ -167,14 +169,17 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
             rx[1] = __builtin_fmaf(-alpha, s.ao.z, rx[1]); ry[1] = __builtin_fmaf(-alpha, s.ao.w, ry[1]);
             rq[0] = __builtin_fmaf(-alpha, s.aa.x, rq[0]); rq[1] = __builtin_fmaf(-alpha, s.aa.y, rq[1]);
         }
-        const float ppx[2] = { s.po.x, s.po.z }, ppy[2] = { s.po.y, s.po.w }, ppq[2] = { s.pa.x, s.pa.y };
+        // FIRST: p_in is not read.  Its term was beta * 0 = +0.0f on the zeros PCGInit1 stored: p_0 = fma(M^-1, r_0, +0.0f), NOT the bare product -- an inactive
+        // pixel has r_0 = -0.0f, and its p_0 stays +0.0f
+        const float ppx[2] = { FIRST ? 0.f : s.po.x, FIRST ? 0.f : s.po.z }, ppy[2] = { FIRST ? 0.f : s.po.y, FIRST ? 0.f : s.po.w }, ppq[2] = { FIRST ? 0.f : s.pa.x, FIRST ? 0.f : s.pa.y };
         // outside the image / beyond the segment: inactive pixels (M^-1 = 0, p = 0)
         const unsigned fl = ok ? (s.f >> (((((long)t * W2 + (x0 >> 1)) & 1) != 0) ? 16 : 0)) & 0xffffu : 0u;
         const float2 m0 = lut[fl & 31u], m1 = lut[(fl >> 8) & 31u];
         const float mo[2] = { m0.x, m1.x }, ma[2] = { m0.y, m1.y };
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            wn.px[q] = ok ? mo[q] * rx[q] + beta * ppx[q] : 0.f; wn.py[q] = ok ? mo[q] * ry[q] + beta * ppy[q] : 0.f; wn.pa[q] = ok ? ma[q] * rq[q] + beta * ppq[q] : 0.f;
+            if (FIRST) { wn.px[q] = ok ? __builtin_fmaf(mo[q], rx[q], 0.f) : 0.f; wn.py[q] = ok ? __builtin_fmaf(mo[q], ry[q], 0.f) : 0.f; wn.pa[q] = ok ? __builtin_fmaf(ma[q], rq[q], 0.f) : 0.f; }
+            else { wn.px[q] = ok ? mo[q] * rx[q] + beta * ppx[q] : 0.f; wn.py[q] = ok ? mo[q] * ry[q] + beta * ppy[q] : 0.f; wn.pa[q] = ok ? ma[q] * rq[q] + beta * ppq[q] : 0.f; }
             wn.rx[q] = rx[q]; wn.ry[q] = ry[q]; wn.ra[q] = rq[q]; wn.mo[q] = mo[q]; wn.ma[q] = ma[q];
         }
         wn.c[0] = s.cs.x; wn.s[0] = s.cs.y; wn.c[1] = s.cs.z; wn.s[1] = s.cs.w; wn.f = fl;
@@ -209,7 +214,8 @@ __global__ __launch_bounds__(MARCH_NT, OCC) void k_iter_march(MarchGeo g, const 
             for (int q = 0; q < 2; ++q)
                 iter_sums_pixel(wc.px[q], wc.py[q], wc.pa[q], ax[q], ay[q], av[q], wc.rx[q], wc.ry[q], wc.ra[q], wc.mo[q], wc.ma[q], acc, s0, s1, s2);
             const long i2 = (long)y * W2 + (x0 >> 1);
-            stf4(Ao4 + i2, make_float4(ax[0], ay[0], ax[1], ay[1]), nt_out); stf2(Aa2 + i2, make_float2(av[0], av[1]), nt_out);
+            // (A_out == NULL, a GN step's first launch on one GPU: the launch behind it recomputes A p_0 and no plane is kept)
+            if (!FIRST || A_out) { stf4(Ao4 + i2, make_float4(ax[0], ay[0], ax[1], ay[1]), nt_out); stf2(Aa2 + i2, make_float2(av[0], av[1]), nt_out); }
             if (DIST) {     // multi-GPU row slabs: the first / last owned row of A p_k also goes into the neighbour's ghost row of its Ap_out
                             // buffer (peer-to-peer, write-through); drained by every wave before the arrival ticket (iter_tail)
 #pragma unroll
@@ -311,7 +317,7 @@ int launch_march_as(const thallo_iw_iter_t& a, hipStream_t stream)
 // the stored-plane kernel's own conditions on a block: an even width, both A p planes (A p_{k-1} unless the launch is a GN step's first)
 int thallo::launch_march(const thallo_iw_iter_t& a, hipStream_t stream)
 {
-    if ((a.W & 1) || a.W < 2 || !a.Ap_out || (!(a.mode & 1) && !a.Ap_in)) return -(int)hipErrorInvalidValue;
+    if ((a.W & 1) || a.W < 2 || (!a.Ap_out && (!(a.mode & 1) || a.dist)) || (!(a.mode & 1) && !a.Ap_in)) return -(int)hipErrorInvalidValue;      // (Ap_out == NULL: a first launch on one GPU that keeps no A p_0)
     if (a.dist && a.gs) return -(int)hipErrorNotSupported;      // (the deferred cross-rank finish: the recomputing kernel only)
     return !a.dist ? launch_march_as<false>(a, stream) : launch_march_as<true>(a, stream);
 }

@@ -582,7 +582,8 @@ __device__ __forceinline__ void fma4(float4& d, float a, const float4& q)
 }
 // terms j0 .. count-1 onto the running value of float4 i: eight planes' loads in flight per lane (the terms are still applied one after the other): a background
 // launch on 256 workgroups is latency-bound -- 9 x 16 B x 65,536 threads in flight against 5 x with four
-__device__ __forceinline__ void apply_terms4(float4& d, int j, long i, const thallo_update_terms_t& T, const float* al)
+template <class Terms>
+__device__ __forceinline__ void apply_terms4(float4& d, int j, long i, const Terms& T, const float* al)
 {
     for (; j + 8 <= T.count; j += 8) {
         float4 q[8];
@@ -647,6 +648,91 @@ __global__ __launch_bounds__(BLOCK) void k_linear_update_n(float* __restrict__ X
         __syncthreads();
         for (long i = i0; i < len; i += stride) {
             if (i != i0) d = ZERO ? 0.0f : delta[i];
+            for (int j = 0; j < T.count; ++j) d = __builtin_fmaf(al[j], T.p[j][i], d);
+            if (X) X[i] = X[i] + d; else delta[i] = d;
+        }
+    }
+}
+
+// Every term of a GN step in ONE launch (thallo_hip_linear_update_all): up to THALLO_HIP_MAX_STEP_TERMS pending terms applied to a running value that starts at
+// 0.0f, oldest first, one fma each -- the bits of k_linear_update_n launched from zero and then again per 32 terms, without delta's round trips in between.
+// The term table is a kernel-argument block (3.3 KB): plane pointers and the alphas' words; only the first THALLO_HIP_MAX_UPDATE_TERMS terms may be lists of
+// partials (alphaN_0 is one: PCGInit1 leaves partials), added up as update_alphas does; the host refuses a list further back.
+struct StepTerms {
+    const float* p[THALLO_HIP_MAX_STEP_TERMS]; const float* aN[THALLO_HIP_MAX_STEP_TERMS]; const float* aD[THALLO_HIP_MAX_STEP_TERMS];
+    int cN[THALLO_HIP_MAX_UPDATE_TERMS], cD[THALLO_HIP_MAX_UPDATE_TERMS];
+    int count;
+};
+static_assert(sizeof(StepTerms) + 3 * 8 <= 4096, "the term table has to fit the kernel-argument segment");
+// al[j] for every term: the words 64 at a time by lane j of wave 0 (both rounds' loads in flight before the first division), the lists as update_alphas has them.
+// No barrier inside: the caller's __syncthreads() publishes al.  Every lane of the workgroup must call it.
+__device__ __forceinline__ void step_alphas(const StepTerms& T, float* __restrict__ al)
+{
+    const int lane = threadIdx.x & (THALLO_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / THALLO_WAVE));
+    const bool head = lane < T.count && lane < THALLO_HIP_MAX_UPDATE_TERMS;
+    const int jl = head ? lane : 0;
+    const float* pn = T.aN[jl]; const float* pd = T.aD[jl];
+    const int cn = T.cN[jl], cd = T.cD[jl];
+    const bool list = head && !(cn == 1 && cd == 1);
+    if (wave == 0) {
+        constexpr int ROUNDS = THALLO_HIP_MAX_STEP_TERMS / THALLO_WAVE;
+        float n[ROUNDS], d[ROUNDS];
+#pragma unroll
+        for (int u = 0; u < ROUNDS; ++u) {
+            const int j = lane + u * THALLO_WAVE;
+            const bool word = j < T.count && !(u == 0 && list);
+            n[u] = word ? T.aN[j][0] : 0.0f; d[u] = word ? T.aD[j][0] : 1.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < ROUNDS; ++u) {
+            const int j = lane + u * THALLO_WAVE;
+            if (j < T.count && !(u == 0 && list)) al[j] = safe_div<false>(n[u], d[u]);
+        }
+    }
+    unsigned lists = (unsigned)__ballot(list);      // (among the first 32 terms only)
+    lists &= 0x11111111u << wave;
+    while (lists) {
+        const int j = __builtin_ctz(lists);
+        lists &= lists - 1;
+        const float2 s = sum_partials_pair(wave_uniform_ptr(pn, j), __builtin_amdgcn_readlane(cn, j), wave_uniform_ptr(pd, j), __builtin_amdgcn_readlane(cd, j));
+        if (lane == 0) al[j] = safe_div<false>(s.x, s.y);
+    }
+}
+// X != NULL: X += the sum, delta untouched (it may be NULL); X == NULL: delta = the sum.  The first trip's first eight planes are requested ahead of the alphas.
+template <bool V4>
+__global__ __launch_bounds__(BLOCK) void k_linear_update_all(float* __restrict__ X, float* __restrict__ delta, StepTerms T, long len)
+{
+    __shared__ float al[THALLO_HIP_MAX_STEP_TERMS];
+    const long i0 = (long)blockIdx.x * BLOCK + threadIdx.x, stride = (long)gridDim.x * BLOCK;
+    if (V4) {
+        const long n4 = len >> 2;
+        const bool have = i0 < n4, eight = T.count >= 8;
+        float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q[8];
+        if (have && eight) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) q[u] = ldf4(reinterpret_cast<const float4*>(T.p[u]) + i0, true);
+        }
+        step_alphas(T, al);
+        __syncthreads();
+        if (have) {
+            if (eight) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) fma4(d, al[u], q[u]);
+            }
+            apply_terms4(d, eight ? 8 : 0, i0, T, al);
+            store_update4(X, delta, i0, d);
+        }
+        for (long i = i0 + stride; i < n4; i += stride) {
+            float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            apply_terms4(e, 0, i, T, al);
+            store_update4(X, delta, i, e);
+        }
+    } else {
+        step_alphas(T, al);
+        __syncthreads();
+        for (long i = i0; i < len; i += stride) {
+            float d = 0.0f;
             for (int j = 0; j < T.count; ++j) d = __builtin_fmaf(al[j], T.p[j][i], d);
             if (X) X[i] = X[i] + d; else delta[i] = d;
         }
@@ -1184,6 +1270,28 @@ int thallo_hip_linear_update_n(float* X, float* delta, thallo_update_terms_t ter
 int thallo_hip_linear_update_n_from_zero(float* X, float* delta, thallo_update_terms_t terms, long len, int max_workgroups, thallo_stream_t stream)
 {
     return linear_update_n(true, X, delta, terms, len, max_workgroups, stream);
+}
+
+int thallo_hip_linear_update_all(float* X, float* delta, const thallo_update_term_t* terms, int count, long len, int max_workgroups, thallo_stream_t stream)
+{
+    if ((!X && !delta) || len < 0 || count < 0 || count > THALLO_HIP_MAX_STEP_TERMS || (count > 0 && !terms)) return -(int)hipErrorInvalidValue;
+    bool v4 = !(len & 3) && !((uintptr_t)(X ? X : delta) & 15);      // (what the launch stores to; with X given it never touches delta)
+    StepTerms T = {};
+    T.count = count;
+    for (int j = 0; j < count; ++j) {
+        const thallo_update_term_t& t = terms[j];
+        if (!t.p || !t.alphaN.partials || !t.alphaD.partials || t.alphaN.count < 1 || t.alphaD.count < 1) return -(int)hipErrorInvalidValue;
+        if (j < THALLO_HIP_MAX_UPDATE_TERMS) { T.cN[j] = t.alphaN.count; T.cD[j] = t.alphaD.count; }
+        else if (t.alphaN.count != 1 || t.alphaD.count != 1) return -(int)hipErrorInvalidValue;      // (a list of partials that far back: not this entry's)
+        if ((uintptr_t)t.p & 15) v4 = false;
+        T.p[j] = t.p; T.aN[j] = t.alphaN.partials; T.aD[j] = t.alphaD.partials;
+    }
+    if (len == 0) return 0;
+    int grid = flat_grid(v4 ? len >> 2 : len, 2 * cu_count());
+    if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
+    hipLaunchKernelGGL(v4 ? k_linear_update_all<true> : k_linear_update_all<false>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, X, delta, T, len);
+    int e = check_launch();
+    return e ? e : grid;
 }
 
 int thallo_hip_finish_sum(thallo_sum_t sum, float* out, thallo_stream_t stream)

@@ -153,6 +153,9 @@ public:
     // implement pcg_step1_mode; the driver then finishes the GN step with up to two pending alpha*p terms.
     virtual bool batches_delta() const { return false; }
     virtual bool takes_any_p_plane() const { return false; }
+    // One GPU, whole image: pcg_init with v.pre, v.z and v.p[cur] == NULL stores none of them, and the first launch of the one-kernel loop handed Abuf(cur ^ 1) == NULL
+    // keeps no A p_0 -- the plugin's loop reads none of the four (M^-1 from its own planes, p_0 formed in the first launch, A p_0 recomputed by the second)
+    virtual bool lean_head_ok() const { return false; }
     virtual bool init_takes_null_delta() const { return false; }      // pcg_init with v.delta == NULL stores no zeros there (the ring's first delta update starts from 0.0f instead)
     // iterations k0 .. k1-1 of the one-kernel GN loop in ONE launch (image_warping's persistent marching loop): planes[k % n] as in the ring schedule, the plan's
     // slot layout passed through (thallo_hip_iw_pcg_march_persist).  Returns the workgroup count or < 0

@@ -314,6 +314,8 @@ public:
     }
     bool batches_delta() const override { return true; }
     bool init_takes_null_delta() const override { return true; }
+    // (the stored-plane marching kernel as a step's first launch, the recomputing one behind it; not THALLO_MARCH=3, not the tile kernel -- which reads `pre` -- nor a slab)
+    bool lean_head_ok() const override { return march_ && march_rc_ && row0_ == 0 && row1_ == H && !persist_; }
     bool takes_any_p_plane() const override { return march_; }      // (whole images and -- round 6 -- row slabs: the marching kernels keep the ghost rows of whatever plane they write current)
     bool persist_ok() const override { return persist_; }
 #ifdef THALLO_RESEARCH

@@ -268,6 +268,7 @@ const char* env_switch(const char* name)
         { "THALLO_DELTA_FIRST_TOUCH", "delta_first_touch" },    // 0: PCGInit1 zeroes delta in every schedule, and the ring schedule's first delta update of a GN step reads those zeros back
         { "THALLO_SCHUR_S_MAX_MB", "schur_s_max_mb" },          // N: the assembled reduced camera matrix (ThalloX_PlanSetLinearSolver kind 2) may take at most N MiB of device memory (default: a quarter of what is free)
         { "THALLO_SCHUR_DENSE_MAX_MB", "schur_dense_max_mb" },  // N: the dense lower triangle of the reduced camera matrix (ThalloX_PlanSetLinearSolver kind 3) may take at most N MiB of device memory (default: what kind 2's budget leaves)
+        { "THALLO_LEAN_HEAD", "lean_head" },                    // 0: PCGInit1 stores pre, z and p_{-1} = 0 and a GN step's first launch stores A p_0 in every schedule, also where the marching loop reads none of them (A/B)
         { "THALLO_PERSIST", "persist" },                        // 1: iterations 1 .. L-1 of a GN step of image_warping's marching kernel as persistent launches (bit-identical, measured slower)
     };
     for (const char* k : known) if (!strcmp(k, name)) return getenv(name);
@@ -295,13 +296,14 @@ void Plan::read_ab_switches()
     one_kernel_    = !off("THALLO_ONE_KERNEL");
     fin_in_kernel_ = !off("THALLO_FIN_IN_KERNEL");
     { const char* e = env_switch("THALLO_FIN_IN_KERNEL"); fin_deferred_ = !(e && e[0]); }      // unset: deferred where the loop offers it (step_gn_expanded); 1: the in-kernel finish everywhere
-    { const char* e = env_switch("THALLO_DELTA_PLANES"); delta_planes_ = e && e[0] ? atoi(e) : -1; if (delta_planes_ > THALLO_HIP_MAX_UPDATE_TERMS + 1) delta_planes_ = THALLO_HIP_MAX_UPDATE_TERMS + 1;
-      if (delta_planes_ < -(THALLO_HIP_MAX_UPDATE_TERMS + 1)) delta_planes_ = -(THALLO_HIP_MAX_UPDATE_TERMS + 1);
+    { const char* e = env_switch("THALLO_DELTA_PLANES"); delta_planes_ = e && e[0] ? atoi(e) : -1; if (delta_planes_ > THALLO_HIP_MAX_STEP_TERMS) delta_planes_ = THALLO_HIP_MAX_STEP_TERMS;
+      if (delta_planes_ < -THALLO_HIP_MAX_STEP_TERMS) delta_planes_ = -THALLO_HIP_MAX_STEP_TERMS;
       const char* c = e ? strchr(e, ':') : nullptr; aux_async_ = c != nullptr; aux_workgroups_ = c && atoi(c + 1) > 0 ? atoi(c + 1) : 0; }      // ("N:W": the update NEXT TO the loop, on at most W workgroups)
     batch_delta_   = delta_planes_ != 0;
     lm_fold_p_     = !off("THALLO_LM_FOLD_P");
     lm_fold_step_  = !off("THALLO_LM_FOLD_STEP");
     delta_first_touch_ = !off("THALLO_DELTA_FIRST_TOUCH");
+    lean_head_     = !off("THALLO_LEAN_HEAD");
 }
 
 void Plan::set_param(const char* name, const void* value)
@@ -493,7 +495,8 @@ Plan::Owned Plan::owned_range(size_t u) const
 // gn_begin: "Nonlinear Setup" around PCGInit1 (alphaN_0's partials into slot B = 2) and what the opt-in forms put behind it (forms_setup: the mask of held unknowns,
 // the blocks; p_0 = M^-1 r_0 is formed behind them), "Linear Solve" started; false: a launch failed, the step ends.
 // delta_unset: PCGInit1 stores no zeros into delta -- the caller has proved that this step's first reader of delta is a launch that takes "delta is zero" instead.
-bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
+// lean: nor pre, z and the zeros of p_{-1} -- the caller has proved that nothing of this step reads them (step_gn_one_kernel).
+bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset, bool lean)
 {
     hipStream_t s = ctx.stream;
     // (a step that had to allocate -- the first one, or the first after lIterations changed -- has enqueued clears behind "Nonlinear Iteration"'s start: a record of its own)
@@ -501,6 +504,7 @@ bool Plan::gn_begin(int ev_iter, int& ev_lin, bool delta_unset)
     cur_ = 0;
     SolverVectors v_init = v_;
     if (delta_unset) v_init.delta = nullptr;
+    if (lean) v_init.pre = v_init.z = v_init.p[cur_] = nullptr;
     int nb = plugin->pcg_init(ctx, v_init, cur_, slot(2));
     if (nb < 0) { set_error("PCGInit1 launch failed (%d)", nb); return false; }
     if (prior_on() && (nb = prior_init(slot(2))) < 0) { set_error("the prior's launch behind PCGInit1 failed (%d)", nb); return false; }
@@ -596,20 +600,27 @@ int Plan::step_gn_one_kernel(int ev_iter)
 {
     if (ensure_iter_buffers()) { set_error("out of device memory for the one-kernel schedule"); return 0; }
     const int L = sp.lIterations;
-    const int n_ring = ring_planes(L);
+    int n_ring = ring_planes(L);
+    if (plugin->persist_ok() && n_ring > THALLO_HIP_MAX_UPDATE_TERMS + 1) n_ring = THALLO_HIP_MAX_UPDATE_TERMS + 1;      // (the research build's persistent launch takes a ring of that many)
     const GnSchedule sched = gn_schedule(L, n_ring);
     const bool async = n_ring >= 2 && aux_async_ && sched != GnSchedule::Persist && aux_stream();      // (where the delta updates run: ring_flush)
     // delta's first touch: on the ring (n_ring >= 2, so L >= 3), with the updates on the loop's own stream, no launch of the loop touches delta; the step's first
     // PCGDeltaUpdate -- or, when every term still fits it, PCGLinearUpdate -- is its first reader and is told that delta is zero, and PCGInit1 stores no zeros there
     // (24 B per unknown pixel less per step).  Every other schedule, and every step that ends early, never reads what PCGInit1 left out: the next step decides anew.
     const bool delta_unset = delta_first_touch_ && n_ring >= 2 && !async && sched != GnSchedule::Persist && plugin->init_takes_null_delta();
+    // The lean head: Gauss-Newton on one GPU, a plugin whose loop takes M^-1 from its own planes, forms p_0 = M^-1 r_0 in its first launch and recomputes A p_0 in
+    // its second (L >= 2: every launch behind the first is the recomputing one), nothing between PCGInit1 and the loop that reads or rewrites what PCGInit1 leaves:
+    // PCGInit1 stores no pre, z, p_{-1} = 0 (36 B per unknown pixel) and the first launch neither loads p_{-1} nor stores A p_0 (24 B).  Every other schedule
+    // -- LM, row slabs, the resident and persistent loops, the tile kernel, THALLO_MARCH=3, generated plugins -- keeps every plane.
+    const bool lean = lean_head_ && L >= 2 && sched != GnSchedule::Persist && plugin->lean_head_ok() && !prior_on() && !forms_behind_init() && !held_on() && !robust_on();
     int ev_lin;
-    if (!gn_begin(ev_iter, ev_lin, delta_unset)) return 0;
+    if (!gn_begin(ev_iter, ev_lin, delta_unset, lean)) return 0;
     // Round 5: a RING of p planes instead of the ping-pong pair.  Launch k writes p_k into plane k mod n and carries no delta update at all; delta is touched once
     // per n - 1 iterations by thallo_hip_linear_update_n (every pending alpha_j p_j, oldest first, one fma each: the bits of an update per iteration) and the step's
     // last terms ride in PCGLinearUpdate.  Per iteration and unknown 4 (12 + 24 / (n - 1)) / 12 bytes of delta traffic instead of 24 (every iteration) or 18 (every other).
     GnStep st{ L, n_ring < 2 && batch_delta_ && delta_planes_ != 0 && plugin->batches_delta(), PRing(*this, n_ring, async) };
     st.ring.delta_zero = delta_unset;
+    st.lean = lean;
     bool done = false;
     switch (sched) {
     case GnSchedule::Persist:        done = gn_loop_persist(st); break;
@@ -618,7 +629,11 @@ int Plan::step_gn_one_kernel(int ev_iter)
     }
     if (!done) return 0;
     const int ev_fin = gn_finish(L, ev_lin);
-    if (st.ring.on() && L > 0) {
+    if (st.ring.on() && L > 0 && ring_takes_one_pass(st.ring, L)) {
+        // the whole loop ran on the ring and no launch has touched delta: every term goes into the unknowns in one pass per unknown image, delta stays out of the step
+        if (!ring_step_update(st.ring, L)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
+        plugin->unknowns_written();
+    } else if (st.ring.on() && L > 0) {
         // PCGLinearUpdate with every pending term: all but the last THALLO_HIP_MAX_UPDATE_TERMS go into delta first
         if (ring_flush(st.ring, L - 1 - THALLO_HIP_MAX_UPDATE_TERMS) || st.ring.wait_for(L)) { set_error("PCGDeltaUpdate launch failed"); return 0; }
         if (!ring_linear_update(st.ring, L, [](int rc) { return rc >= 0; })) { set_error("PCGLinearUpdate launch failed"); return 0; }
@@ -638,6 +653,16 @@ int Plan::gn_launch_mode(GnStep& st, int k)
     return R.launch(k, cur_);
 }
 
+// What launch k is handed: the step's vectors; on the lean head launch 0 gets a copy without the plane its A p_0 would go into
+SolverVectors& Plan::first_launch_vectors(GnStep& st, int k, SolverVectors& v0)
+{
+    SolverVectors& v = st.ring.vectors();
+    if (k != 0 || !st.lean) return v;
+    v0 = v;
+    (cur_ ? v0.Ap : v0.Ap2) = nullptr;      // Abuf(cur_ ^ 1)
+    return v0;
+}
+
 // Deferred finish (where the plugin offers it): the launch of iteration k adds up iteration k-1's partials
 // itself -- alphaD_{k-1} and betaN_{k-1} = N - 2 alpha S1 + alpha^2 S2 -- while its first rows load, instead of iteration k-1's last workgroup
 // reading them back at the very end of its launch; one one-wave launch per GN step finishes the last iteration.
@@ -649,7 +674,8 @@ bool Plan::gn_loop_deferred(GnStep& st, int k_end)
         if (mode < 0) return false;
         const PrevAlpha a = prev_alpha(k);
         const thallo_prev_t prev = { k ? slot(jD - 2) : nullptr, v_.s12buf((k - 1) & 1), st.nb_prev, k ? scal(jD - 2) : nullptr, k ? scal(jB - 2) : nullptr };
-        const int nb = plugin->pcg_iter_deferred(ctx, st.ring.vectors(), cur_, mode, a.aN, a.aN2, a.aD2, prev, slot(jD), v_.s12buf(k & 1));
+        SolverVectors v0;
+        const int nb = plugin->pcg_iter_deferred(ctx, first_launch_vectors(st, k, v0), cur_, mode, a.aN, a.aN2, a.aD2, prev, slot(jD), v_.s12buf(k & 1));
         if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return false; }
         if (k) words_done(k - 1);             // (that launch's workgroup 0 writes the two words of iteration k-1)
         set_nb(jD, nb); st.nb_prev = nb; cur_ ^= 1;
@@ -695,7 +721,8 @@ bool Plan::gn_loop_finish_in_launch(GnStep& st)
         const int mode = gn_launch_mode(st, k);
         if (mode < 0) return false;
         const PrevAlpha a = prev_alpha(k);
-        const int nb = plugin->pcg_iter(ctx, st.ring.vectors(), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD),
+        SolverVectors v0;
+        const int nb = plugin->pcg_iter(ctx, first_launch_vectors(st, k, v0), cur_, mode, a.aN, a.aD, sum(jN), a.aN2, a.aD2, slot(jD),
                                         fin_in_kernel_ ? scal(jD) : nullptr, fin_in_kernel_ ? scal(jB) : nullptr);
         if (nb < 0) { set_error("PCGIteration launch failed (%d)", nb); return false; }
         set_nb(jD, nb); cur_ ^= 1;
@@ -760,6 +787,33 @@ int Plan::ring_flush(PRing& R, int upto)
     return 0;
 }
 
+// The end of a step whose whole loop ran on the ring (n >= L planes: nothing was flushed inside the loop), one GPU, updates on the loop's own stream: the L terms are
+// applied to a running value that starts at 0.0f and added to the unknowns in ONE launch per unknown image (thallo_hip_linear_update_all; timed as "PCGDeltaUpdate":
+// it is the step's update of delta, which never reaches memory), instead of ceil((L - 32) / 32) launches that carry delta through memory and the tail that reads it
+// back -- the same fmas in the same order.  Taken where the previous end needs two or more such launches ahead of its tail (L > 64); a shorter loop keeps the
+// previous end, one launch from zero and the tail, whose launch counts tests/test_gpu_delta_first_touch.py pins at L = 40.
+bool Plan::ring_takes_one_pass(const PRing& R, int L)
+{
+    if (R.async || R.flushed != 0 || L <= 2 * THALLO_HIP_MAX_UPDATE_TERMS || L > THALLO_HIP_MAX_STEP_TERMS) return false;
+    for (int j = THALLO_HIP_MAX_UPDATE_TERMS; j < L; ++j)      // (the launches of the loop leave words; a list of partials that far back is not the entry's)
+        if (sum(2 + 2 * j).count != 1 || sum(2 + 2 * j + 1).count != 1) return false;
+    return true;
+}
+bool Plan::ring_step_update(PRing& R, int L)
+{
+    thallo_update_term_t T[THALLO_HIP_MAX_STEP_TERMS];
+    long off = 0;
+    for (size_t u = 0; u < plugin->unknown_images().size(); ++u) {
+        TimedLaunch t(ctx, "PCGDeltaUpdate");
+        const Owned o = owned_range(u);
+        for (int j = 0; j < L; ++j) { T[j].p = R.plane(j) + off + o.lo; T[j].alphaN = sum(2 + 2 * j); T[j].alphaD = sum(2 + 2 * j + 1); }
+        if (thallo_hip_linear_update_all(plugin->unknown_ptr((int)u) + o.lo, nullptr, T, L, o.len, 0, ctx.stream) < 0) return false;
+        off += plugin->unknown_images()[u].n_floats;
+    }
+    R.flushed = L;
+    return true;
+}
+
 // The plan's second stream (lowest priority, non-blocking: the loop's stream may be the NULL stream): background updates of delta next to the PCG loop
 bool Plan::aux_stream()
 {
@@ -774,8 +828,8 @@ bool Plan::aux_stream()
 // Planes in the ring of p vectors of the one-kernel GN loop (0: no ring).  v_.p[1], v_.p[0] are its first two; the others are allocated by ring_prepare() -- at Init and
 // again only when lIterations asks for more than the last attempt did -- never inside the step's launch sequence (a hipMalloc + NULL-stream memset per plane is
 // a device-wide synchronisation, illegal under stream capture, and was retried at every step of a memory-limited plan).
-// Footprint: (planes - 2) x one solver vector; by default at most 33 planes, a quarter of the free device memory and 32 GiB (2048^2 image_warping: 31 x 50.3 MB = 1.56 GB;
-// 16384 x 8192: 20 planes of 1.6 GB).  THALLO_DELTA_PLANES=N asks for exactly N (no memory test); planes are released with the plan.
+// Footprint: (planes - 2) x one solver vector; by default min(L, 128) planes -- a loop of up to 128 iterations never touches delta --, at most a quarter of the free
+// device memory and 32 GiB (2048^2 image_warping, L = 100: 98 x 50.3 MB = 4.9 GB; 16384 x 8192: 20 planes of 1.6 GB, the loop flushes into delta as before).  THALLO_DELTA_PLANES=N asks for exactly N (no memory test); planes are released with the plan.
 bool Plan::ring_possible() const
 {   // one GPU, or (round 6) one rank's row slab of the one-kernel schedule: launch k writes p_k into whichever plane it is handed (the ghost rows are kept current there too)
     return plugin->takes_any_p_plane() && (!dist_ || dist_->form == DistForm::Slab);
@@ -783,7 +837,8 @@ bool Plan::ring_possible() const
 int Plan::ring_wanted(int L) const
 {
     if (!ring_possible() || delta_planes_ == 0 || delta_planes_ == 1 || L < 3) return 0;
-    const int want = delta_planes_ >= 2 ? delta_planes_ : delta_planes_ <= -2 ? -delta_planes_ : THALLO_HIP_MAX_UPDATE_TERMS + 1;
+    // (default: as long as the loop on one GPU, whose step then ends in one pass; a row slab keeps the 33 planes its in-loop flushes were measured with)
+    const int want = delta_planes_ >= 2 ? delta_planes_ : delta_planes_ <= -2 ? -delta_planes_ : dist_ ? THALLO_HIP_MAX_UPDATE_TERMS + 1 : THALLO_HIP_MAX_STEP_TERMS;
     return want > L ? L : want;             // (L planes: delta is never touched inside the loop)
 }
 void Plan::ring_prepare(int L)

@@ -221,7 +221,7 @@ private:
 
     float* slot(int j) { return (float*)parts_.ptr + (size_t)j * THALLO_HIP_MAX_PARTIALS; }
     std::vector<char> fin_;         // slot already reduced to one word (scal(j)) by a 1-wave finish_sum launch
-    bool fin_in_kernel_ = true, one_kernel_ = true, batch_delta_ = true, lm_fold_p_ = true, lm_fold_step_ = true, delta_first_touch_ = true;   // A/B switches: read_ab_switches()
+    bool fin_in_kernel_ = true, one_kernel_ = true, batch_delta_ = true, lm_fold_p_ = true, lm_fold_step_ = true, delta_first_touch_ = true, lean_head_ = true;   // A/B switches: read_ab_switches()
     int delta_planes_ = -1;         // THALLO_DELTA_PLANES (-1: unset)
     std::vector<float*> ring_;      // the ring of p planes of the one-kernel GN loop (ring_planes)
     bool ring_possible() const;     // the plugin's iteration takes any p plane, on one GPU or on a row slab of the one-kernel schedule
@@ -261,6 +261,8 @@ private:
         int  wait_to_overwrite(int k) { return k >= n && synced < k - n + 1 ? wait_for(k - n) : 0; }      // ... before launch k writes plane k mod n
     };
     int  ring_flush(PRing& R, int upto);                // one GPU: delta += alpha_j p_j for every j <= upto not flushed yet ("PCGDeltaUpdate", on the loop's or the second stream)
+    bool ring_takes_one_pass(const PRing& R, int L);    // the step's end is ONE pass over all L terms (nothing flushed, 64 < L <= 128, words behind term 32, loop's own stream)
+    bool ring_step_update(PRing& R, int L);             // ... that pass: X += sum_j alpha_j p_j per unknown image, delta neither read nor written ("PCGDeltaUpdate")
     struct Owned { long lo, len; };
     Owned owned_range(size_t u) const;                  // the part of unknown image u this plan updates: its owned rows on a row slab, else all of it
     // PCGLinearUpdate with the ring's pending terms p_flushed .. p_{L-1} riding in it, over the owned range of every unknown image; `launched(rc)` says whether to go on
@@ -296,7 +298,9 @@ private:
         const bool batched;                             // no ring: every other delta update is deferred (THALLO_IW_STEP1_MODE(k, 1))
         PRing ring;
         int nb_prev = 0;                                // deferred finish: the partial count of the launch before
+        bool lean = false;                              // PCGInit1 left pre, z and p_{-1} out; launch 0 keeps no A p_0 (step_gn_one_kernel)
     };
+    SolverVectors& first_launch_vectors(GnStep& st, int k, SolverVectors& v0);
     int  step_gn_one_kernel(int ev_iter);
     GnSchedule gn_schedule(int L, int n_ring);
     int  gn_launch_mode(GnStep& st, int k);             // the ring made ready for launch k; the launch's delta mode (< 0: failed)
@@ -305,7 +309,7 @@ private:
     bool gn_loop_deferred(GnStep& st, int k_end);       // iterations [0, k_end)
     bool gn_loop_finish_in_launch(GnStep& st);
     int  step_gn_resident(int ev_iter);
-    bool gn_begin(int ev_iter, int& ev_lin, bool delta_unset = false);      // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2 (delta_unset: it stores no zeros into delta), forms_setup, "Linear Solve" started
+    bool gn_begin(int ev_iter, int& ev_lin, bool delta_unset = false, bool lean = false);      // the head of every PCG-loop GN step: "Nonlinear Setup", PCGInit1 into slot 2 (delta_unset: it stores no zeros into delta), forms_setup, "Linear Solve" started
     int  gn_finish(int L, int ev_lin);                  // ... its tail: "Nonlinear Finish" started (the caller's update of the unknowns follows) ...
     int  gn_end(int ev_fin, int ev_iter);               // ... and the step counted, its events ended
     bool resident_used_ = false;    // a resident launch ran since the last cost evaluation (its error word is read there)
