@@ -219,6 +219,31 @@ int thallo_hip_linear_update_all(float* X, float* delta, const thallo_update_ter
    out_ballot = max over lanes of ballot(lane != 0) = 0xFFFFFFFFFFFFFFFE; out_peers = sum over lanes of (peer mask of key lane % 4) & 0xFF = 255 * 64 / 4;
    sums4[i] = 480 + 16 i. */
 int thallo_hip_wave64_selftest(unsigned long long* out_ballot, unsigned* out_peers, float* sums4);
+/* A generated energy's three operations one by one (tests/test_gpu_generated_kernels.py): the plugin a plan of (file, dims, useAutoscheduler, doublePrecision) would get --
+   the THALLO_AB switches frontend_aggregate / frontend_preload / frontend_computed / inc_lanes and THALLO_DENSE_JTJ_MAX apply as they do there -- driven through its own
+   interface, on the null stream, on the caller's device vectors of thallo_hip_vector_elems(n_unknowns) elements (floats; doubles under doublePrecision = 1, partials too).
+   open: NULL + ThalloX_LastError on failure.  bind: the void** of Thallo_ProblemInit; prepare: once per bind, as at Init.
+   cost: partials_out holds THALLO_HIP_MAX_PARTIALS words, the return value = how many were written (their sum is the cost, the factor 0.5 included).
+   pcg_init: r = -J^T F, diag = the raw diagonal of J^T J, pre = M^-1 (1 / (1 + sqrt(diag))^2, or 1 without the preconditioner), z = pre r, delta = 0, the partials of r . z;
+             p as the plugin leaves it: zeros in float (the first PCGStep3 forms p_0 = z), z in double.  apply_jtj: Ap = J^T J p, the partials of p . Ap.
+   set_row_slab / set_slab_global: the row-slab unit on one device -- owned local rows [row0, row1), the local image being rows [global_row0, ..) of global_rows; then the
+             three operations cover the owned rows only (Ap is 0 elsewhere, the sums run over the owned rows).
+   kernels: what = 0 the generated kernels launched through this handle so far, 1 every kernel the plugin holds, 2 those launched since the last call with what = 2; names each followed by ';', valid until the next call. */
+void* thallo_hip_genprobe_open(const char* file, const unsigned* dims, int useAutoscheduler, int doublePrecision);
+void thallo_hip_genprobe_close(void* handle);
+long thallo_hip_genprobe_n_unknowns(void* handle);
+const char* thallo_hip_genprobe_schedule_name(void* handle);
+int thallo_hip_genprobe_use_preconditioner(void* handle);
+int thallo_hip_genprobe_whole_store(void* handle);      /* 1: one merged gather kernel writes every unknown -- PCGInit1 and applyJTJ store instead of accumulating */
+int thallo_hip_genprobe_bind(void* handle, void** params);
+int thallo_hip_genprobe_prepare(void* handle);
+int thallo_hip_genprobe_cost(void* handle, void* partials_out);
+int thallo_hip_genprobe_pcg_init(void* handle, void* r, void* diag, void* pre, void* z, void* p, void* delta, void* alphaN_partials);
+int thallo_hip_genprobe_apply_jtj(void* handle, const void* p, void* Ap, void* alphaD_partials);
+int thallo_hip_genprobe_set_row_slab(void* handle, int row0, int row1);
+int thallo_hip_genprobe_set_slab_global(void* handle, int global_row0, int global_rows);
+int thallo_hip_genprobe_slab_ghost_rows(void* handle);
+const char* thallo_hip_genprobe_kernels(void* handle, int what);
 int thallo_hip_finish_sum(thallo_sum_t s, float* out, thallo_stream_t stream);
 /* ... behind a device-side gate word (non-zero: the launch does nothing; the LM loop's gate, see thallo_hip_lm_zeta) */
 int thallo_hip_finish_sum_gated(thallo_sum_t s, float* out, const unsigned* gate, thallo_stream_t stream);

@@ -64,7 +64,7 @@ def shim():
     import thallo_amd
     L = C.CDLL(thallo_amd.lib()._name)
     S, G = api.SumT, api.SegsT
-    vp, lg, it, fl = C.c_void_p, C.c_long, C.c_int, C.c_float
+    vp, lg, it, fl, db = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double
     sig = {
         "vector_elems": [lg], "device_cu_count": [],
         "pcg_step2": [vp] * 4 + [lg, S, S, vp, vp],
@@ -168,6 +168,12 @@ def shim():
         "lapimg_pcg_init": [it, it, vp, vp, fl, it] + [vp] * 7,
         "lapimg_apply_jtj": [it, it, fl, it] + [vp] * 4,
         "lapimg_pcg_step1": [it, it, fl, it] + [vp] * 5 + [it] + [S] * 3 + [vp, vp],
+        # the double-precision PCG / LM kernels (csrc/pcg_kernels_f64.hip; test_gpu_f64_kernels.py): the vectors, n, the device words, the partials, the stream
+        "f64_init_finish": [vp] * 4 + [lg, it, vp, vp], "f64_dot": [vp, vp, lg, vp, vp], "f64_step2": [vp] * 6 + [lg] + [vp] * 4,
+        "f64_step3": [vp, vp, lg, vp, vp, vp], "f64_linear_update": [vp, vp, lg, vp], "f64_finish": [vp, it, vp, vp],
+        "f64_lm_finalize_diagonal": [vp] * 7 + [lg, db, db, db, it, it, vp, vp], "f64_lm_step1_finish": [vp, vp, vp, lg, vp, vp],
+        "f64_lm_step2": [vp] * 7 + [lg] + [vp] * 5, "f64_lm_step2_first_half": [vp, vp, lg, vp, vp, vp],
+        "f64_lm_step2_second_half": [vp] * 6 + [lg, vp, vp, vp], "f64_lm_step3": [vp, vp, lg, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, "thallo_hip_" + name)
@@ -175,6 +181,14 @@ def shim():
         f.restype = (None if name in ("lm_set_gate", "arap_debug_set", "sfs_march_debug_set", "march_debug_set", "resident_debug_set")
                      else lg if name in ("vector_elems", "iw_resident_bytes") else C.c_uint if name == "iw_iter_size" else it)
     assert L.thallo_hip_iw_iter_size() == C.sizeof(api.IwIterT), "thallo_iw_iter_t and its ctypes mirror differ"
+    # the probe of a generated plugin (csrc/dsl_plugin.cpp; test_gpu_generated_kernels.py): name -> (argtypes, restype)
+    cs = C.c_char_p
+    for name, (args, res) in {"open": ([cs, C.POINTER(C.c_uint), it, it], vp), "close": ([vp], None), "n_unknowns": ([vp], lg), "schedule_name": ([vp], cs),
+                              "use_preconditioner": ([vp], it), "whole_store": ([vp], it), "bind": ([vp, C.POINTER(vp)], it), "prepare": ([vp], it), "cost": ([vp, vp], it), "pcg_init": ([vp] * 8, it),
+                              "apply_jtj": ([vp] * 4, it), "set_row_slab": ([vp, it, it], it), "set_slab_global": ([vp, it, it], it), "slab_ghost_rows": ([vp], it),
+                              "kernels": ([vp, it], cs)}.items():
+        f = getattr(L, "thallo_hip_genprobe_" + name)
+        f.argtypes, f.restype = args, res
     _SHIM = L
     return L
 

@@ -9,6 +9,8 @@ import pytest
 
 from thallo_amd import api
 from helpers import to_host
+import generated_reference as gr
+from generated_reference import rotate3d as _rotate3d
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "energies")
@@ -74,16 +76,7 @@ def test_gradient_domain_pasting(torch, dbl):
     M = np.ones((H, W), np.float32); M[2:9, 3:12] = 0.0; M[5, 6] = 1.0          # a region with a pinned pixel inside
     free = np.repeat(M.reshape(-1) == 0, 4)
 
-    def F(x):
-        X = x.reshape(H, W, 4); out = []
-        for dx, dy in ((1, 0), (-1, 0), (0, 1), (0, -1)):
-            r = np.zeros_like(X)
-            ys, xs = slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx))
-            yn, xn = slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx))
-            r[ys, xs] = (X[ys, xs] - X[yn, xn]) - (T[ys, xs] - T[yn, xn])
-            out.append(r.reshape(-1))
-        return np.concatenate(out)
-
+    F = gr.gradient_paste_F(W, H, T)
     ref_x, ref_costs = mirror(F, X0.reshape(-1), free, 3, 20, precond=False)
     got_x, got_costs = run(torch, "gradient_paste.t", (W, H), [X0.copy(), T, M], [0], dbl, nIterations=3, lIterations=20)
     check(got_x, got_costs, ref_x, ref_costs, dbl)
@@ -103,16 +96,7 @@ def test_cotangent_weighted_fairing(torch, dbl):
     N, E = A.shape[0], len(e)
     w_fit, w_reg = float(np.float32(0.8)), float(np.float32(0.6))          # Param(float): both precisions receive the floats nearest to 0.8 / 0.6
 
-    def F(x):
-        X = x.reshape(N, 3)
-        def cot(p, q, apex):
-            a, b = p - apex, q - apex
-            c = np.cross(a, b)
-            return (a * b).sum(-1) / np.sqrt((c * c).sum(-1))
-        p0, p1, p2, p3 = X[v[0]], X[v[1]], X[v[2]], X[v[3]]
-        wgt = 0.5 * (cot(p0, p1, p2) + cot(p0, p1, p3))
-        return np.concatenate([(w_fit * (X - A)).reshape(-1), (w_reg * wgt[:, None] * (p1 - p0)).reshape(-1)])
-
+    F = gr.cotan_smooth_F(N, v, A, w_fit, w_reg)
     got_x, got_costs = run(torch, "cotan_smooth.t", (N, E), [w_fit, w_reg, X0.copy(), A, v[0], v[1], v[2], v[3]], [2], dbl, nIterations=4, lIterations=12)
     ref_x, ref_costs = mirror(F, X0.reshape(-1), np.ones(3 * N, bool), 4, 12, precond=True)
     check(got_x, got_costs, ref_x, ref_costs, dbl)
@@ -129,23 +113,11 @@ def test_robust_point_to_plane(torch, dbl):
     nb = rng.permutation(N).astype(np.int32)
     w_rob = float(np.float32(0.35))
 
-    def F(x):
-        X = x[:3 * N].reshape(N, 3); R = x[3 * N:]
-        d = (Nrm * (X - T)).sum(-1)
-        return np.concatenate([R * R * d, w_rob * (1.0 - R * R), (0.3 * (X - X[nb])).reshape(-1)])
-
+    F = gr.robust_plane_F(N, T, Nrm, nb, w_rob)
     x0 = np.concatenate([X0.reshape(-1), R0])
     ref_x, ref_costs = mirror(F, x0, np.ones(4 * N, bool), 5, 10, precond=True)
     got_x, got_costs = run(torch, "robust_plane.t", (N,), [X0.copy(), R0.copy(), T, Nrm, w_rob, nb], [0, 1], dbl, nIterations=5, lIterations=10)
     check(got_x, got_costs, ref_x, ref_costs, dbl)
-
-
-def _rotate3d(a, v):
-    """lib.t:123-137 (Euler angles alpha, beta, gamma -> R v), on (..., 3) arrays; complex-capable"""
-    ca, cb, cg, sa, sb, sg = np.cos(a[..., 0]), np.cos(a[..., 1]), np.cos(a[..., 2]), np.sin(a[..., 0]), np.sin(a[..., 1]), np.sin(a[..., 2])
-    m = [cg * cb, -sg * ca + cg * sb * sa, sg * sa + cg * sb * ca, sg * cb, cg * ca + sg * sb * sa, -cg * sa + sg * sb * ca, -sb, cb * sa, cb * ca]
-    return np.stack([m[0] * v[..., 0] + m[1] * v[..., 1] + m[2] * v[..., 2], m[3] * v[..., 0] + m[4] * v[..., 1] + m[5] * v[..., 2],
-                     m[6] * v[..., 0] + m[7] * v[..., 1] + m[8] * v[..., 2]], -1)
 
 
 @pytest.mark.parametrize("dbl", [True, False])
@@ -161,19 +133,7 @@ def test_lattice_arap_over_a_three_dimensional_domain(torch, dbl):
     Ang0 = 0.05 * rng.standard_normal(Rest.shape)
     w_fit, w_reg = float(np.float32(2.0)), float(np.float32(0.9))
     n = W * H * D * 3
-
-    def F(x):
-        P = x[:n].reshape(D, H, W, 3); A = x[n:].reshape(D, H, W, 3)
-        held = Tgt[..., 0] >= -999999.9
-        out = [np.where(held[..., None], w_fit * (P - Tgt), 0.0).reshape(-1)]
-        for dx, dy, dz in ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)):
-            r = np.zeros_like(P)
-            s = (slice(max(0, -dz), D - max(0, dz)), slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx)))
-            t = (slice(max(0, dz), D - max(0, -dz)), slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx)))
-            r[s] = w_reg * ((P[s] - P[t]) - _rotate3d(A[s], Rest[s] - Rest[t]))
-            out.append(r.reshape(-1))
-        return np.concatenate(out)
-
+    F = gr.volume_arap_F(W, H, D, Rest, Tgt, w_fit, w_reg)
     x0 = np.concatenate([Pos0.reshape(-1), Ang0.reshape(-1)])
     got_x, got_costs = run(torch, "volume_arap.t", (W, H, D), [w_fit, w_reg, Pos0.copy(), Ang0.copy(), Rest, Tgt], [2, 3], dbl, nIterations=4, lIterations=15)
     ref_x, ref_costs = mirror(F, x0, np.ones(2 * n, bool), 4, 15, precond=True)
@@ -189,11 +149,7 @@ def test_two_unknown_index_spaces(torch, dbl):
     T = rng.uniform(-1, 1, N)
     S0 = rng.uniform(-0.5, 0.5, U); P0 = rng.uniform(-1, 1, N)
 
-    def F(x):
-        S, P = x[:U], x[U:]
-        fit = (S[None, :] + P[:, None] - T[:, None])          # element (n, u); the order of the residuals does not matter to J^T J
-        return np.concatenate([fit.reshape(-1), 0.5 * P])
-
+    F = gr.two_domains_F(N, U, T)
     got_x, got_costs = run(torch, "two_domains.t", (N, U), [S0.copy(), P0.copy(), T], [0, 1], dbl, nIterations=3, lIterations=8)
     ref_x, ref_costs = mirror(F, np.concatenate([S0, P0]), np.ones(N + U, bool), 3, 8, precond=True)
     check(got_x, got_costs, ref_x, ref_costs, dbl)
@@ -211,22 +167,11 @@ def test_deconvolution_with_a_window_wider_than_the_dual_width(torch, tmp_path, 
     truth = rng.uniform(0.0, 1.0, (H, W))
     c = KS // 2
 
-    def blur(X):
-        out = np.zeros((H, W), dtype=X.dtype)
-        for ky in range(KS):
-            for kx in range(KS):
-                out[c:H - c, c:W - c] += Ker[ky, kx] * X[ky:H - 2 * c + ky, kx:W - 2 * c + kx]
-        return out
-
+    blur = lambda X: gr.conv2d_blur(W, H, KS, Ker, X)
     B = blur(truth) + 1e-3 * rng.standard_normal((H, W))
     X0 = B.copy()
 
-    def F(x):
-        X = x.reshape(H, W)
-        data = np.zeros((H, W), dtype=X.dtype)
-        data[c:H - c, c:W - c] = (blur(X) - B)[c:H - c, c:W - c]
-        return np.concatenate([data.reshape(-1), 0.05 * x])
-
+    F = gr.conv2d_wide_F(W, H, KS, Ker, B)
     text = open(os.path.join(HERE, "conv2d_wide.t")).read()
     if KS != 11: text = text.replace("kx - 5", f"kx - {c}").replace("ky - 5", f"ky - {c}").replace("InBoundsExpanded(x, y, 5)", f"InBoundsExpanded(x, y, {c})")
     (tmp_path / "conv2d_wide.t").write_text(text)
@@ -251,11 +196,7 @@ def test_one_rigid_motion_for_a_point_set(torch, dbl):
     Goal[rng.uniform(size=N) < 0.2] = -1e6
     x0 = np.zeros(6)
 
-    def F(x):
-        Shift, Euler = x[:3], x[3:]
-        r = _rotate3d(np.broadcast_to(Euler, (N, 3)).astype(x.dtype), Rest.astype(x.dtype)) + Shift - Goal
-        return np.where((Goal[:, :1] >= -999999.9), r, 0.0).reshape(-1)
-
+    F = gr.rigid_fit_F(N, Rest, Goal)
     dev_params = [np.zeros((1, 3)), np.zeros((1, 3)), Rest, Goal]
     dev = []
     for p in dev_params: dev.append(torch.from_numpy(p if dbl else p.astype(np.float32)).cuda())
@@ -288,16 +229,7 @@ def test_embedded_deformation_nodes(torch, dbl):
     M0 = np.tile(np.eye(3).reshape(1, 9), (N, 1)) + 0.02 * rng.standard_normal((N, 9))
     w_fit, w_reg, w_rot = float(np.float32(3.0)), float(np.float32(1.0)), float(np.float32(2.0))
 
-    def F(x):
-        Off = x[:3 * N].reshape(N, 3); M = x[3 * N:].reshape(N, 3, 3)
-        fit = np.where(Goal[:, :1] >= -999999.9, w_fit * (Off - Goal), 0.0)
-        d = Rest[b] - Rest[a]
-        edge = (Off[b] - Off[a]) - np.einsum("eij,ej->ei", M[a], d.astype(x.dtype))
-        c0, c1, c2 = M[:, :, 0], M[:, :, 1], M[:, :, 2]
-        dot = lambda u, v: (u * v).sum(-1)
-        rot = w_rot * np.stack([dot(c0, c1), dot(c0, c2), dot(c1, c2), dot(c0, c0) - 1, dot(c1, c1) - 1, dot(c2, c2) - 1], -1)
-        return np.concatenate([fit.reshape(-1), (w_reg * edge).reshape(-1), rot.reshape(-1)])
-
+    F = gr.embedded_nodes_F(N, a, b, Rest, Goal, w_fit, w_reg, w_rot)
     x0 = np.concatenate([Off0.reshape(-1), M0.reshape(-1)])
     got_x, got_costs = run(torch, "embedded_nodes.t", (N, E), [w_fit, w_reg, w_rot, Off0.copy(), M0.copy(), Rest, Goal, a, b], [3, 4], dbl, nIterations=4, lIterations=10)
     ref_x, ref_costs = mirror(F, x0, np.ones(12 * N, bool), 4, 10, precond=True)

@@ -26,6 +26,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <set>
 
 namespace thallo {
 
@@ -61,6 +63,8 @@ int rtc_build(const std::string& src, bool wide, const char* what, hipModule_t* 
     if (hipModuleLoadData(mod, code.data()) != hipSuccess) { set_error("%s: hipModuleLoadData failed for code generated with %s", what, arch.c_str()); (void)hipGetLastError(); return -1; }
     return 0;
 }
+
+thread_local bool record_kernel_names = false;
 
 class GeneratedPlugin : public EnergyPlugin, public EnergyPlugin64 {
     dsl::Problem P;
@@ -122,11 +126,18 @@ class GeneratedPlugin : public EnergyPlugin, public EnergyPlugin64 {
         long g = (n + 255) / 256; if (g < 1) g = 1; if (g > cap) g = cap;
         return (int)g;
     }
-    int launch(int kernel, int grid, void** args, hipStream_t s)
+    // tests only (thallo_hip_genprobe_*, which sets record_kernel_names around make_generated_plugin): the kernels' names by function handle and the set of those
+    // that were launched; a plan's plugin keeps neither
+    const bool keep_names_ = record_kernel_names;
+    std::map<hipFunction_t, std::string> fn_names_;
+    std::set<std::string>* launched_ = nullptr;
+    bool get_fn(hipModule_t m, const std::string& name, hipFunction_t* f)      // true = missing
     {
-        hipError_t e = hipModuleLaunchKernel(fn[kernel], grid, 1, 1, 256, 1, 1, 0, s, args, nullptr);
-        return e == hipSuccess ? 0 : -(int)e;
+        if (hipModuleGetFunction(f, m, name.c_str()) != hipSuccess) return true;
+        if (keep_names_) fn_names_[*f] = name;
+        return false;
     }
+    int launch(int kernel, int grid, void** args, hipStream_t s) { return launch_fn(fn[kernel], grid, args, s); }
     int kernel_of(int residual, int kind) const { return residual * dsl::GEN_KINDS + kind; }
     std::vector<char> gather_;                     // per residual: the unknown-wise (gather) kernels run (compute_at_output, or the autoscheduler's choice where eligible)
     // merged gather kernels, one per iteration domain (G.groups): group_of_[ri] = the group residual ri runs in (-1: its own kernel); group_nel_: elements of the domain
@@ -136,6 +147,7 @@ class GeneratedPlugin : public EnergyPlugin, public EnergyPlugin64 {
     bool whole_ = false;                           // ONE group holds every residual and writes every unknown: its applyJTJ stores (no Ap clear, no read-modify-write) and alphaD rides along
     int launch_fn(hipFunction_t f, int grid, void** args, hipStream_t s)
     {
+        if (launched_) launched_->insert(fn_names_[f]);
         hipError_t e = hipModuleLaunchKernel(f, grid, 1, 1, 256, 1, 1, 0, s, args, nullptr);
         return e == hipSuccess ? 0 : -(int)e;
     }
@@ -279,7 +291,7 @@ public:
                 if (!use_inc_[(size_t)ir.ri]) continue;
                 for (size_t k = 0; k < ir.groups.size(); ++k) {
                     IncRun* run = new IncRun(); run->ri = ir.ri; run->g = ir.groups[k];
-                    if (hipModuleGetFunction(&run->jtj, mod, ir.jtj[k].c_str()) != hipSuccess || hipModuleGetFunction(&run->jtf, mod, ir.jtf[k].c_str()) != hipSuccess) {
+                    if (get_fn(mod, ir.jtj[k], &run->jtj) || get_fn(mod, ir.jtf[k], &run->jtf)) {
                         delete run; set_error("%s: generated kernel %s missing", label.c_str(), ir.jtj[k].c_str()); return;
                     }
                     inc_runs_.push_back(run);
@@ -429,6 +441,9 @@ public:
         return 0;
     }
     bool ok() const { return ok_; }
+    void trace_launches(std::set<std::string>* into) { launched_ = into; }
+    bool whole_store() const { return whole_; }
+    std::string kernel_names() const { std::string t; std::set<std::string> u; for (auto& kv : fn_names_) u.insert(kv.second); for (auto& n : u) t += n + ";"; return t; }
 
     int compile()
     {
@@ -441,25 +456,25 @@ public:
         for (auto& k : G.kernels) {
             hipFunction_t f = nullptr;
             if (k.name.empty()) { fn.push_back(nullptr); continue; }       // (no gather form for this residual)
-            if (hipModuleGetFunction(&f, mod, k.name.c_str()) != hipSuccess) { set_error("%s: generated kernel %s missing", label.c_str(), k.name.c_str()); return -1; }
+            if (get_fn(mod, k.name, &f)) { set_error("%s: generated kernel %s missing", label.c_str(), k.name.c_str()); return -1; }
             fn.push_back(f);
         }
         for (auto& gc : G.computed) {
             hipFunction_t f = nullptr;
-            if (hipModuleGetFunction(&f, mod, gc.kernel.c_str()) != hipSuccess) { set_error("%s: generated kernel %s missing", label.c_str(), gc.kernel.c_str()); return -1; }
+            if (get_fn(mod, gc.kernel, &f)) { set_error("%s: generated kernel %s missing", label.c_str(), gc.kernel.c_str()); return -1; }
             ca_fn.push_back(f);
         }
         for (auto& ir : G.inc) {
             hipFunction_t f = nullptr;
-            if (hipModuleGetFunction(&f, mod, ir.uidx.c_str()) != hipSuccess) { set_error("%s: generated kernel %s missing", label.c_str(), ir.uidx.c_str()); return -1; }
+            if (get_fn(mod, ir.uidx, &f)) { set_error("%s: generated kernel %s missing", label.c_str(), ir.uidx.c_str()); return -1; }
             inc_uidx_.push_back(f);
         }
         for (auto& g : G.groups) {
             hipFunction_t fa = nullptr, fb = nullptr;
-            if (hipModuleGetFunction(&fa, mod, g.jtj.c_str()) != hipSuccess || hipModuleGetFunction(&fb, mod, g.jtf.c_str()) != hipSuccess) { set_error("%s: generated group kernel %s missing", label.c_str(), g.jtj.c_str()); return -1; }
+            if (get_fn(mod, g.jtj, &fa) || get_fn(mod, g.jtf, &fb)) { set_error("%s: generated group kernel %s missing", label.c_str(), g.jtj.c_str()); return -1; }
             grp_jtj.push_back(fa); grp_jtf.push_back(fb);
             hipFunction_t fc = nullptr;
-            if (!g.cost.empty() && hipModuleGetFunction(&fc, mod, g.cost.c_str()) != hipSuccess) { set_error("%s: generated group kernel %s missing", label.c_str(), g.cost.c_str()); return -1; }
+            if (!g.cost.empty() && get_fn(mod, g.cost, &fc)) { set_error("%s: generated group kernel %s missing", label.c_str(), g.cost.c_str()); return -1; }
             grp_cost.push_back(fc);
         }
         return 0;
@@ -724,7 +739,7 @@ private:
         if (rtc_build("#include <hip/hip_runtime.h>\n" + GS.source, GS.has_wide, (P.file + " (row slab)").c_str(), &smod_)) return -1;
         auto get = [&](const std::string& n, std::vector<hipFunction_t>& v) {
             hipFunction_t f = nullptr;
-            if (hipModuleGetFunction(&f, smod_, n.c_str()) != hipSuccess) { set_error("%s: generated slab kernel %s missing", label.c_str(), n.c_str()); return false; }
+            if (get_fn(smod_, n, &f)) { set_error("%s: generated slab kernel %s missing", label.c_str(), n.c_str()); return false; }
             v.push_back(f); return true;
         };
         for (auto& gc : GS.computed) if (!get(gc.kernel, sca_fn_)) return -1;
@@ -822,6 +837,88 @@ EnergyPlugin* make_generated_plugin(const char* filename, const unsigned* dims, 
 }
 
 }  // namespace thallo
+
+// A generated plugin's three operations one by one, for tests (tests/test_gpu_generated_kernels.py): the plugin make_generated_plugin returns for a plan -- the same
+// THALLO_AB / THALLO_DENSE_JTJ_MAX switches apply -- driven through its own interface on the caller's device vectors (thallo_hip_vector_elems(n) elements each: floats,
+// or doubles when the probe was opened with doublePrecision = 1), on the null stream.  No solver loop and no option a plan does not have.
+namespace {
+struct GenProbe { thallo::GeneratedPlugin* plugin = nullptr; thallo::LaunchCtx ctx; bool f64 = false; std::set<std::string> launched, ever; std::string text; };
+}
+extern "C" void* thallo_hip_genprobe_open(const char* file, const unsigned* dims, int useAutoscheduler, int doublePrecision)
+{
+    if (!file || !dims) { thallo::set_error("thallo_hip_genprobe_open: no file or no dimensions"); return nullptr; }
+    thallo::record_kernel_names = true;
+    thallo::EnergyPlugin* g = thallo::make_generated_plugin(file, dims, useAutoscheduler != 0, doublePrecision != 0);
+    thallo::record_kernel_names = false;
+    if (!g) return nullptr;
+    GenProbe* h = new GenProbe(); h->plugin = static_cast<thallo::GeneratedPlugin*>(g); h->f64 = doublePrecision != 0;      // (make_generated_plugin makes nothing else)
+    h->plugin->trace_launches(&h->launched);
+    return h;
+}
+extern "C" void thallo_hip_genprobe_close(void* handle) { GenProbe* h = (GenProbe*)handle; if (!h) return; (void)hipDeviceSynchronize(); delete h->plugin; delete h; }
+extern "C" long thallo_hip_genprobe_n_unknowns(void* handle) { return handle ? ((GenProbe*)handle)->plugin->n_unknowns() : -1; }
+extern "C" const char* thallo_hip_genprobe_schedule_name(void* handle) { return handle ? ((GenProbe*)handle)->plugin->schedule_name() : nullptr; }
+extern "C" int thallo_hip_genprobe_use_preconditioner(void* handle) { return handle ? (((GenProbe*)handle)->plugin->use_preconditioner() ? 1 : 0) : -1; }
+// 1: ONE merged gather kernel holds every residual and writes every unknown, so PCGInit1 and applyJTJ STORE r, the diagonal and Ap (modes 1 and 3 of the group kernels)
+extern "C" int thallo_hip_genprobe_whole_store(void* handle) { return handle ? (((GenProbe*)handle)->plugin->whole_store() ? 1 : 0) : -1; }
+extern "C" int thallo_hip_genprobe_bind(void* handle, void** params)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h || !params) return -(int)hipErrorInvalidValue;
+    const int rc = h->plugin->bind(params); if (rc < 0) return rc;
+    h->plugin->unknowns_changed();
+    return 0;
+}
+extern "C" int thallo_hip_genprobe_prepare(void* handle) { GenProbe* h = (GenProbe*)handle; return h ? h->plugin->prepare(h->ctx) : -(int)hipErrorInvalidValue; }
+// partials_out: THALLO_HIP_MAX_PARTIALS words; returns how many were written
+extern "C" int thallo_hip_genprobe_cost(void* handle, void* partials_out)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h || !partials_out) return -(int)hipErrorInvalidValue;
+    return h->f64 ? h->plugin->f64()->cost64(h->ctx, (double*)partials_out) : h->plugin->cost(h->ctx, (float*)partials_out);
+}
+// PCGInit1 + _Finish: r = -J^T F, diag = the raw diagonal of J^T J, pre = M^-1, z = M^-1 r, delta = 0, the partials of r . z; p as the plugin leaves it (float: zeros --
+// PCGStep3 of the first iteration forms p_0 = z; double: p = z).  Returns the number of partials.
+extern "C" int thallo_hip_genprobe_pcg_init(void* handle, void* r, void* diag, void* pre, void* z, void* p, void* delta, void* alphaN_partials)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h || !r || !diag || !pre || !z || !p || !delta || !alphaN_partials) return -(int)hipErrorInvalidValue;
+    const long n = h->plugin->n_unknowns();
+    if (h->f64) {
+        thallo::Vectors64 v; v.n = n; v.n_alloc = thallo_hip_vector_elems(n);
+        v.r = (double*)r; v.diag = (double*)diag; v.pre = (double*)pre; v.z = (double*)z; v.p = (double*)p; v.delta = (double*)delta;
+        return h->plugin->f64()->pcg_init64(h->ctx, v, (double*)alphaN_partials);
+    }
+    thallo::SolverVectors v; v.n = n; v.n_alloc = thallo_hip_vector_elems(n);
+    v.r = (float*)r; v.diag = (float*)diag; v.pre = (float*)pre; v.z = (float*)z; v.p[0] = (float*)p; v.delta = (float*)delta;
+    return h->plugin->pcg_init(h->ctx, v, 0, (float*)alphaN_partials);
+}
+// PCGStep1: Ap = J^T J p, the partials of p . Ap (their number is the return value)
+extern "C" int thallo_hip_genprobe_apply_jtj(void* handle, const void* p, void* Ap, void* alphaD_partials)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h || !p || !Ap || !alphaD_partials) return -(int)hipErrorInvalidValue;
+    if (h->f64) {
+        thallo::Vectors64 v; v.n = h->plugin->n_unknowns(); v.n_alloc = thallo_hip_vector_elems(v.n);
+        return h->plugin->f64()->apply_jtj64(h->ctx, v, (const double*)p, (double*)Ap, (double*)alphaD_partials);
+    }
+    return h->plugin->apply_jtj(h->ctx, (const float*)p, (float*)Ap, (float*)alphaD_partials);
+}
+extern "C" int thallo_hip_genprobe_set_row_slab(void* handle, int row0, int row1)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h) return -(int)hipErrorInvalidValue;
+    const int rc = h->plugin->set_row_slab(row0, row1); if (rc < 0) return rc;
+    return h->plugin->slab_setup_ok() ? 0 : (thallo::set_error("%s", h->plugin->slab_setup_error()), -1);
+}
+extern "C" int thallo_hip_genprobe_set_slab_global(void* handle, int global_row0, int global_rows)
+{ GenProbe* h = (GenProbe*)handle; return h ? h->plugin->set_slab_global(global_row0, global_rows) : -(int)hipErrorInvalidValue; }
+extern "C" int thallo_hip_genprobe_slab_ghost_rows(void* handle) { GenProbe* h = (GenProbe*)handle; return h && h->plugin->supports_row_slabs() ? h->plugin->slab_ghost_rows() : -1; }
+// what = 0: the names of the generated kernels this handle has launched since open; 1: of every kernel the plugin took from its modules (hipModuleGetFunction; the slab
+// unit's once it is compiled); 2: of those launched since the last call with what = 2 (one case's launches).  Each name followed by ';'; the text lives until the next call on this handle.
+extern "C" const char* thallo_hip_genprobe_kernels(void* handle, int what)
+{
+    GenProbe* h = (GenProbe*)handle; if (!h) return nullptr;
+    h->ever.insert(h->launched.begin(), h->launched.end());
+    if (what == 1) h->text = h->plugin->kernel_names();
+    else { h->text.clear(); for (auto& n : (what == 2 ? h->launched : h->ever)) h->text += n + ";"; if (what == 2) h->launched.clear(); }
+    return h->text.c_str();
+}
 
 // Known-answer test of the wave64 primitives the generated kernels use -- the text they are generated with, compiled here with hipRTC (tests/cuda_unit_tests/
 // ballot.t:11, get_peers.t:12, reduce_peers.t:14 restated for 64 lanes).  One wave: out_ballot = max over the lanes of ballot(lane != 0) (the reference: 0xFFFFFFFE
